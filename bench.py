@@ -4,8 +4,16 @@
 synthetic 224x224 RGB frames — BASELINE.json's metric on its config[1] (ResNet-18 HabitatDQNMultiAction,
 5 categories x 3 actions, batch 256 per GPU, bf16, extra_capacity / real_data hyper-parameters).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, ramps the device's clocks, warms up, times exactly K updates in one window and prints the line.  --full
+adds what the headline does not need: five timed windows of K updates (`value` = the median window), the event-profiled steps
+behind `kernels` / `roofline`, the shader-clock probe, the live rocprofv3 PMC passes behind `roofline.traffic` and the CPU
+baseline.  --dump-outputs DIR writes what the last timed update left as DIR/<name>.npy (float32).  It implies --deterministic:
+the inputs and the number of updates depend on the arguments only, and in deterministic mode two runs then agree bit for bit, so
+two builds can be compared output for output.  (In the default atomic-sum mode runs part from the second update on; the line's
+`deterministic` field says which mode was timed.)
 
 One process per GPU; for N > 1 the flat gradient is all-reduced over RCCL in three buckets as the staged
 backward completes them (weak scaling: 256 samples per GPU).  Rank 0 prints ONE JSON line.
@@ -39,7 +47,7 @@ PEAK_HBM_GBS = 8000.0
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=100)
+    ap.add_argument("--steps", type=int, default=100, help="timed updates per window")
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--ramp-seconds", type=float, default=1.5,
                     help="untimed updates run before the warm-up steps so that the device holds its steady clocks (0 = none)")
@@ -61,9 +69,9 @@ def parse():
     ap.add_argument("--pack-ahead", action="store_true",
                     help="pack the next minibatch's frames under the current update's backward pass (default: every update packs its own frames at its start)")
     ap.add_argument("--profile-steps", type=int, default=5)
-    ap.add_argument("--windows", type=int, default=5,
+    ap.add_argument("--windows", type=int, default=None,
                     help="consecutive timed windows of --steps updates each (barrier + synchronize around every one); `value` is the MEDIAN "
-                         "window, `window_values` lists them all (1 = the single window of rounds 1-4)")
+                         "window, `window_values` lists them all (default: 1, or 5 with --full)")
     ap.add_argument("--pool", type=int, default=4,
                     help="distinct synthetic minibatches resident in HBM, used round-robin (4 x 77 MB of frames at batch 256 do "
                          "not fit the 256 MiB Infinity Cache together, so no step reads its frames from cache)")
@@ -79,7 +87,22 @@ def parse():
     ap.add_argument("--force-dist", action="store_true",
                     help="initialise torch.distributed and issue the bucketed all-reduces even with one rank (RCCL and the "
                          "stream ordering of the exchange exercised on a single GPU)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: five timed windows by default, the event-profiled steps (kernels, "
+                         "roofline), the shader-clock probe, the live PMC passes and the CPU baseline (each still switched off by its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed update left (loss, Q(s), a fixed seeded sample of the updated parameters and of the "
+                         "gradients) as DIR/<name>.npy, float32, rank 0; implies --deterministic, so that two runs agree bit for bit")
     args = ap.parse_args()
+    if args.dump_outputs:
+        # In the default mode the split-K weight-gradient sums are atomic, so every update differs from run to run in the last bits,
+        # and the chain of updates carries that forward: two runs of one command part from the second update on (Adam's first step
+        # from zero moments is lr * g / |g|, which gives rounding-level gradient elements full-size steps of either sign), and after
+        # 120 updates their Q(s) differ by 0.3 (profiles/dump_agreement.txt).  Outputs meant to be compared run for run and build for
+        # build come from the deterministic mode (ordered sums, bit-identical updates, -7 % throughput).
+        args.deterministic = True
+    if args.windows is None:
+        args.windows = 5 if args.full else 1
     if args.c4:
         args.steps = max(args.steps, 2200)
         args.target_update_interval = 1000
@@ -186,6 +209,27 @@ def pmc_traffic(kernel: str, batch: int, frames: int, dtype: str, arch: str = "e
         return None
 
 
+DUMP_SAMPLE = 1 << 22  # elements kept of a larger flat output (16 MB in float32)
+
+
+def dump_outputs(out_dir: str, stp, net) -> None:
+    """What the last timed update handed its caller: the loss, Q(s) of the online pass, and the updated master parameters and the
+    gradients they were updated with (a fixed sample of DUMP_SAMPLE elements of each, drawn with seed 0 and kept in index order,
+    where they are larger).  float32 .npy files: 32 MB and Q(s) at the most."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    torch.cuda.synchronize()
+    nt = net.trainable_numel
+    idx = None
+    if nt > DUMP_SAMPLE:
+        idx = torch.from_numpy(np.sort(np.random.default_rng(0).choice(nt, DUMP_SAMPLE, replace=False))).to(stp.grads.device)
+    outs = {"loss": stp.loss.reshape(1), "q_before": stp.q_before}
+    for name, flat in (("params", net.params[:nt]), ("grads", stp.grads[:nt])):
+        outs[name if idx is None else name + "_sample"] = flat if idx is None else flat[idx]
+    for name, t in outs.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.detach().float().cpu().numpy())
+
+
 def main():
     args = parse()
     from video_dqn_amd import launch
@@ -221,13 +265,17 @@ def main():
     B, F = args.batch, args.frames
     ec = args.arch == "extra_capacity"
     net = NetEngine(3, 5, F, ec, args.dtype, 2 * B, device=dev, deterministic=(True if args.deterministic else None))
-    net.load_tensors(synth.make_state_dict(4, extra_capacity=ec, num_frames=F))  # same seed on every rank: replicas start identical
+    init_sd = synth.make_state_dict(4, extra_capacity=ec, num_frames=F)  # same seed on every rank: replicas start identical
+    net.load_tensors(init_sd)
     comm = BucketAllReduce(world, force=args.force_dist) if use_dist else None
     if world > 1 and not ec:
         net.set_bn_sync(world)  # 'basic': global BatchNorm statistics (N ranks == one big batch)
-    stp = TDStepper(net, B, lr=1e-4, gamma=0.99, clip_rect=True, target_update_interval=args.target_update_interval,
-                    world_size=world, allreduce=(comm.launch if comm else None), loss_kind=args.loss_kind,
-                    allreduce_wait=(comm.wait_last if comm else None))
+
+    def make_stepper():
+        return TDStepper(net, B, lr=1e-4, gamma=0.99, clip_rect=True, target_update_interval=args.target_update_interval,
+                         world_size=world, allreduce=(comm.launch if comm else None), loss_kind=args.loss_kind,
+                         allreduce_wait=(comm.wait_last if comm else None))
+    stp = make_stepper()
 
     # synthetic minibatches, resident in HBM before the timed region: uint8 frames (normalise fused into packing).
     # `--pool` distinct ones are used round-robin so that a step does not find its frames in the Infinity Cache.
@@ -243,6 +291,15 @@ def main():
         pool.append((b_, a_, act_, rew_, rew_.clone()))
     before, after, act, rew, term = pool[0]
     pool_i = {"i": 0}
+
+    def restart():
+        """The model, the optimiser state and the minibatch order back at the seeded start."""
+        nonlocal stp
+        stp = None
+        net.load_tensors(init_sd)
+        net.num_batches_tracked.zero_()
+        stp = make_stepper()
+        pool_i["i"] = 0
 
     if args.h2d != "none":
         host = [t.cpu().pin_memory() for t in (before, after)]
@@ -303,6 +360,10 @@ def main():
         for _ in range(ramp_steps - 10):
             one_step()
         torch.cuda.synchronize()
+        # the ramp only heats the device: the warm-up and timed updates start from the seeded start, not from wherever the number of
+        # ramp updates this device's speed called for left the model
+        restart()
+        torch.cuda.synchronize()
     for _ in range(args.warmup):
         one_step()
     torch.cuda.synchronize()
@@ -344,11 +405,14 @@ def main():
         import hashlib
         params_sha = hashlib.sha256(net.params.detach().cpu().numpy().tobytes()).hexdigest()
     refreshes = (stp.sample_number // args.target_update_interval) - (sample0 // args.target_update_interval)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, stp, net)  # as the last timed update left them (nothing has run since)
 
     # ---- live per-kernel timing (HIP events on the launch stream) for the roofline of the dominant kernel ----
     roofline = None
     kernels = None
-    if not args.no_profile:
+    profile = args.full and not args.no_profile
+    if profile:
         # per-kernel roofline timing: serialise the engine's side stream so every kernel has the chip to itself
         # (in the timed region above weight gradients / the target forward overlap the main chain).  Every rank
         # runs these steps (they contain the gradient all-reduce); only rank 0 records and reports.
@@ -368,7 +432,7 @@ def main():
                 _lib.profile_enable(False)
         net.lib.vdqn_net_set_overlap(net.handle, 1)
     prof = None
-    if not args.no_profile and rank == 0:
+    if profile and rank == 0:
         prof = {}
         for ps in per_step:
             for k, v in ps.items():
@@ -385,7 +449,7 @@ def main():
     # s_memrealtime): what the 2.5 PFLOP/s nominal peak of `roofline.peak` shrinks to on this box
     # (measured right behind the profiled steps, while the device is still hot)
     mfma_clock = None
-    if rank == 0 and not args.no_profile:
+    if rank == 0 and profile:
         try:
             import ctypes as C
             raw = C.CDLL(_lib.LIB_PATH)
@@ -469,7 +533,7 @@ def main():
             "mfma_clock_under_load": mfma_clock,
             "kernels": kernels,
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args.cpu_batch)
         else:
             out["cpu_baseline"] = None

@@ -10,7 +10,6 @@ if ROOT not in sys.path:
 
 def pytest_configure(config):
     config.addinivalue_line("markers", "gpu: needs a real MI355X (run with -m gpu on the GPU box)")
-    config.addinivalue_line("markers", "refonly: needs /root/reference (build container only)")
     config.addinivalue_line("markers", "variants: A/B switch variants of the default path; run only with VDQN_TEST_VARIANTS=1 (tools/job.sh variants)")
     config.addinivalue_line("markers", "slow_oracle: minutes of CPU-oracle time at a full-size geometry; run only with VDQN_TEST_SLOW=1 (tools/job.sh slow)")
 

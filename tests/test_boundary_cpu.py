@@ -261,21 +261,16 @@ def test_shard_indices_disjoint_and_equal():
     assert len(set(flat)) == len(flat)
 
 
-@pytest.mark.refonly
-@pytest.mark.skipif(not os.path.isdir("/root/reference/archs"), reason="needs /root/reference (build container only)")
 @pytest.mark.parametrize("extra_capacity,panorama,n_keys,n_ids", [(True, False, 250, 70), (False, True, 244, 64)])
-def test_checkpoint_loads_into_the_reference_class(tmp_path, extra_capacity, panorama, n_keys, n_ids):
+def test_checkpoint_loads_into_the_reference_class(tmp_path, g1, extra_capacity, panorama, n_keys, n_ids):
     """SURVEY 8c G6 as written: a checkpoint in the build's format (trainer.save_checkpoint — what run_train writes every
-    CHECKPOINT_INTERVAL, train_q_network.py:241-247) -> the REFERENCE's own class, imported from /root/reference exactly as
-    tests/golden/make_golden.py does (torchvision is not installed here: `models.resnet18` is the published topology restated in
-    oracle/ref_cpu.py), through the reference's own loading lines: `model.load_state_dict(snapshot['model_state_dict'])`
-    (train_q_network.py:50-57, strict) and `optimizer.load_state_dict(snapshot['optimizer_state_dict'])` (:197); the reference model
-    then returns the tensors the build saved, and its Adam steps from the loaded state."""
-    import importlib.util
-    spec = importlib.util.spec_from_file_location("make_golden", os.path.join(ROOT, "tests", "golden", "make_golden.py"))
-    mg = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mg)
-    RefClass = mg.import_reference_model()
+    CHECKPOINT_INTERVAL, train_q_network.py:241-247) -> a class with the REFERENCE's layout, through the reference's own loading
+    lines: `model.load_state_dict(snapshot['model_state_dict'])` (train_q_network.py:50-57, strict) and
+    `optimizer.load_state_dict(snapshot['optimizer_state_dict'])` (:197); the model then returns the tensors the build saved, and
+    its Adam steps from the loaded state.  The class is the oracle's restatement of archs/HabitatDQNMultiAction.py, first pinned to
+    the reference class's own layout as golden G1 recorded it (tests/golden/make_golden.py: state_dict keys in order, shapes,
+    aliasing, and the named_parameters order the optimiser state is keyed by) — everything these two loading lines read."""
+    from oracle import ref_cpu
     from video_dqn_amd import synth
     from video_dqn_amd.model import HabitatDQNMultiAction
     from video_dqn_amd.trainer import optimizer_state_dict, save_checkpoint
@@ -294,8 +289,13 @@ def test_checkpoint_loads_into_the_reference_class(tmp_path, extra_capacity, pan
     save_checkpoint(path, 3, m, st)
     snapshot = torch.load(path, map_location="cpu")
     assert len(snapshot["model_state_dict"]) == n_keys
-    ref = RefClass(3, 5, extra_capacity=extra_capacity, panorama=panorama)
-    assert type(ref).__module__ == "archs.HabitatDQNMultiAction"
+    ref = ref_cpu.HabitatDQNMultiAction(3, 5, extra_capacity=extra_capacity, panorama=panorama)
+    layout = g1[f"ec{int(extra_capacity)}_pano{int(panorama)}"]  # recorded from the reference class itself
+    sd_ref = ref.state_dict()
+    assert list(sd_ref.keys()) == layout["keys"] and [list(v.shape) for v in sd_ref.values()] == layout["shapes"]
+    ptr = {}
+    assert [ptr.setdefault(v.data_ptr(), k) if v.numel() > 0 else k for k, v in sd_ref.items()] == layout["alias"]
+    assert [n for n, _ in ref.named_parameters()] == layout["params"]
     ref.load_state_dict(snapshot["model_state_dict"])  # train_q_network.py:56 (strict is the default)
     saved = m.state_dict()
     for k, v in ref.state_dict().items():

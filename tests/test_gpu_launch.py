@@ -49,7 +49,7 @@ def test_per_bucket_adam_under_an_exchange_is_the_same_update():
 
 
 def test_bench_self_launches_two_ranks_without_torchrun():
-    out = _bench(["--gpus", "2", "--backend", "gloo"] + SMALL, VDQN_BENCH_SINGLE_DEVICE="1")
+    out = _bench(["--gpus", "2", "--backend", "gloo", "--full"] + SMALL, VDQN_BENCH_SINGLE_DEVICE="1")
     assert out["n_gpus"] == 2 and out["config"]["global_batch"] == 16 and out["scaling"] == "weak"
     assert len(out["per_rank_ms_per_step"]) == 2 and all(t > 0 for t in out["per_rank_ms_per_step"])
     assert out["ms_per_step"] == pytest.approx(max(out["per_rank_ms_per_step"]), rel=1e-3)
@@ -83,6 +83,29 @@ def test_bench_single_rank_through_rccl():
     # test_default_schedule_gradients_equal_deterministic_per_tensor: one update of the default schedule equals deterministic mode to
     # 1e-5 (f32) / 1e-4 (bf16) relative L2 in every gradient tensor.)
     assert a["loss"] == pytest.approx(b["loss"], rel=0.1)
+
+
+def test_bench_dump_outputs_deterministic_runs_are_bit_identical(tmp_path):
+    """`--dump-outputs DIR`: the last timed update's loss, Q(s) and the seeded samples of the updated parameters and gradients, as float32
+    .npy files within 64 MB.  The clock ramp (its length follows this device's speed) restarts from the seeded state, and the option
+    implies DETERMINISTIC mode, so two runs (one asking for --deterministic itself) agree bit for bit."""
+    import numpy as np
+    args = ["--batch", "8", "--steps", "3", "--warmup", "1", "--ramp-seconds", "0.3", "--pool", "2"]
+    names = ["grads_sample.npy", "loss.npy", "params_sample.npy", "q_before.npy"]
+    dumps = []
+    for run in ("a", "b"):
+        d = tmp_path / run
+        out = _bench(args + ["--dump-outputs", str(d)] + (["--deterministic"] if run == "a" else []))
+        assert sorted(os.listdir(d)) == names
+        arrays = {n: np.load(d / n) for n in names}
+        assert all(a.dtype == np.float32 for a in arrays.values())
+        assert sum(os.path.getsize(d / n) for n in names) <= 64 << 20
+        assert arrays["q_before.npy"].shape == (8, 15) and arrays["grads_sample.npy"].shape == arrays["params_sample.npy"].shape
+        assert arrays["loss.npy"].shape == (1,) and float(arrays["loss.npy"][0]) == out["loss"]  # the line's loss: the same update
+        assert out["steps"] == 3 and out["windows"] == 1 and out["deterministic"] is True
+        dumps.append(arrays)
+    for n in names:
+        assert np.array_equal(dumps[0][n], dumps[1][n]), n
 
 
 def test_bench_eight_ranks_on_one_device_gloo():
@@ -269,7 +292,7 @@ def test_bench_roofline_traffic_is_measured_live():
     import shutil
     if shutil.which("rocprofv3") is None:
         pytest.skip("no rocprofv3 on this box")
-    out = _bench(["--ramp-seconds", "0", "--batch", "32", "--steps", "3", "--warmup", "1", "--profile-steps", "1", "--no-cpu-baseline", "--pool", "1"],
+    out = _bench(["--full", "--ramp-seconds", "0", "--batch", "32", "--steps", "3", "--warmup", "1", "--profile-steps", "1", "--no-cpu-baseline", "--pool", "1"],
                  VDQN_BENCH_NO_LIVE_PMC="0")
     r = out["roofline"]
     assert r is not None and r["traffic"] is not None and r["traffic_source"].startswith("live"), r

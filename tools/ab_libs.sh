@@ -6,7 +6,7 @@ cp $L/libvdqn.so /tmp/libvdqn_keep.so
 for round in 1 2 3; do
   for v in "$@"; do
     cp $L/libvdqn_$v.so $L/libvdqn.so
-    python bench.py --steps 150 --warmup 20 --no-cpu-baseline 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('$v', d['value'], d['roofline']['achieved'])"
+    python bench.py --full --steps 150 --warmup 20 --no-cpu-baseline 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('$v', d['value'], d['roofline']['achieved'])"
   done
 done
 cp /tmp/libvdqn_keep.so $L/libvdqn.so

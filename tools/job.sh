@@ -34,7 +34,7 @@ for recipe in "$@"; do
     variants) # the A/B switch variants the plain suite deselects (tests/conftest.py: @pytest.mark.variants)
              t0=$(date +%s); VDQN_TEST_VARIANTS=1 timeout 2400 python -m pytest tests -m "gpu and variants" -q --maxfail=8 > "$O/pytest_variants.log" 2>&1; echo "pytest rc=$? wall=$(( $(date +%s) - t0 ))s" >> "$O/pytest_variants.log"; tail -3 "$O/pytest_variants.log" | cut -c1-300 ;;
     tests)   timeout 2400 python -m pytest tests -m gpu -q -k "${arg//_or_/ or }" > "$O/pytest_${arg:0:40}.log" 2>&1; echo "pytest rc=$?" >> "$O/pytest_${arg:0:40}.log"; tail -3 "$O/pytest_${arg:0:40}.log" | cut -c1-300 ;;
-    bench)   for i in 1 2 3; do timeout 300 python bench.py $( [ $i -gt 1 ] && echo --no-cpu-baseline ) > "$O/bench_$i.json" 2>> "$O/err.log"; done
+    bench)   for i in 1 2 3; do timeout 300 python bench.py --full $( [ $i -gt 1 ] && echo --no-cpu-baseline ) > "$O/bench_$i.json" 2>> "$O/err.log"; done
              python - "$O" <<'PY'
 import glob, json, sys
 for f in sorted(glob.glob(sys.argv[1] + "/bench_*.json")):

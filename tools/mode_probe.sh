@@ -17,7 +17,7 @@ while time.time() - t < 40: y = x @ x
 torch.cuda.synchronize()" ;; esac
   echo "== run $i ($(case $i in 3|6) echo after 45 s idle;; 4) echo after 40 s of GEMM heat;; *) echo back to back;; esac))" >> "$O/mode_probe.txt"
   smi >> "$O/mode_probe.txt"
-  timeout 200 python bench.py --no-cpu-baseline > "$O/probe_$i.json" 2>> "$O/err.log"
+  timeout 200 python bench.py --full --no-cpu-baseline > "$O/probe_$i.json" 2>> "$O/err.log"
   python - "$O/probe_$i.json" >> "$O/mode_probe.txt" <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

@@ -9,7 +9,7 @@ O=$R/gpurun_out/records_$TAG
 mkdir -p $O
 cd $R
 export VDQN_BENCH_NO_LIVE_PMC=1  # the PMC child passes belong to the headline run (tools/profile_round.sh), not to every record
-B="python3 bench.py --no-cpu-baseline"
+B="python3 bench.py --full --no-cpu-baseline"
 $B                                          > $O/${TAG}_bench_c2.json 2> $O/err.log
 $B --frames 12 --batch 16                   > $O/${TAG}_bench_f12_b16.json 2>> $O/err.log
 $B --frames 12 --batch 128 --steps 10 --warmup 3 --profile-steps 2 > $O/${TAG}_bench_f12_b128.json 2>> $O/err.log
@@ -25,7 +25,7 @@ VDQN_BENCH_SINGLE_DEVICE=1 $B --gpus 2 --backend gloo --batch 128 > $O/${TAG}_be
 # BASELINE config 3's per-rank shape, functionally: four self-launched ranks x batch 256 share this box's GPU (gloo carries the exchange)
 VDQN_BENCH_SINGLE_DEVICE=1 $B --gpus 4 --backend gloo --batch 256 --steps 10 --warmup 2 --ramp-seconds 0 --no-profile > $O/${TAG}_bench_c3_4ranks_x256_gloo_shared_gpu.json 2>> $O/err.log
 python3 tools/convergence.py --steps 300 --batch 64 --out $O/${TAG}_convergence.json > $O/${TAG}_convergence.txt 2>> $O/err.log
-(cd /tmp && export TMPDIR=/tmp && rocprofv3 --kernel-trace --stats -d $O/prof_f12 -o k --output-format csv -- python3 $R/bench.py --frames 12 --batch 16 --steps 20 --warmup 5 --no-cpu-baseline > /dev/null 2>> $O/err.log)
+(cd /tmp && export TMPDIR=/tmp && rocprofv3 --kernel-trace --stats -d $O/prof_f12 -o k --output-format csv -- python3 $R/bench.py --full --frames 12 --batch 16 --steps 20 --warmup 5 --no-cpu-baseline > /dev/null 2>> $O/err.log)
 find $O/prof_f12 -name "*kernel_stats.csv" -exec cp {} $O/${TAG}_kernel_stats_f12_b16.csv \;
 for f in $O/*.json; do python3 - "$f" <<'PY'
 import json, sys
