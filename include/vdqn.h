@@ -15,6 +15,11 @@
  *   - activations are NHWC; `dtype` selects the storage/compute type of activations and packed weights:
  *       VDQN_F32  : f32 storage, exact-f32 MFMA (v_mfma_f32_16x16x4_f32)   — the parity mode
  *       VDQN_BF16 : bf16 storage, v_mfma_f32_16x16x32_bf16, f32 accumulate — the throughput mode
+ *       VDQN_F32X3: f32 storage (everything as VDQN_F32), the GEMMs as split bf16 x 3: each f32 operand is split into
+ *                   hi = bf16(x), lo = bf16(x - hi) and a product is hi*hi + hi*lo + lo*hi on v_mfma_f32_16x16x32_bf16
+ *                   (~2^-16 relative per product, f32 accumulate) — f32-grade results at bf16 MFMA rates.  Accepted by
+ *                   vdqn_conv2d, vdqn_conv2d_wgrad, vdqn_stem_conv_pool(_n) and vdqn_net_config; every other entry takes
+ *                   VDQN_F32 for the same tensors (the engine calls them so) and rejects it.
  *     master parameters, gradients, Adam state and Q-values are always f32.
  */
 #ifndef VDQN_H_
@@ -29,6 +34,7 @@ extern "C" {
 
 #define VDQN_F32 0
 #define VDQN_BF16 1
+#define VDQN_F32X3 2 /* f32 tensors, GEMMs computed as split bf16 x 3 (see above) */
 
 #define VDQN_OK 0
 #define VDQN_ERR_INVALID (-1)
@@ -85,7 +91,7 @@ typedef struct vdqn_conv_args {
   int32_t n_img, hi, wi, ci, pix_stride;
   int32_t ho, wo, co, ldo;
   int32_t r, s, stride, pad;
-  int32_t mode, relu, dtype;
+  int32_t mode, relu, dtype; /* dtype: VDQN_F32 | VDQN_BF16 | VDQN_F32X3 */
   /* Optional sibling 1x1 / stride-2 / pad-0 convolution fused into a 3x3 / stride-2 / pad-1 call: the downsample branch of a
    * ResNet BasicBlock (torchvision resnet.py `downsample`; archs/HabitatDQNMultiAction.py:30), whose input pixel is the 3x3's
    * centre tap.  All NULL / 0 = no sibling.
@@ -122,7 +128,7 @@ typedef struct vdqn_wgrad_args {
   int32_t n_img, hi, wi, ci, pix_stride;
   int32_t ho, wo, co, ldg;
   int32_t r, s, stride, pad;
-  int32_t splitk, dtype;
+  int32_t splitk, dtype;  /* VDQN_F32 | VDQN_BF16 | VDQN_F32X3 */
   void* workspace;          /* NULL: atomics; else >= vdqn_conv2d_wgrad_workspace_bytes(a) bytes, 16-byte aligned */
   int64_t workspace_bytes;
 } vdqn_wgrad_args;
@@ -269,7 +275,7 @@ typedef struct vdqn_net_config {
   int32_t num_frames;      /* F: 1, or 4 for PANORAMA/PREVIOUS_IMAGES (archs/...:16-19); any F >= 1 accepted */
   int32_t extra_capacity;  /* 1: ARCHITECTURE 'extra_capacity' (BatchNorm on running stats, conv+MLP head);
                               0: 'basic' (defaults.py:14 — train-mode BatchNorm, average pool + one Linear) */
-  int32_t dtype;           /* VDQN_F32 | VDQN_BF16 */
+  int32_t dtype;           /* VDQN_F32 | VDQN_BF16 | VDQN_F32X3 (sizes, layouts and tensors as VDQN_F32) */
   int32_t max_batch;       /* largest per-call sample count B the workspaces are sized for */
   int32_t deterministic;   /* 1: run-to-run bit-identical updates (the reference's cudnn.deterministic = True,
                               train_q_network.py:88-89): weight gradients through the two-stage ordered reduction of

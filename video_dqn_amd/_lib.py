@@ -11,8 +11,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # VDQN_LIB=<name> loads lib/libvdqn_<name>.so (a variant built with VDQN_LIB_OUT=<name>: A/B and diagnostic builds)
 LIB_PATH = os.path.join(_HERE, "lib", f"libvdqn{'_' + os.environ['VDQN_LIB'] if os.environ.get('VDQN_LIB') else ''}.so")
 
-VDQN_F32, VDQN_BF16 = 0, 1
-ABI_VERSION = 14
+VDQN_F32, VDQN_BF16, VDQN_F32X3 = 0, 1, 2
+ABI_VERSION = 15
 
 c_i32, c_i64, c_f32, c_vp = C.c_int32, C.c_int64, C.c_float, C.c_void_p
 

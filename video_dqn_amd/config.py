@@ -9,7 +9,7 @@
     over the defaults, LOSS_CLIP validation, every key copied onto the instance, ``device``/``gpu_id``.
 
 Keys added by this build (all optional, defaults reproduce the reference): BATCH_SIZE (the reference
-hard-codes 16, train_q_network.py:98), NUM_WORKERS (8), COMPUTE_DTYPE ('bf16' | 'f32'), NUM_FRAMES (0 = the
+hard-codes 16, train_q_network.py:98), NUM_WORKERS (8), COMPUTE_DTYPE ('bf16' | 'f32' | 'bf16x3': f32 storage, GEMMs as split bf16 x 3), NUM_FRAMES (0 = the
 reference's rule: 4 if PANORAMA or PREVIOUS_IMAGES else 1), SYNTHETIC_DATA (train on generated frames), DEVICE_RESIDENT_DATA ('auto' | 'on' | 'off': keep a decoded-frame shard
 dataset in HBM and gather minibatches on the device), SHARD_INPUT ('stream' | 'dataloader': how a shard dataset that is NOT
 resident reaches the GPU — memory-mapped shards + native gather into pinned double buffers, or torch's DataLoader),

@@ -30,6 +30,19 @@ __device__ __forceinline__ bf16raw f32_to_bf16(float f) {
   __bf16 b = (__bf16)f;  // v_cvt_pk_bf16_f32: RNE, NaN stays NaN
   return __builtin_bit_cast(bf16raw, b);
 }
+// bf16x3 (VDQN_F32X3): 8 f32 values of one MFMA operand slot split into two bf16x8 fragments, x = hi + lo + d with
+// hi = RNE bf16(x), lo = RNE bf16(x - hi) (the difference is exact in f32) and |d| <= 2^-17 |x|.  The product of two split
+// operands is then hi*hi + hi*lo + lo*hi (three v_mfma_f32_16x16x32_bf16, f32 accumulate) up to ~2^-16 relative.  x0 holds
+// slots 0..3, x1 slots 4..7.  The plain __bf16 casts emit v_cvt_pk_bf16_f32 (NaN stays NaN).
+__device__ __forceinline__ void split_bf16x8(const f32x4 x0, const f32x4 x1, bf16x8& hi, bf16x8& lo) {
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const float v = j < 4 ? x0[j] : x1[j - 4];
+    const __bf16 h = (__bf16)v;
+    hi[j] = h;
+    lo[j] = (__bf16)(v - (float)h);
+  }
+}
 template <typename T> __device__ __forceinline__ float to_f32(T v);
 template <> __device__ __forceinline__ float to_f32<float>(float v) { return v; }
 template <> __device__ __forceinline__ float to_f32<bf16raw>(bf16raw v) { return bf16_to_f32(v); }

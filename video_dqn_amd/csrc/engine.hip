@@ -29,7 +29,7 @@ void vdqn_set_error(const char* fmt, ...) {
   va_end(ap);
 }
 extern "C" const char* vdqn_last_error(void) { return g_err; }
-extern "C" int vdqn_abi_version(void) { return 14; }
+extern "C" int vdqn_abi_version(void) { return 15; }
 extern "C" int32_t vdqn_abi_struct_size(int32_t which) {
   switch (which) {
     case 0: return (int32_t)sizeof(vdqn_conv_args);
@@ -109,7 +109,8 @@ inline int64_t align_up(int64_t v, int64_t a = 256) { return (v + a - 1) / a * a
 }  // namespace
 
 struct vdqn_net {
-  vdqn_net_config cfg;
+  vdqn_net_config cfg;  // cfg.dtype is the STORAGE dtype: VDQN_F32 for a VDQN_F32X3 engine (every pointwise entry takes that)
+  int gemm_dtype;       // dtype of the GEMM calls (convolutions, linear layers, weight gradients, stem): the requested one
   int esz;  // bytes per activation element
   std::vector<Layer> layers;
   std::vector<vdqn_param_info> params;
@@ -886,7 +887,7 @@ vdqn_wgrad_args wgrad_shape_args(const vdqn_net* net, const Layer& L, int n_unit
   a.r = L.k_r; a.s = L.k_s;
   a.stride = L.kind == K_CONV1_S2D ? 1 : L.stride;
   a.pad = L.kind == K_CONV1_S2D ? 0 : L.pad;
-  a.splitk = 0; a.dtype = net->cfg.dtype;
+  a.splitk = 0; a.dtype = net->gemm_dtype;
   return a;
 }
 // images one vdqn_conv2d_wgrad call can take for layer L (< 2^24 output pixels, < 2 GiB per operand: 32-bit buffer offsets)
@@ -936,7 +937,7 @@ int run_conv(const vdqn_net* net, const Layer& L, const unsigned char* packed, c
   a.r = L.k_r; a.s = L.k_s;
   a.stride = L.kind == K_CONV1_S2D ? 1 : L.stride;
   a.pad = L.kind == K_CONV1_S2D ? 0 : L.pad;
-  a.mode = 0; a.relu = relu; a.dtype = net->cfg.dtype;
+  a.mode = 0; a.relu = relu; a.dtype = net->gemm_dtype;
   g_prof_alg_flops = 2.0 * n_units * L.ho * L.wo * (double)L.co * L.ci * L.r * L.s;
   if (sib) {  // the block's 1x1 / stride-2 downsample (BatchNorm folded, no ReLU): second output of the same launch
     a.wt2 = packed + sib->wf_off;
@@ -965,7 +966,7 @@ int run_dgrad(const vdqn_net* net, const Layer& L, const unsigned char* packed, 
   a.n_img = n_units; a.hi = L.ho; a.wi = L.wo; a.ci = L.co_pad; a.pix_stride = L.co_pad;
   a.ho = L.hi; a.wo = L.wi; a.co = L.k_ci; a.ldo = L.k_ci;
   a.r = L.k_r; a.s = L.k_s; a.stride = L.stride; a.pad = L.pad;
-  a.mode = 1; a.relu = 0; a.dtype = net->cfg.dtype;
+  a.mode = 1; a.relu = 0; a.dtype = net->gemm_dtype;
   g_prof_alg_flops = 2.0 * n_units * L.ho * L.wo * (double)L.co * L.ci * L.r * L.s;
   if (sib) {  // + the data gradient of the block's 1x1 / stride-2 downsample, accumulated in the same tiles
     a.in2 = sib_gy;
@@ -1037,7 +1038,7 @@ int forward_impl(const vdqn_net* net, const unsigned char* packed, const void* t
   } else {
     const Layer& L1 = net->layers[net->l_conv1];
     prof_layer(L1, n);
-    RC(vdqn_stem_conv_pool_n(t_in, packed + L1.wf_off, reinterpret_cast<const float*>(packed + L1.bias_off), acts + A.pool, acts + A.idx, n, n_idx, dt, st));
+    RC(vdqn_stem_conv_pool_n(t_in, packed + L1.wf_off, reinterpret_cast<const float*>(packed + L1.bias_off), acts + A.pool, acts + A.idx, n, n_idx, net->gemm_dtype, st));
   }
   const unsigned char* x = acts + A.pool;
   for (int b = 0; b < 8; ++b) {
@@ -1123,13 +1124,15 @@ int forward_train_impl(const vdqn_net* net, const unsigned char* packed, const f
 extern "C" int vdqn_net_create(const vdqn_net_config* cfg, vdqn_net** out) {
   VDQN_CHECK(cfg && out, "vdqn_net_create: null arg");
   VDQN_CHECK(cfg->extra_capacity == 0 || cfg->extra_capacity == 1, "vdqn_net_create: extra_capacity must be 0 or 1");
-  VDQN_CHECK(cfg->dtype == VDQN_F32 || cfg->dtype == VDQN_BF16, "vdqn_net_create: bad dtype %d", cfg->dtype);
+  VDQN_CHECK(cfg->dtype == VDQN_F32 || cfg->dtype == VDQN_BF16 || cfg->dtype == VDQN_F32X3, "vdqn_net_create: bad dtype %d", cfg->dtype);
   VDQN_CHECK(cfg->action_dim >= 1 && cfg->num_classes >= 1 && cfg->action_dim * cfg->num_classes <= 64, "vdqn_net_create: action_dim*num_classes must be in 1..64");
   VDQN_CHECK(cfg->num_frames >= 1 && cfg->num_frames <= 64, "vdqn_net_create: num_frames out of range");
   VDQN_CHECK(cfg->max_batch >= 1, "vdqn_net_create: max_batch");
   VDQN_CHECK(cfg->deterministic == 0 || cfg->deterministic == 1, "vdqn_net_create: deterministic must be 0 or 1");
   vdqn_net* net = new vdqn_net();
   net->cfg = *cfg;
+  net->gemm_dtype = cfg->dtype;
+  if (cfg->dtype == VDQN_F32X3) net->cfg.dtype = VDQN_F32;  // f32 layout, tensors and pointwise kernels; only the GEMMs differ
   net->esz = cfg->dtype == VDQN_BF16 ? 2 : 4;
   {
     const char* no = getenv("VDQN_NO_OVERLAP");

@@ -52,8 +52,12 @@ namespace {
 // NS = staging buffers per operand: 2 (one K-step of DMA lead; two workgroups per CU hide the rest) or 4 (three K-steps of
 // lead, counted vmcnt waits) for launches with at most one tile per CU, where nothing else hides the ~0.85 us DMA round trip
 // of every K-step (the head's skinny GEMMs: features.8, top.*).
-template <typename T, int BM, int BN, int MODE, int WN, int NS = 2>
+// X3 (T = float only): the bf16x3 compute mode (VDQN_F32X3) — the f32 staging unchanged, the MFMA block is VDQN_MFMA_X3
+// (igemm_common.h): a lane's two K-halves of a K-step joined into one 8-slot operand, split into bf16 hi / lo and multiplied as
+// hi*hi + hi*lo + lo*hi on v_mfma_f32_16x16x32_bf16.
+template <typename T, int BM, int BN, int MODE, int WN, int NS = 2, bool X3 = false>
 __global__ __launch_bounds__(BM * WN, 2) void igemm_kernel(const IgemmParams p) {
+  static_assert(!X3 || sizeof(T) == 4, "bf16x3 splits f32 operands");
   constexpr int NT = BM * WN;   // threads: BM/64 x WN waves, each owning 64 x BN/WN
   constexpr int RPS = NT / 8;   // tile rows staged per pass (8 lanes x 16 B per 128-byte row)
   constexpr int ESZ = (int)sizeof(T);
@@ -300,6 +304,7 @@ __global__ __launch_bounds__(BM * WN, 2) void igemm_kernel(const IgemmParams p) 
     }                                                                                                                    \
   }
 #define VDQN_MFMA_ALL(SET)                                                                                               \
+  if constexpr (X3) VDQN_MFMA_X3(SET) else                                                                               \
   _Pragma("unroll") for (int h_ = 0; h_ < 2; ++h_) _Pragma("unroll") for (int f_ = 0; f_ < 4; ++f_)                     \
       _Pragma("unroll") for (int j_ = 0; j_ < NF; ++j_) {                                                                \
     if constexpr (sizeof(T) == 2) {                                                                                      \
@@ -582,9 +587,10 @@ __global__ __launch_bounds__(BM * WN, 2) void igemm_kernel(const IgemmParams p) 
 // asm, source-side swizzle (key = window row & 7), register double-buffered fragments, one barrier per K-step, the
 // LDS-free epilogue — is the generic kernel's.
 // ---------------------------------------------------------------------------------------------------------
-template <typename T, int BN, int MODE>
+template <typename T, int BN, int MODE, bool X3 = false>  // X3: bf16x3, as in igemm_kernel
 __global__ __launch_bounds__(256, BN == 64 ? 3 : 2) void igemm_win_kernel(const IgemmParams p) {
   static_assert(MODE == 0 || MODE == 1, "window kernel: forward or stride-1 data gradient");
+  static_assert(!X3 || sizeof(T) == 4, "bf16x3 splits f32 operands");
   constexpr int BM = 128, WN = 2, RPS = 32, AROWS = 4;
   constexpr int ESZ = (int)sizeof(T);
   constexpr int KC = 128 / ESZ;
@@ -765,6 +771,7 @@ __global__ __launch_bounds__(256, BN == 64 ? 3 : 2) void igemm_win_kernel(const 
     }                                                                                                                    \
   }
 #define VDQN_MFMA_ALL(SET)                                                                                               \
+  if constexpr (X3) VDQN_MFMA_X3(SET) else                                                                               \
   _Pragma("unroll") for (int h_ = 0; h_ < 2; ++h_) _Pragma("unroll") for (int f_ = 0; f_ < 4; ++f_)                     \
       _Pragma("unroll") for (int j_ = 0; j_ < NF; ++j_) {                                                                \
     if constexpr (sizeof(T) == 2) {                                                                                      \
@@ -812,18 +819,19 @@ __global__ __launch_bounds__(256, BN == 64 ? 3 : 2) void igemm_win_kernel(const 
   igemm_epilogue<T, BM, BN, MODE, WN>(p, acc, smem, m0, n0, tile_m, rows_total, pix_per_img, row_w, 0, 0, p.bias);
 }
 
-template <typename T, int BN, int MODE>
+template <typename T, int BN, int MODE, bool X3 = false>
 int launch_igemm_win(const IgemmParams& p, hipStream_t stream) {
   const size_t smem = 2 * (128 + 8) * 128 + 2 * BN * 128 + 128;
-  vdqn_ensure_dyn_smem(reinterpret_cast<const void*>(&igemm_win_kernel<T, BN, MODE>), (size_t)smem);
+  vdqn_ensure_dyn_smem(reinterpret_cast<const void*>(&igemm_win_kernel<T, BN, MODE, X3>), (size_t)smem);
   const unsigned grid = (unsigned)(p.tiles_m * p.tiles_n);
   const double esz = sizeof(T);
-  static const char* const kTag[2][2][2] = {{{"igemm_win<bf16,64,fwd>", "igemm_win<bf16,64,dgrad>"}, {"igemm_win<bf16,128,fwd>", "igemm_win<bf16,128,dgrad>"}},
-                                            {{"igemm_win<f32,64,fwd>", "igemm_win<f32,64,dgrad>"}, {"igemm_win<f32,128,fwd>", "igemm_win<f32,128,dgrad>"}}};
-  vdqn_prof_begin(kTag[sizeof(T) == 2 ? 0 : 1][BN == 128 ? 1 : 0][MODE], 2.0 * p.M * p.co * p.ktot,
+  static const char* const kTag[3][2][2] = {{{"igemm_win<bf16,64,fwd>", "igemm_win<bf16,64,dgrad>"}, {"igemm_win<bf16,128,fwd>", "igemm_win<bf16,128,dgrad>"}},
+                                            {{"igemm_win<f32,64,fwd>", "igemm_win<f32,64,dgrad>"}, {"igemm_win<f32,128,fwd>", "igemm_win<f32,128,dgrad>"}},
+                                            {{"igemm_win<bf16x3,64,fwd>", "igemm_win<bf16x3,64,dgrad>"}, {"igemm_win<bf16x3,128,fwd>", "igemm_win<bf16x3,128,dgrad>"}}};
+  vdqn_prof_begin(kTag[sizeof(T) == 2 ? 0 : (X3 ? 2 : 1)][BN == 128 ? 1 : 0][MODE], 2.0 * p.M * p.co * p.ktot,
                   esz * ((double)p.n_img * p.hi * p.wi * p.ci + (double)p.co * p.ktot + (double)p.M * p.co * (1 + (p.resid != nullptr) + (p.mask != nullptr))),
                   stream);
-  hipLaunchKernelGGL((igemm_win_kernel<T, BN, MODE>), dim3(grid), dim3(256), smem, stream, p);
+  hipLaunchKernelGGL((igemm_win_kernel<T, BN, MODE, X3>), dim3(grid), dim3(256), smem, stream, p);
   vdqn_prof_end(stream);
   VDQN_LAUNCH_CHECK();
   return VDQN_OK;
@@ -1501,47 +1509,51 @@ int launch_conv64(const IgemmParams& p, hipStream_t stream) {
   return VDQN_OK;
 }
 
-template <typename T, int BM, int BN, int MODE, int NS = 2>
+template <typename T, int BM, int BN, int MODE, int NS = 2, bool X3 = false>
 int launch_igemm(const IgemmParams& p, hipStream_t stream) {
   // 256x64 tiles: 4 waves of 64x64 (WN = 1); everything else a (BM/64) x 2 wave grid
   constexpr int WN = (BM == 256 && BN == 64) ? 1 : 2;
   const size_t smem = NS * (BM + BN) * 128;
-  vdqn_ensure_dyn_smem(reinterpret_cast<const void*>(&igemm_kernel<T, BM, BN, MODE, WN, NS>), (size_t)smem);
+  vdqn_ensure_dyn_smem(reinterpret_cast<const void*>(&igemm_kernel<T, BM, BN, MODE, WN, NS, X3>), (size_t)smem);
   const unsigned grid = (unsigned)(p.tiles_m * p.tiles_n);
   const double esz = sizeof(T);
   // one tag per kernel symbol (T, BM, BN, MODE), so bench.py rows line up with rocprofv3's kernel names
-  static const char* const kTag[2][4][3] = {{{"igemm<bf16,64,fwd>", "igemm<bf16,64,dgrad>", "igemm<bf16,64,dgrad_s2>"},
+  static const char* const kTag[3][4][3] = {{{"igemm<bf16,64,fwd>", "igemm<bf16,64,dgrad>", "igemm<bf16,64,dgrad_s2>"},
                                              {"igemm<bf16,128,fwd>", "igemm<bf16,128,dgrad>", "igemm<bf16,128,dgrad_s2>"},
                                              {"igemm<bf16,256x64,fwd>", "igemm<bf16,256x64,dgrad>", "igemm<bf16,256x64,dgrad_s2>"},
                                              {"igemm<bf16,256x128,fwd>", "igemm<bf16,256x128,dgrad>", "igemm<bf16,256x128,dgrad_s2>"}},
                                             {{"igemm<f32,64,fwd>", "igemm<f32,64,dgrad>", "igemm<f32,64,dgrad_s2>"},
                                              {"igemm<f32,128,fwd>", "igemm<f32,128,dgrad>", "igemm<f32,128,dgrad_s2>"},
                                              {"igemm<f32,256x64,fwd>", "igemm<f32,256x64,dgrad>", "igemm<f32,256x64,dgrad_s2>"},
-                                             {"igemm<f32,256x128,fwd>", "igemm<f32,256x128,dgrad>", "igemm<f32,256x128,dgrad_s2>"}}};
+                                             {"igemm<f32,256x128,fwd>", "igemm<f32,256x128,dgrad>", "igemm<f32,256x128,dgrad_s2>"}},
+                                            {{"igemm<bf16x3,64,fwd>", "igemm<bf16x3,64,dgrad>", "igemm<bf16x3,64,dgrad_s2>"},
+                                             {"igemm<bf16x3,128,fwd>", "igemm<bf16x3,128,dgrad>", "igemm<bf16x3,128,dgrad_s2>"},
+                                             {"igemm<bf16x3,256x64,fwd>", "igemm<bf16x3,256x64,dgrad>", "igemm<bf16x3,256x64,dgrad_s2>"},
+                                             {"igemm<bf16x3,256x128,fwd>", "igemm<bf16x3,256x128,dgrad>", "igemm<bf16x3,256x128,dgrad_s2>"}}};
   if constexpr (MODE == 3)
-    vdqn_prof_begin(sizeof(T) == 2 ? "stem_conv_pool<bf16>" : "stem_conv_pool<f32>", 2.0 * p.n_img * 112 * 112 * 64 * 147,
+    vdqn_prof_begin(sizeof(T) == 2 ? "stem_conv_pool<bf16>" : (X3 ? "stem_conv_pool<bf16x3>" : "stem_conv_pool<f32>"), 2.0 * p.n_img * 112 * 112 * 64 * 147,
                     esz * ((double)p.n_img * 115 * 115 * 16 + 64.0 * 256 + (double)p.n_img * 56 * 56 * 64) + (double)p.n_img * 56 * 56 * 64, stream);
   else
-    vdqn_prof_begin(kTag[sizeof(T) == 2 ? 0 : 1][BM == 256 ? (BN == 128 ? 3 : 2) : (BN == 128 ? 1 : 0)][MODE],
+    vdqn_prof_begin(kTag[sizeof(T) == 2 ? 0 : (X3 ? 2 : 1)][BM == 256 ? (BN == 128 ? 3 : 2) : (BN == 128 ? 1 : 0)][MODE],
                     2.0 * p.M * p.co * p.ktot,
                     esz * ((double)p.n_img * p.hi * p.wi * p.ci + (double)p.co * p.ktot + (double)p.M * p.co * (1 + (p.resid != nullptr) + (p.mask != nullptr))),
                     stream);
-  hipLaunchKernelGGL((igemm_kernel<T, BM, BN, MODE, WN, NS>), dim3(grid), dim3(BM * WN), smem, stream, p);
+  hipLaunchKernelGGL((igemm_kernel<T, BM, BN, MODE, WN, NS, X3>), dim3(grid), dim3(BM * WN), smem, stream, p);
   vdqn_prof_end(stream);
   VDQN_LAUNCH_CHECK();
   return VDQN_OK;
 }
 
-template <typename T, int BM, int BN>
+template <typename T, int BM, int BN, bool X3 = false>
 int launch_mode(const IgemmParams& p, int mode, hipStream_t st) {
   if constexpr (BM == 128) {
     // at most one tile per CU and a long K loop: nothing but a deeper ring hides the DMA round trip of every K-step
     static const bool deep_on = !getenv("VDQN_IGEMM_DEEP") || atoi(getenv("VDQN_IGEMM_DEEP")) != 0;
-    if (mode == 0 && deep_on && p.tiles_m * p.tiles_n <= 256 && p.nk >= 8) return launch_igemm<T, BM, BN, 0, 4>(p, st);
+    if (mode == 0 && deep_on && p.tiles_m * p.tiles_n <= 256 && p.nk >= 8) return launch_igemm<T, BM, BN, 0, 4, X3>(p, st);
   }
-  if (mode == 0) return launch_igemm<T, BM, BN, 0>(p, st);
-  if (mode == 1) return launch_igemm<T, BM, BN, 1>(p, st);
-  if constexpr (BM == 128) return launch_igemm<T, BM, BN, 2>(p, st);
+  if (mode == 0) return launch_igemm<T, BM, BN, 0, 2, X3>(p, st);
+  if (mode == 1) return launch_igemm<T, BM, BN, 1, 2, X3>(p, st);
+  if constexpr (BM == 128) return launch_igemm<T, BM, BN, 2, 2, X3>(p, st);
   return VDQN_ERR_INVALID;
 }
 
@@ -1554,8 +1566,9 @@ extern "C" void vdqn_debug_stamp_buffer(void* p) { g_stamp_buffer = p; }  // dia
 extern "C" int vdqn_conv2d(const vdqn_conv_args* a, void* stream) {
   VDQN_CHECK(a != nullptr, "vdqn_conv2d: null args");
   VDQN_CHECK(a != nullptr, "vdqn_conv2d: null args");
-  VDQN_CHECK(a->dtype == VDQN_F32 || a->dtype == VDQN_BF16, "vdqn_conv2d: bad dtype %d", a->dtype);
+  VDQN_CHECK(a->dtype == VDQN_F32 || a->dtype == VDQN_BF16 || a->dtype == VDQN_F32X3, "vdqn_conv2d: bad dtype %d", a->dtype);
   const int esz = a->dtype == VDQN_BF16 ? 2 : 4;
+  const bool x3 = a->dtype == VDQN_F32X3;  // f32 tensors, the f32 kernels' bf16x3 instances
   const int kc = 128 / esz;
   VDQN_CHECK(a->in && a->wt && (a->out || a->out_f32), "vdqn_conv2d: null tensor");
   VDQN_CHECK(a->ci > 0 && a->ci % kc == 0, "vdqn_conv2d: ci=%d must be a multiple of %d", a->ci, kc);
@@ -1653,6 +1666,10 @@ extern "C" int vdqn_conv2d(const vdqn_conv_args* a, void* stream) {
       if (bn == 128) return mode == 0 ? launch_igemm_win<bf16raw, 128, 0>(p, st) : launch_igemm_win<bf16raw, 128, 1>(p, st);
       return mode == 0 ? launch_igemm_win<bf16raw, 64, 0>(p, st) : launch_igemm_win<bf16raw, 64, 1>(p, st);
     }
+    if (x3) {
+      if (bn == 128) return mode == 0 ? launch_igemm_win<float, 128, 0, true>(p, st) : launch_igemm_win<float, 128, 1, true>(p, st);
+      return mode == 0 ? launch_igemm_win<float, 64, 0, true>(p, st) : launch_igemm_win<float, 64, 1, true>(p, st);
+    }
     if (bn == 128) return mode == 0 ? launch_igemm_win<float, 128, 0>(p, st) : launch_igemm_win<float, 128, 1>(p, st);
     return mode == 0 ? launch_igemm_win<float, 64, 0>(p, st) : launch_igemm_win<float, 64, 1>(p, st);
   }
@@ -1678,16 +1695,18 @@ extern "C" int vdqn_conv2d(const vdqn_conv_args* a, void* stream) {
   static const long long min256 = [] { const char* e = getenv("VDQN_BM256_MIN_ROWS"); return e ? atoll(e) : 256ll * 1024; }();
   if (bn == 64 && mode != 2 && p.M >= min256 && !has_sib) {
     p.tiles_m = (p.M + 255) / 256;
+    if (x3) return launch_mode<float, 256, 64, true>(p, mode, st);
     return a->dtype == VDQN_BF16 ? launch_mode<bf16raw, 256, 64>(p, mode, st) : launch_mode<float, 256, 64>(p, mode, st);
   }
   if (a->dtype == VDQN_BF16) return bn == 128 ? launch_mode<bf16raw, 128, 128>(p, mode, st) : launch_mode<bf16raw, 128, 64>(p, mode, st);
+  if (x3) return bn == 128 ? launch_mode<float, 128, 128, true>(p, mode, st) : launch_mode<float, 128, 64, true>(p, mode, st);
   return bn == 128 ? launch_mode<float, 128, 128>(p, mode, st) : launch_mode<float, 128, 64>(p, mode, st);
 }
 
 extern "C" int vdqn_stem_conv_pool_n(const void* t_in, const void* wt, const float* bias, void* pool, void* idx, int32_t n_img, int32_t n_idx_img,
                                      int32_t dtype, void* stream) {
   VDQN_CHECK(t_in && wt && bias && pool && n_img > 0 && n_idx_img >= 0 && n_idx_img <= n_img && (idx || n_idx_img == 0), "vdqn_stem_conv_pool: bad args");
-  VDQN_CHECK(dtype == VDQN_F32 || dtype == VDQN_BF16, "vdqn_stem_conv_pool: bad dtype %d", dtype);
+  VDQN_CHECK(dtype == VDQN_F32 || dtype == VDQN_BF16 || dtype == VDQN_F32X3, "vdqn_stem_conv_pool: bad dtype %d", dtype);
   VDQN_CHECK((((uintptr_t)t_in | (uintptr_t)wt | (uintptr_t)pool | (uintptr_t)idx) & 15) == 0, "vdqn_stem_conv_pool: tensors must be 16-byte aligned");
   const int esz = dtype == VDQN_BF16 ? 2 : 4;
   VDQN_CHECK((long long)n_img * 64 < (1ll << 31) / 256, "vdqn_stem_conv_pool: too many images");
@@ -1710,6 +1729,7 @@ extern "C" int vdqn_stem_conv_pool_n(const void* t_in, const void* wt, const flo
   // one-tile-per-workgroup MODE 3 path below, which f32 uses and VDQN_STEM_PERSISTENT=0 selects)
   static const bool persistent = [] { const char* e = getenv("VDQN_STEM_PERSISTENT"); return !(e && e[0] == '0'); }();
   if (dtype == VDQN_BF16 && persistent) return vdqn_stem_bf16(t_in, wt, bias, pool, idx, n_img, n_idx_img, st);
+  if (dtype == VDQN_F32X3) return launch_igemm<float, 256, 64, 3, 2, true>(p, st);
   return dtype == VDQN_BF16 ? launch_igemm<bf16raw, 256, 64, 3>(p, st) : launch_igemm<float, 256, 64, 3>(p, st);
 }
 

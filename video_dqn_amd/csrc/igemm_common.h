@@ -399,4 +399,24 @@ __device__ __forceinline__ void lean_epilogue_dgrad_128(const LeanEpiD& e, f32x4
     }                                                       \
   }
 
+// bf16x3 MFMA block of igemm_kernel / igemm_win_kernel (X3): fa / fb hold a K-step's f32 fragments as two K-halves of 4 values.
+// Slots 0..3 of the joined operand are K-half 0 (components x..w), slots 4..7 K-half 1 — the same (K-half, component) -> slot
+// map for both operands, so one 16x16x32 product sums exactly the 32 K values of the eight 16x16x4 f32 MFMAs it replaces, and its
+// C fragment layout is theirs (the epilogues do not change).  The small terms go first; each pass walks every accumulator, so no
+// MFMA waits on its predecessor's result.
+#define VDQN_MFMA_X3(SET)                                                                                                \
+  {                                                                                                                      \
+    bf16x8 ah_[4], al_[4], bh_[NF], bl_[NF];                                                                             \
+    _Pragma("unroll") for (int f_ = 0; f_ < 4; ++f_)                                                                     \
+        split_bf16x8(__builtin_bit_cast(f32x4, fa[SET][0][f_]), __builtin_bit_cast(f32x4, fa[SET][1][f_]), ah_[f_], al_[f_]); \
+    _Pragma("unroll") for (int j_ = 0; j_ < NF; ++j_)                                                                    \
+        split_bf16x8(__builtin_bit_cast(f32x4, fb[SET][0][j_]), __builtin_bit_cast(f32x4, fb[SET][1][j_]), bh_[j_], bl_[j_]); \
+    _Pragma("unroll") for (int f_ = 0; f_ < 4; ++f_) _Pragma("unroll") for (int j_ = 0; j_ < NF; ++j_)                  \
+        acc[f_][j_] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bl_[j_], ah_[f_], acc[f_][j_], 0, 0, 0);                   \
+    _Pragma("unroll") for (int f_ = 0; f_ < 4; ++f_) _Pragma("unroll") for (int j_ = 0; j_ < NF; ++j_)                  \
+        acc[f_][j_] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bh_[j_], al_[f_], acc[f_][j_], 0, 0, 0);                   \
+    _Pragma("unroll") for (int f_ = 0; f_ < 4; ++f_) _Pragma("unroll") for (int j_ = 0; j_ < NF; ++j_)                  \
+        acc[f_][j_] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bh_[j_], ah_[f_], acc[f_][j_], 0, 0, 0);                   \
+  }
+
 }  // namespace

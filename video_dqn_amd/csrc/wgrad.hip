@@ -59,8 +59,12 @@ template <typename T, int BT> constexpr int wg_ksub() {
   return sizeof(T) == 2 ? (BT == 64 ? 4 : 2) : (BT == 64 ? 2 : 1);
 }
 
-template <typename T, int BT>
+// X3 (T = float only): the bf16x3 compute mode (VDQN_F32X3) — the f32 staging unchanged; a lane's values of the eight 4-pixel
+// sub-steps of a 32-pixel MFMA step are joined into one 8-slot operand, split into bf16 hi / lo (split_bf16x8) and multiplied as
+// hi*hi + hi*lo + lo*hi on v_mfma_f32_16x16x32_bf16.
+template <typename T, int BT, bool X3 = false>
 __global__ __launch_bounds__(256, 2) void wgrad_kernel(const WgradParams p) {
+  static_assert(!X3 || sizeof(T) == 4, "bf16x3 splits f32 operands");
   constexpr int E16 = 16 / (int)sizeof(T);
   constexpr int RB = BT * (int)sizeof(T);  // bytes per LDS row (one pixel)
   constexpr int CPR = RB / 16;             // 16-byte chunks per row
@@ -227,6 +231,43 @@ __global__ __launch_bounds__(256, 2) void wgrad_kernel(const WgradParams p) {
         for (int j = 0; j < NFR; ++j)
           acc[f][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, af[f]), __builtin_bit_cast(bf16x8, bfr[j]),
                                                               acc[f][j], 0, 0, 0);
+    } else if constexpr (X3) {
+      // slot st of a lane's operand = pixel row 4 st + grp, for both operands: the 16x16x32 product sums the 32 pixels of the eight
+      // 16x16x4 f32 MFMAs it replaces, C layout unchanged.  Small terms first, each pass over every accumulator.
+      f32x4 av[NFR][2], bv[NFR][2];
+#pragma unroll
+      for (int st = 0; st < 8; ++st) {
+        const int row = 4 * st + grp;
+        const int sz = wg_swz<T, BT>(row);
+#pragma unroll
+        for (int f = 0; f < NFR; ++f) {
+          const int col = wr * (BT / 2) + f * 16 + i16;
+          av[f][st >> 2][st & 3] = *reinterpret_cast<const float*>(a + row * RB + (((col >> 2) ^ sz) << 4) + ((col & 3) << 2));
+        }
+#pragma unroll
+        for (int j = 0; j < NFR; ++j) {
+          const int col = wc * (BT / 2) + j * 16 + i16;
+          bv[j][st >> 2][st & 3] = *reinterpret_cast<const float*>(b + row * RB + (((col >> 2) ^ sz) << 4) + ((col & 3) << 2));
+        }
+      }
+      bf16x8 ah[NFR], al[NFR], bh[NFR], bl[NFR];
+#pragma unroll
+      for (int f = 0; f < NFR; ++f) {
+        split_bf16x8(av[f][0], av[f][1], ah[f], al[f]);
+        split_bf16x8(bv[f][0], bv[f][1], bh[f], bl[f]);
+      }
+#pragma unroll
+      for (int f = 0; f < NFR; ++f)
+#pragma unroll
+        for (int j = 0; j < NFR; ++j) acc[f][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al[f], bh[j], acc[f][j], 0, 0, 0);
+#pragma unroll
+      for (int f = 0; f < NFR; ++f)
+#pragma unroll
+        for (int j = 0; j < NFR; ++j) acc[f][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[f], bl[j], acc[f][j], 0, 0, 0);
+#pragma unroll
+      for (int f = 0; f < NFR; ++f)
+#pragma unroll
+        for (int j = 0; j < NFR; ++j) acc[f][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[f], bh[j], acc[f][j], 0, 0, 0);
     } else {
 #pragma unroll
       for (int st = 0; st < 8; ++st) {
@@ -784,15 +825,17 @@ __global__ __launch_bounds__(256) void colsum_kernel(const T* __restrict__ gy, f
   }
 }
 
-template <typename T, int BT>
+template <typename T, int BT, bool X3 = false>
 int launch_wgrad(const WgradParams& p, int tiles, int splitk, hipStream_t stream) {
   const size_t smem = 4 * 32 * wg_ksub<T, BT>() * BT * sizeof(T);
-  vdqn_ensure_dyn_smem(reinterpret_cast<const void*>(&wgrad_kernel<T, BT>), (size_t)smem);
+  vdqn_ensure_dyn_smem(reinterpret_cast<const void*>(&wgrad_kernel<T, BT, X3>), (size_t)smem);
   const double esz = sizeof(T);
-  vdqn_prof_begin(sizeof(T) == 2 ? (BT == 128 ? "wgrad<bf16,128>" : "wgrad<bf16,64>") : (BT == 128 ? "wgrad<f32,128>" : "wgrad<f32,64>"),
+  vdqn_prof_begin(sizeof(T) == 2 ? (BT == 128 ? "wgrad<bf16,128>" : "wgrad<bf16,64>")
+                  : X3           ? (BT == 128 ? "wgrad<bf16x3,128>" : "wgrad<bf16x3,64>")
+                                 : (BT == 128 ? "wgrad<f32,128>" : "wgrad<f32,64>"),
                   2.0 * p.M * p.co * p.taps * p.ci,
                   esz * ((double)p.M * p.ldg + (double)p.n_img * p.hi * p.wi * p.ci) + 4.0 * p.co * p.taps * p.ci, stream);
-  hipLaunchKernelGGL((wgrad_kernel<T, BT>), dim3(tiles * splitk), dim3(256), smem, stream, p);
+  hipLaunchKernelGGL((wgrad_kernel<T, BT, X3>), dim3(tiles * splitk), dim3(256), smem, stream, p);
   vdqn_prof_end(stream);
   VDQN_LAUNCH_CHECK();
   return VDQN_OK;
@@ -1216,7 +1259,7 @@ int g_wgrad_win_blocks_override = -1;  // tools/ab_inproc.py: vdqn_debug_set_wgr
 
 int plan_wgrad(const vdqn_wgrad_args* a, WgradPlan* pl) {
   VDQN_CHECK(a != nullptr, "vdqn_conv2d_wgrad: null args");
-  VDQN_CHECK(a->dtype == VDQN_F32 || a->dtype == VDQN_BF16, "vdqn_conv2d_wgrad: bad dtype %d", a->dtype);
+  VDQN_CHECK(a->dtype == VDQN_F32 || a->dtype == VDQN_BF16 || a->dtype == VDQN_F32X3, "vdqn_conv2d_wgrad: bad dtype %d", a->dtype);
   VDQN_CHECK(a->ci % 64 == 0 && a->ldg % 64 == 0, "vdqn_conv2d_wgrad: ci=%d and ldg=%d must be multiples of 64", a->ci, a->ldg);
   VDQN_CHECK(a->stride == 1 || a->stride == 2, "vdqn_conv2d_wgrad: stride %d unsupported", a->stride);
   const int64_t M64 = (int64_t)a->n_img * a->ho * a->wo;
@@ -1336,6 +1379,7 @@ extern "C" int vdqn_conv2d_wgrad(const vdqn_wgrad_args* a, void* stream) {
   if (pl.variant == 0) rc = launch_stem_wgrad(p, st);
   else if (pl.variant == 1) rc = launch_wgrad_win(p, pl.tiles, pl.splitk, st);
   else if (a->dtype == VDQN_BF16) rc = pl.bt == 128 ? launch_wgrad<bf16raw, 128>(p, pl.tiles, pl.splitk, st) : launch_wgrad<bf16raw, 64>(p, pl.tiles, pl.splitk, st);
+  else if (a->dtype == VDQN_F32X3) rc = pl.bt == 128 ? launch_wgrad<float, 128, true>(p, pl.tiles, pl.splitk, st) : launch_wgrad<float, 64, true>(p, pl.tiles, pl.splitk, st);
   else rc = pl.bt == 128 ? launch_wgrad<float, 128>(p, pl.tiles, pl.splitk, st) : launch_wgrad<float, 64>(p, pl.tiles, pl.splitk, st);
   if (rc != VDQN_OK) return rc;
   if (p.ws && pl.variant != 0) {

@@ -21,8 +21,11 @@ from . import _lib
 
 LOSS_KINDS = {"l2": 0, "huber": 1}  # vdqn_td_args.loss_kind
 
+# "bf16x3": f32 storage (parameters, activations, workspaces and checkpoints exactly as "f32"), the convolutions / linear layers /
+# weight gradients computed as split bf16 x 3 (include/vdqn.h VDQN_F32X3): f32-grade results at bf16 MFMA rates
 DTYPES = {"f32": _lib.VDQN_F32, "fp32": _lib.VDQN_F32, "float32": _lib.VDQN_F32,
-          "bf16": _lib.VDQN_BF16, "bfloat16": _lib.VDQN_BF16}
+          "bf16": _lib.VDQN_BF16, "bfloat16": _lib.VDQN_BF16,
+          "bf16x3": _lib.VDQN_F32X3}
 
 
 # VDQN_EARLY_ADAM=0: `TDStepper.step` runs the whole optimiser update behind the backward pass (one launch)
@@ -72,7 +75,10 @@ class NetEngine:
         self.device = torch.device("cpu") if self.storage_only else require_gpu(device)
         self.extra_capacity = bool(extra_capacity)
         self.action_dim, self.num_classes, self.num_frames = action_dim, num_classes, num_frames
+        # dtype_name is the STORAGE dtype ("bf16" | "f32": what torch tensors of activations / gradients use); compute_dtype adds
+        # the GEMM mode ("bf16" | "f32" | "bf16x3")
         self.dtype_name = "bf16" if DTYPES[dtype] == _lib.VDQN_BF16 else "f32"
+        self.compute_dtype = {_lib.VDQN_BF16: "bf16", _lib.VDQN_F32: "f32", _lib.VDQN_F32X3: "bf16x3"}[DTYPES[dtype]]
         # run-to-run bit-identical updates (the reference pins cudnn.deterministic, train_q_network.py:88-89): config key
         # DETERMINISTIC / this argument, or VDQN_DETERMINISTIC=1 in the environment
         if deterministic is None:

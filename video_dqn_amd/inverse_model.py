@@ -151,13 +151,14 @@ class InverseActionModel(nn.Module):
             feat = acts[off:off + 2 * B * 49 * 512 * esz].view(self.tdtype).view(2 * B, 7, 7, 512)
             x = torch.cat([feat[:B], feat[B:]], dim=3).contiguous()  # torch.cat([resnet_k, resnet_k_plus_one], dim=1) in NHWC
             p = self._packed_head
-            x = ops.conv2d(x, p["conv1"][0], ho=7, wo=7, co=256, r=1, s=1, stride=1, pad=0, bias=p["conv1"][1], relu=True)
-            x = ops.conv2d(x, p["conv2"][0], ho=5, wo=5, co=256, r=3, s=3, stride=1, pad=0, bias=p["conv2"][1], relu=True)
-            x = ops.conv2d(x, p["conv3"][0], ho=3, wo=3, co=64, r=3, s=3, stride=1, pad=0, bias=p["conv3"][1], relu=True)
+            prec = "bf16x3" if eng.compute_dtype == "bf16x3" else None  # the engine's GEMM mode for the head too
+            x = ops.conv2d(x, p["conv1"][0], ho=7, wo=7, co=256, r=1, s=1, stride=1, pad=0, bias=p["conv1"][1], relu=True, precision=prec)
+            x = ops.conv2d(x, p["conv2"][0], ho=5, wo=5, co=256, r=3, s=3, stride=1, pad=0, bias=p["conv2"][1], relu=True, precision=prec)
+            x = ops.conv2d(x, p["conv3"][0], ho=3, wo=3, co=64, r=3, s=3, stride=1, pad=0, bias=p["conv3"][1], relu=True, precision=prec)
             x = x.view(B, 1, 1, 576)
-            x = ops.conv2d(x, p["fc1"][0], ho=1, wo=1, co=128, r=1, s=1, stride=1, pad=0, bias=p["fc1"][1], relu=True)
-            x, x32 = ops.conv2d(x, p["fc2"][0], ho=1, wo=1, co=64, r=1, s=1, stride=1, pad=0, bias=p["fc2"][1], want_f32=True)
-            _, y32 = ops.conv2d(x, p["fc_accuracy"][0], ho=1, wo=1, co=64, r=1, s=1, stride=1, pad=0, bias=p["fc_accuracy"][1], want_f32=True)
+            x = ops.conv2d(x, p["fc1"][0], ho=1, wo=1, co=128, r=1, s=1, stride=1, pad=0, bias=p["fc1"][1], relu=True, precision=prec)
+            x, x32 = ops.conv2d(x, p["fc2"][0], ho=1, wo=1, co=64, r=1, s=1, stride=1, pad=0, bias=p["fc2"][1], want_f32=True, precision=prec)
+            _, y32 = ops.conv2d(x, p["fc_accuracy"][0], ho=1, wo=1, co=64, r=1, s=1, stride=1, pad=0, bias=p["fc_accuracy"][1], want_f32=True, precision=prec)
             x32 = x32.view(B, 64)
             enc = torch.empty_like(x32)
             _lib.check(eng.lib.vdqn_softmax_rows(_ptr(x32), _ptr(enc), B, 64, 3, _stream()), "vdqn_softmax_rows")

@@ -74,6 +74,7 @@ class InverseTrainer:
         mdl, eng = self.model, self.model.engine
         dt = mdl.tdtype
         code = ops.dtype_code(torch.empty(0, dtype=dt))
+        prec = "bf16x3" if eng.compute_dtype == "bf16x3" else None  # GEMM mode of the head's convolutions / linear layers
         B = k.shape[0]
         src_kind = 0 if k.dtype == torch.uint8 else 1
         frames = (torch.cat([k, k_plus_one], 0) if src_kind == 0 else torch.cat([k.float(), k_plus_one.float()], 0)).to(eng.device).contiguous()
@@ -91,12 +92,12 @@ class InverseTrainer:
             x0 = torch.cat([feat[:B], feat[B:]], dim=3).contiguous()
             # ---- forward (train mode) ----
             w1, w2, w3 = _conv_w(h["conv1.weight"], dt), _conv_w(h["conv2.weight"], dt), _conv_w(h["conv3.weight"], dt)
-            a1 = ops.conv2d(x0, w1, ho=7, wo=7, co=256, r=1, s=1, stride=1, pad=0, bias=_pad_bias(h["conv1.bias"]), relu=True)
-            a2 = ops.conv2d(a1, w2, ho=5, wo=5, co=256, r=3, s=3, stride=1, pad=0, bias=_pad_bias(h["conv2.bias"]), relu=True)
-            a3 = ops.conv2d(a2, w3, ho=3, wo=3, co=64, r=3, s=3, stride=1, pad=0, bias=_pad_bias(h["conv3.bias"]), relu=True)
+            a1 = ops.conv2d(x0, w1, ho=7, wo=7, co=256, r=1, s=1, stride=1, pad=0, bias=_pad_bias(h["conv1.bias"]), relu=True, precision=prec)
+            a2 = ops.conv2d(a1, w2, ho=5, wo=5, co=256, r=3, s=3, stride=1, pad=0, bias=_pad_bias(h["conv2.bias"]), relu=True, precision=prec)
+            a3 = ops.conv2d(a2, w3, ho=3, wo=3, co=64, r=3, s=3, stride=1, pad=0, bias=_pad_bias(h["conv3.bias"]), relu=True, precision=prec)
             wf1 = h["fc1.weight"].view(128, 64, 9).permute(0, 2, 1).reshape(128, 576, 1, 1)  # NCHW flatten -> NHWC flatten
             a3f = a3.view(B, 1, 1, 576)
-            h1 = ops.conv2d(a3f, _conv_w(wf1, dt), ho=1, wo=1, co=128, r=1, s=1, stride=1, pad=0, bias=_pad_bias(h["fc1.bias"]), relu=True)
+            h1 = ops.conv2d(a3f, _conv_w(wf1, dt), ho=1, wo=1, co=128, r=1, s=1, stride=1, pad=0, bias=_pad_bias(h["fc1.bias"]), relu=True, precision=prec)
             if dropout_mask is None:
                 dropout_mask = (torch.rand((B, 128), device=eng.device) >= 0.5)
             mask = dropout_mask.to(eng.device).to(dt).view(B, 1, 1, 128).contiguous()
@@ -104,10 +105,10 @@ class InverseTrainer:
             _lib.check(eng.lib.vdqn_mask_scale(_ptr(h1), _ptr(mask), _ptr(d1), h1.numel(), 2.0, code, _stream()), "vdqn_mask_scale")
             w_fc2 = torch.zeros((64, 128, 1, 1), device=eng.device)
             w_fc2[:3] = h["fc2.weight"].view(3, 128, 1, 1)
-            h2 = ops.conv2d(d1, _conv_w(w_fc2, dt), ho=1, wo=1, co=64, r=1, s=1, stride=1, pad=0, bias=_pad_bias(h["fc2.bias"]), relu=True)
+            h2 = ops.conv2d(d1, _conv_w(w_fc2, dt), ho=1, wo=1, co=64, r=1, s=1, stride=1, pad=0, bias=_pad_bias(h["fc2.bias"]), relu=True, precision=prec)
             w_acc = torch.zeros((64, 64, 1, 1), device=eng.device)
             w_acc[:3, :3] = h["fc_accuracy.weight"].view(3, 3, 1, 1)
-            _, y32 = ops.conv2d(h2, _conv_w(w_acc, dt), ho=1, wo=1, co=64, r=1, s=1, stride=1, pad=0, bias=_pad_bias(h["fc_accuracy.bias"]), want_f32=True)
+            _, y32 = ops.conv2d(h2, _conv_w(w_acc, dt), ho=1, wo=1, co=64, r=1, s=1, stride=1, pad=0, bias=_pad_bias(h["fc_accuracy.bias"]), want_f32=True, precision=prec)
             y32 = y32.view(B, 64)
             # ---- loss + backward of the head ----
             self.loss.zero_()
@@ -116,11 +117,11 @@ class InverseTrainer:
             _lib.check(eng.lib.vdqn_softmax_ce(_ptr(y32), _ptr(labels), _ptr(self.loss), _ptr(dy), B, 64, 3, 1.0 / B, code, _stream()), "vdqn_softmax_ce")
 
             def wgrad(gy, x, co, r):
-                dw, db = ops.conv2d_wgrad(gy, x, co=co, r=r, s=r, stride=1, pad=0)
+                dw, db = ops.conv2d_wgrad(gy, x, co=co, r=r, s=r, stride=1, pad=0, precision=prec)
                 return dw, db
 
             def dgrad(gy, w_oihw, hi, ci, r, mask_t=None):
-                return ops.conv2d(gy, _conv_wd(w_oihw, dt), ho=hi, wo=hi, co=ci, r=r, s=r, stride=1, pad=0, mode=1, mask=mask_t)
+                return ops.conv2d(gy, _conv_wd(w_oihw, dt), ho=hi, wo=hi, co=ci, r=r, s=r, stride=1, pad=0, mode=1, mask=mask_t, precision=prec)
             g = self.gviews
             dw, db = wgrad(dy, h2, 64, 1)
             g["fc_accuracy.weight"].copy_(dw[:3, 0, 0, :3]); g["fc_accuracy.bias"].copy_(db[:3])

@@ -22,13 +22,27 @@ def dtype_code(t: torch.Tensor) -> int:
     raise TypeError(f"unsupported activation dtype {t.dtype}")
 
 
+def gemm_dtype_code(t: torch.Tensor, precision: Optional[str]) -> int:
+    """dtype code of a GEMM call (conv2d, conv2d_wgrad, stem_conv_pool) on tensors like `t`.  precision=None: the tensors' own
+    (f32 -> exact f32 MFMAs, bf16 -> bf16 MFMAs); "bf16x3": f32 tensors, the GEMM computed as split bf16 x 3 (VDQN_F32X3)."""
+    code = dtype_code(t)
+    if precision is None:
+        return code
+    if precision != "bf16x3":
+        raise ValueError(f"unknown precision {precision!r} (None or 'bf16x3')")
+    if code != _lib.VDQN_F32:
+        raise TypeError(f"precision='bf16x3' splits f32 operands; got {t.dtype}")
+    return _lib.VDQN_F32X3
+
+
 def conv2d(x: torch.Tensor, wt: torch.Tensor, *, ho: int, wo: int, co: int, r: int, s: int, stride: int, pad: int,
            bias: Optional[torch.Tensor] = None, resid: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None,
            relu: bool = False, mode: int = 0, pix_stride: Optional[int] = None, ci: Optional[int] = None,
            want_f32: bool = False, ldo: Optional[int] = None, want_colsum: bool = False,
            wt2: Optional[torch.Tensor] = None, bias2: Optional[torch.Tensor] = None, co2: int = 0, relu2: bool = False,
-           in2: Optional[torch.Tensor] = None):
+           in2: Optional[torch.Tensor] = None, precision: Optional[str] = None):
     """x: [n, hi, wi, c] NHWC; wt: [co_pad, r, s, ci].  Returns out [n, ho, wo, ldo] (and the f32 copy).
+    precision="bf16x3" (f32 tensors): the GEMM as split bf16 x 3 instead of exact f32 MFMAs (gemm_dtype_code).
     Fused sibling 1x1 / stride 2 (include/vdqn.h): forward — wt2 [co2, 1, 1, ci] (+ bias2, relu2) gives a second output
     (returned after `out`); data gradient — in2 [n, hi, wi, ci2] and wt2 [co, 1, 1, ci2] add the sibling's gradient."""
     lib = _lib.load()
@@ -45,7 +59,7 @@ def conv2d(x: torch.Tensor, wt: torch.Tensor, *, ho: int, wo: int, co: int, r: i
     a.n_img, a.hi, a.wi, a.ci, a.pix_stride = n, hi, wi, ci, pix_stride
     a.ho, a.wo, a.co, a.ldo = ho, wo, co, ldo
     a.r, a.s, a.stride, a.pad = r, s, stride, pad
-    a.mode, a.relu, a.dtype = mode, int(relu), dtype_code(x)
+    a.mode, a.relu, a.dtype = mode, int(relu), gemm_dtype_code(x, precision)
     # every field that decides which kernel takes the call is set BEFORE the colsum-row query (the skinny kernels refuse a call with
     # column sums or a sibling: a query on half-filled args would answer for another kernel than the one that runs)
     out2 = None
@@ -74,8 +88,9 @@ def conv2d(x: torch.Tensor, wt: torch.Tensor, *, ho: int, wo: int, co: int, r: i
 
 def conv2d_wgrad(gy: torch.Tensor, x: torch.Tensor, *, co: int, r: int, s: int, stride: int, pad: int,
                  ci: Optional[int] = None, pix_stride: Optional[int] = None, splitk: int = 0, want_dbias: bool = True,
-                 deterministic: bool = False, poison_workspace: bool = False):
+                 deterministic: bool = False, poison_workspace: bool = False, precision: Optional[str] = None):
     """gy: [n, ho, wo, ldg]; x: [n, hi, wi, c].  Returns dw f32 [co_pad, r, s, ci] (and dbias [co_pad]).
+    precision="bf16x3" (f32 tensors): split bf16 x 3 MFMAs (gemm_dtype_code).
     deterministic: the two-stage ordered reduction (a workspace of vdqn_conv2d_wgrad_workspace_bytes) instead of atomics;
     poison_workspace fills that workspace with NaN first (tests: nothing the call does not write may reach dw)."""
     lib = _lib.load()
@@ -91,7 +106,7 @@ def conv2d_wgrad(gy: torch.Tensor, x: torch.Tensor, *, co: int, r: int, s: int, 
     a.n_img, a.hi, a.wi, a.ci, a.pix_stride = n, hi, wi, ci, pix_stride
     a.ho, a.wo, a.co, a.ldg = ho, wo, co, ldg
     a.r, a.s, a.stride, a.pad = r, s, stride, pad
-    a.splitk, a.dtype = splitk, dtype_code(x)
+    a.splitk, a.dtype = splitk, gemm_dtype_code(x, precision)
     ws = None
     if deterministic:
         nbytes = lib.vdqn_conv2d_wgrad_workspace_bytes(C.byref(a))
@@ -250,20 +265,23 @@ def avgpool_bwd(g: torch.Tensor, x: torch.Tensor) -> torch.Tensor:
     return gx
 
 
-def stem_conv_pool(t_in: torch.Tensor, wt: torch.Tensor, bias: torch.Tensor, want_idx: bool = True, n_idx: int = None):
+def stem_conv_pool(t_in: torch.Tensor, wt: torch.Tensor, bias: torch.Tensor, want_idx: bool = True, n_idx: int = None,
+                   precision: Optional[str] = None):
     """t_in [n,115,115,16] (pack_input), wt [64,4,1,64], bias f32 [64] -> (pool [n,56,56,64], idx uint8).
+    precision="bf16x3" (f32 tensors): split bf16 x 3 MFMAs (gemm_dtype_code).
 
     want_idx=False: frames that never see a backward pass — idx is None and the arg-max bytes are not computed.
     n_idx: arg-max bytes for the first n_idx images only (vdqn_stem_conv_pool_n); the other rows of idx stay as allocated."""
     lib = _lib.load()
     n = t_in.shape[0]
+    dt = gemm_dtype_code(t_in, precision)
     pool = torch.empty((n, 56, 56, 64), dtype=t_in.dtype, device=t_in.device)
     if n_idx is not None:
         idx = torch.zeros((n, 56, 56, 64), dtype=torch.uint8, device=t_in.device)
-        _lib.check(lib.vdqn_stem_conv_pool_n(_ptr(t_in), _ptr(wt), _ptr(bias), _ptr(pool), _ptr(idx), n, int(n_idx), dtype_code(t_in), _stream()),
+        _lib.check(lib.vdqn_stem_conv_pool_n(_ptr(t_in), _ptr(wt), _ptr(bias), _ptr(pool), _ptr(idx), n, int(n_idx), dt, _stream()),
                    "vdqn_stem_conv_pool_n")
         return pool, idx
     idx = torch.empty((n, 56, 56, 64), dtype=torch.uint8, device=t_in.device) if want_idx else None
-    _lib.check(lib.vdqn_stem_conv_pool(_ptr(t_in), _ptr(wt), _ptr(bias), _ptr(pool), _ptr(idx) if want_idx else None, n, dtype_code(t_in), _stream()),
+    _lib.check(lib.vdqn_stem_conv_pool(_ptr(t_in), _ptr(wt), _ptr(bias), _ptr(pool), _ptr(idx) if want_idx else None, n, dt, _stream()),
                "vdqn_stem_conv_pool")
     return pool, idx
