@@ -189,6 +189,11 @@ typedef struct vdqn_td_args {
                              training loop reads back as Q(s)), written by the same launch */
 } vdqn_td_args;
 int vdqn_td_loss(const vdqn_td_args* a, void* stream);
+/* The same loss with per-sample importance weights (prioritized replay): sample b's loss terms and its dq row are scaled by
+ * weight[b] (f32 [batch]; inv_count is unchanged), and err_out[b] (f32 [batch], optional) receives the sample's mean absolute
+ * TD error sum_c |d_bc| * valid_bc / n_cat, from the raw d under either loss kind.  No atomics for err_out; `deterministic` keeps
+ * its one-block loss sum.  With weight == 1 the loss and dq are bit-identical to vdqn_td_loss. */
+int vdqn_td_loss_weighted(const vdqn_td_args* a, const float* weight, float* err_out, void* stream);
 
 /* Ground-truth branch (train_q_network.py:170-178): l = 0.5 (Qb*mask - gt)^2, mask = !isnan(gt) when
  * value_learning, else l = 0.5 (Qb - gt)^2.  gt is f32 [batch][n_cat] (NaN allowed). */
@@ -423,6 +428,30 @@ int vdqn_net_backward_begin(vdqn_net* net, const vdqn_step_args* a, const float*
 /* The HIP stream (hipStream_t) on which a stage's gradients become complete; NULL when the overlap is off (then it is the
  * stream passed to vdqn_net_backward_stage). */
 void* vdqn_net_grad_stream(vdqn_net* net);
+/* While set (weight != NULL), vdqn_net_td_forward launches vdqn_td_loss_weighted with these [batch] weights and per-sample
+ * error output instead of vdqn_td_loss (TD branch only: the ground-truth branch then fails).  NULL, NULL restores the reference
+ * loss.  The pointers are read at every vdqn_net_td_forward call until they are changed. */
+int vdqn_net_set_sample_weights(vdqn_net* net, const float* weight, float* err_out);
+
+/* ------------------------------------------------------------------------------------------------
+ * Prioritized experience replay (Schaul et al., ICLR 2016), sampled and updated on the device: no host round trip.
+ * The caller holds an f32 priority table prio[n] (>= 0, not all zero; (e + 1e-6)^alpha after an update, 1.0 to start) and a
+ * workspace of vdqn_per_workspace_bytes(n).  The arithmetic is fixed and written out in video_dqn_amd/csrc/replay.hip:
+ * f64 sums over 32-entry segments and 2048-entry chunks, left to right; draw j of the global batch G takes
+ * u_j = ((j + r_j) * S) / G, S = sum(prio), r_j = top 53 bits of splitmix64(splitmix64(seed) ^ (step * G + j)) / 2^53, and the
+ * smallest index whose inclusive prefix exceeds u_j (an entry with p = 0 is never drawn); its weight is
+ * (n * p_i / S)^-beta over the largest such value of the batch.
+ * ------------------------------------------------------------------------------------------------ */
+/* Bytes of the sampling workspace for a table of n entries; -1 when n <= 0 or n > 8388608.  Host only. */
+int64_t vdqn_per_workspace_bytes(int64_t n);
+/* Draw a global batch of `global_batch` (<= 4096) indices: idx_out int64 [G], weight_out f32 [G] (beta in [0, 1]).  Two launches:
+ * the segment / chunk sums into the workspace, then one block that scans the chunk sums and resolves every draw.
+ * prio and workspace 16-byte aligned. */
+int vdqn_per_sample(const float* prio, int64_t n, int32_t global_batch, uint64_t seed, uint64_t step, double beta, void* workspace,
+                    int64_t* idx_out, float* weight_out, void* stream);
+/* prio[idx[j]] = (err[j] + 1e-6)^alpha for j < global_batch (f64 pow, stored as f32); an index that appears more than once takes
+ * the value of its largest j.  Indices outside [0, n) are skipped. */
+int vdqn_per_update(float* prio, int64_t n, const int64_t* idx, const float* err, int32_t global_batch, double alpha, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Data-parallel exchange: one process per GPU, the flat f32 gradient SUM-all-reduced over RCCL (xGMI)

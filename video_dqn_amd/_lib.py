@@ -133,6 +133,11 @@ _SIGS = {
     "vdqn_comm_size": (C.c_int, [c_vp]),
     "vdqn_comm_destroy": (C.c_int, [c_vp]),
     "vdqn_host_gather": (C.c_int, [c_vp, c_vp, c_i64, c_i64, c_i32]),
+    "vdqn_td_loss_weighted": (C.c_int, [C.POINTER(TdArgs), c_vp, c_vp, c_vp]),
+    "vdqn_net_set_sample_weights": (C.c_int, [c_vp, c_vp, c_vp]),
+    "vdqn_per_workspace_bytes": (c_i64, [c_i64]),
+    "vdqn_per_sample": (C.c_int, [c_vp, c_i64, c_i32, C.c_uint64, C.c_uint64, C.c_double, c_vp, c_vp, c_vp, c_vp]),
+    "vdqn_per_update": (C.c_int, [c_vp, c_i64, c_vp, c_vp, c_i32, C.c_double, c_vp]),
 }
 COMM_UID_BYTES = 128
 EXPORTS = tuple(_SIGS)

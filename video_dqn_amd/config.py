@@ -19,7 +19,10 @@ updates — the reference's cudnn.deterministic = True, train_q_network.py:88-89
 squared TD error, train_q_network.py:167; 'huber' = smooth-L1, the option archs/HabitatDQNMultiAction.py:25 leaves open),
 PRETRAINED_WEIGHTS (path of a torchvision resnet18 state_dict: the reference builds models.resnet18(pretrained=True),
 archs/HabitatDQNMultiAction.py:11, which needs a download this build cannot make), BOOTSTRAP_CHECKPOINT (the file the
-BOOTSTRAP branch loads; default = the path hard-coded at train_q_network.py:202).
+BOOTSTRAP branch loads; default = the path hard-coded at train_q_network.py:202), PRIORITIZED_REPLAY (False: draw every
+minibatch by priority — prioritized experience replay, sampled and updated on the GPU — instead of in shuffled epochs; the TD
+branch on an HBM-resident decoded-frame shard dataset only), PER_ALPHA (0.6: priority exponent, p = (|TD error| + 1e-6)^alpha),
+PER_BETA (0.4: importance-sampling exponent at step 0, annealed linearly to 1.0 at NUM_STEPS).
 """
 from __future__ import annotations
 
@@ -142,6 +145,9 @@ def get_cfg_defaults() -> CfgNode:
     c.LOSS_KIND = "l2"
     c.PRETRAINED_WEIGHTS = ""
     c.BOOTSTRAP_CHECKPOINT = "logs/trained_gt_0.99/models/epoch99.torch"
+    c.PRIORITIZED_REPLAY = False  # sample minibatches by priority (PER, on the device) instead of shuffled epochs
+    c.PER_ALPHA = 0.6             # priority exponent: p = (|TD error| + 1e-6) ^ PER_ALPHA
+    c.PER_BETA = 0.4              # importance-sampling exponent at step 0, annealed linearly to 1.0 at NUM_STEPS
     return c
 
 

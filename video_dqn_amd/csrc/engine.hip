@@ -130,6 +130,8 @@ struct vdqn_net {
   int wgrad_rr = 0;                                  // VDQN_WGRAD_STREAMS=2: which side stream took the last weight gradient
   int overlap = 1;
   int bwd_samples = 0;  // batch of the update in flight (set by vdqn_net_td_forward; sizes the bwd workspace layout)
+  const float* sample_w = nullptr;  // vdqn_net_set_sample_weights: [B] importance weights of the TD loss (NULL: the reference loss)
+  float* sample_err = nullptr;      // ... and where that launch writes the [B] per-sample TD errors (may be NULL)
   hipStream_t side = nullptr;
   hipStream_t side2 = nullptr;  // the second half of the online forward pass
   std::vector<hipEvent_t> events;
@@ -1165,6 +1167,14 @@ extern "C" int vdqn_net_set_bn_sync(vdqn_net* net, vdqn_allreduce_fn fn, void* u
   return VDQN_OK;
 }
 
+extern "C" int vdqn_net_set_sample_weights(vdqn_net* net, const float* weight, float* err_out) {
+  VDQN_CHECK(net, "vdqn_net_set_sample_weights: null net");
+  VDQN_CHECK(weight || !err_out, "vdqn_net_set_sample_weights: err_out without weights");
+  net->sample_w = weight;
+  net->sample_err = weight ? err_out : nullptr;
+  return VDQN_OK;
+}
+
 extern "C" void vdqn_net_destroy(vdqn_net* net) {
   if (!net) return;
   if (net->side) {
@@ -1398,8 +1408,10 @@ extern "C" int vdqn_net_td_forward(vdqn_net* net, const vdqn_step_args* a, void*
     t.loss_kind = a->loss_kind;
     t.deterministic = net->cfg.deterministic;
     t.q_copy = a->q_before;  // (the compact copy of Q(s) rides in the loss launch: no 2-D copy between the loss and the first data gradient)
-    RC(vdqn_td_loss(&t, st));
+    if (net->sample_w) RC(vdqn_td_loss_weighted(&t, net->sample_w, net->sample_err, st));
+    else RC(vdqn_td_loss(&t, st));
   } else {
+    VDQN_CHECK(!net->sample_w, "vdqn_net_td_forward: sample weights are set, but the ground-truth branch has no weighted loss");
     RC(vdqn_gt_loss(qf_online, a->act, a->gt, a->loss, bw + W.dq, nullptr, B, net->cfg.num_classes, net->cfg.action_dim, 64, a->inv_count,
                     a->value_learning, dt, st));
   }

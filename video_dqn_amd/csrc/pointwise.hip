@@ -332,6 +332,87 @@ __global__ __launch_bounds__(256) void td_loss_kernel(const vdqn_td_args a) {
   }
 }
 
+// d = Q(s)[b, col] - y for the taken action's column `col` of category c: the Double-DQN target of td_loss_kernel (first
+// arg-max of the online Q(s'), the target network's value there, terminal mask, LINEAR / gamma, rect clip), stated once for the
+// weighted kernel, whose loss terms and per-sample error both take d from here.  (td_loss_kernel keeps its own inline copy: moving
+// it into this helper changes that kernel's register allocation.  tests/test_gpu_replay.py pins the two against each other bit
+// for bit over every target option.)
+__device__ __forceinline__ float td_error_of(const vdqn_td_args& a, int b, int c, int col) {
+  const float qb = a.q_before[(size_t)b * a.ldq + col];
+  const float* qo = a.q_after_online + (size_t)b * a.ldq + c * a.n_act;
+  int best = 0;
+  float bv = qo[0];
+  for (int k = 1; k < a.n_act; ++k) {
+    const float v = qo[k];
+    if (v > bv) {  // strict: first maximum wins (torch.argmax)
+      bv = v;
+      best = k;
+    }
+  }
+  float qa = a.q_after_target[(size_t)b * a.ldq + c * a.n_act + best];
+  qa = qa * (1.0f - a.term[b * a.n_cat + c]);
+  const float r = a.rew[b * a.n_cat + c];
+  float y = a.linear ? r + (qa - 0.1f) : r + a.gamma * qa;
+  if (a.clip_rect) y = fminf(fmaxf(y, 0.f), 1.f);
+  return qb - y;
+}
+
+// The weighted twin of td_loss_kernel (prioritized replay, vdqn_td_loss_weighted): sample b's loss terms and dQ row are scaled by
+// w[b] — before vm, so w = 1 leaves every rounding of td_loss_kernel as it is — and the thread of column 0 writes
+// err[b] = sum_c |d_bc| * valid_bc / n_cat (the raw TD error, whatever the loss kind).  A kernel of its own rather than a template
+// flag on td_loss_kernel: adding a template parameter to that kernel alone already moves its register allocation, and its float
+// and bf16 instances must keep the ISA they have.
+struct td_w_args : vdqn_td_args {
+  const float* w;  // [batch]
+  float* err;      // [batch] or NULL
+};
+template <typename T>
+__global__ __launch_bounds__(256) void td_loss_w_kernel(const td_w_args a) {
+  const int total = a.batch * a.ldq;
+  float my_loss = 0.f;
+  // one element per thread; a deterministic launch is ONE block that walks all elements (fixed summation order)
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
+    const int b = i / a.ldq, col = i - b * a.ldq;
+    float g = 0.f;
+    if (col < a.n_cat * a.n_act) {
+      const int c = col / a.n_act, ac = col - c * a.n_act;
+      const int act = (int)a.act[b];
+      if (a.q_copy) a.q_copy[(size_t)b * (a.n_cat * a.n_act) + col] = a.q_before[(size_t)b * a.ldq + col];
+      if (ac == act) {
+        const float d = td_error_of(a, b, c, col);
+        const float vm = a.use_valid ? a.valid[b * a.n_cat + c] : 1.0f;
+        const float wb = a.w[b];
+        if (a.loss_kind == 1) {  // Huber, beta = 1 (torch.nn.functional.smooth_l1_loss)
+          const float ad = fabsf(d);
+          my_loss += ((ad < 1.0f ? 0.5f * d * d : ad - 0.5f) * wb) * vm;
+          g = (fminf(fmaxf(d, -1.0f), 1.0f) * wb) * vm * a.inv_count;
+        } else {
+          my_loss += (0.5f * d * d * wb) * vm;
+          g = (d * wb) * vm * a.inv_count;
+        }
+      }
+    }
+    if (col == 0 && a.err) {
+      float e = 0.f;
+      for (int c = 0; c < a.n_cat; ++c) e += fabsf(td_error_of(a, b, c, c * a.n_act + (int)a.act[b])) * (a.use_valid ? a.valid[b * a.n_cat + c] : 1.0f);
+      a.err[b] = e / (float)a.n_cat;
+    }
+    if (a.dq) ((T*)a.dq)[i] = from_f32<T>(g);
+    if (a.dq_f32) a.dq_f32[i] = g;
+  }
+  // block reduction of the loss
+  __shared__ float red[4];
+  float v = my_loss;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const float s = red[0] + red[1] + red[2] + red[3];
+    if (s != 0.f) atomicAdd(a.loss, s * a.inv_count);
+  }
+}
+
 // ground-truth branch (train_q_network.py:170-178)
 template <typename T>
 __global__ __launch_bounds__(256) void gt_loss_kernel(const float* __restrict__ q_before, const int64_t* __restrict__ act,
@@ -562,6 +643,25 @@ extern "C" int vdqn_td_loss(const vdqn_td_args* a, void* stream) {
   ProfScope ps_("td_loss", 0.0, (double)a->batch * a->ldq * 16.0, (hipStream_t)stream);
   if (a->dtype == VDQN_BF16) hipLaunchKernelGGL((td_loss_kernel<bf16raw>), dim3(g), dim3(256), 0, (hipStream_t)stream, *a);
   else hipLaunchKernelGGL((td_loss_kernel<float>), dim3(g), dim3(256), 0, (hipStream_t)stream, *a);
+  VDQN_LAUNCH_CHECK();
+  return VDQN_OK;
+}
+
+extern "C" int vdqn_td_loss_weighted(const vdqn_td_args* a, const float* weight, float* err_out, void* stream) {
+  VDQN_CHECK(a && a->q_before && a->q_after_online && a->q_after_target && a->act && a->rew && a->term && a->loss && weight,
+             "vdqn_td_loss_weighted: null arg");
+  VDQN_CHECK(!a->use_valid || a->valid, "vdqn_td_loss_weighted: use_valid without valid mask");
+  VDQN_CHECK(a->batch > 0 && a->n_cat > 0 && a->n_act > 0 && a->ldq >= a->n_cat * a->n_act, "vdqn_td_loss_weighted: bad dims");
+  VDQN_CHECK(a->dtype == VDQN_F32 || a->dtype == VDQN_BF16, "vdqn_td_loss_weighted: bad dtype");
+  VDQN_CHECK(a->loss_kind == 0 || a->loss_kind == 1, "vdqn_td_loss_weighted: loss_kind %d (0 = half squared error, 1 = Huber)", a->loss_kind);
+  const int g = a->deterministic ? 1 : (a->batch * a->ldq + 255) / 256;
+  ProfScope ps_("td_loss_w", 0.0, (double)a->batch * a->ldq * 16.0 + (double)a->batch * 8.0, (hipStream_t)stream);
+  td_w_args k;
+  static_cast<vdqn_td_args&>(k) = *a;
+  k.w = weight;
+  k.err = err_out;
+  if (a->dtype == VDQN_BF16) hipLaunchKernelGGL((td_loss_w_kernel<bf16raw>), dim3(g), dim3(256), 0, (hipStream_t)stream, k);
+  else hipLaunchKernelGGL((td_loss_w_kernel<float>), dim3(g), dim3(256), 0, (hipStream_t)stream, k);
   VDQN_LAUNCH_CHECK();
   return VDQN_OK;
 }

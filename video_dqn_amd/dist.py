@@ -63,6 +63,14 @@ class BucketAllReduce:
         self.bucket_bytes.append(grad_slice.numel() * grad_slice.element_size())
         self._works.append(dist.all_reduce(grad_slice, op=dist.ReduceOp.SUM, group=self.group, async_op=True))
 
+    def launch_errors(self, err_all: torch.Tensor) -> None:
+        """Prioritized replay: SUM the ranks' per-sample TD errors — a zero-filled f32 [G] buffer in which each rank wrote its slice —
+        so that every rank applies the same priority update.  Queued like launch_loss, behind the last gradient bucket (TDStepper
+        calls it there); `finish` orders the compute stream behind it together with the buckets, i.e. before the priority update."""
+        if self.world_size == 1 and not self.force:
+            return
+        self._works.append(dist.all_reduce(err_all, op=dist.ReduceOp.SUM, group=self.group, async_op=True))
+
     def wait_last(self) -> None:
         """Order the CURRENT stream behind the most recently launched bucket (a consumer of that bucket alone — the per-bucket
         optimiser update of TDStepper(dist_early_adam=True) — on a stream of its own; `finish` still joins everything)."""
@@ -176,6 +184,17 @@ class CAbiBucketAllReduce:
     def take_loss(self):
         p, self._loss_pending = self._loss_pending, None
         return p
+
+    def launch_errors(self, err_all: torch.Tensor) -> None:
+        """As BucketAllReduce.launch_errors: the prioritized-replay error buffer summed on the current stream, joined by `finish`."""
+        if self.world_size == 1 and not self.force:
+            return
+        st = torch.cuda.current_stream()
+        self._lib.check(self.lib.vdqn_allreduce_bucket(self.handle, err_all.data_ptr(), err_all.numel(), self._lib.VDQN_F32, st.cuda_stream),
+                        "vdqn_allreduce_bucket")
+        ev = torch.cuda.Event()
+        ev.record(st)
+        self._events.append(ev)
 
     def close(self) -> None:
         if getattr(self, "handle", None):

@@ -292,7 +292,7 @@ class TDStepper:
     def __init__(self, net: NetEngine, batch: int, lr: float, gamma: float, clip_rect: bool, linear: bool = False,
                  remove_before_reward: bool = False, train_on_ground_truth: bool = False, value_learning: bool = False,
                  target_update_interval: int = 8000, betas=(0.9, 0.999), eps: float = 1e-8, world_size: int = 1,
-                 allreduce=None, loss_kind: str = "l2", allreduce_loss=None, allreduce_wait=None):
+                 allreduce=None, loss_kind: str = "l2", allreduce_loss=None, allreduce_wait=None, allreduce_errors=None):
         net._need_gpu()
         self.net, self.B = net, batch
         self.lib = net.lib
@@ -314,6 +314,10 @@ class TDStepper:
         # the optimiser update of stage 0 / stage 1 then runs behind ITS bucket on a stream of its own, under the rest of the backward
         # pass, instead of behind the last bucket (off by default: DESIGN.md section 7 has the measurement)
         self.allreduce_wait = allreduce_wait
+        # callable() or None: with step(td_error=...) under data parallelism, queued behind the loss exchange on the gradient stream
+        # (dist.launch_errors: the SUM of the ranks' slices of the prioritized-replay error buffer; `finish_allreduce` waits for it)
+        self.allreduce_errors = allreduce_errors
+        self._err_ready = None
         self._post_stream = None
         self._post_used = False
         dev = net.device
@@ -436,6 +440,10 @@ class TDStepper:
                 slot = ahead[1]  # these frames were packed during the previous update (ordered in front of `st` by its last stage)
                 a.packed_frames = self._packed_buffer(slot).data_ptr()
             _lib.check(self.lib.vdqn_net_td_forward(n.handle, C.byref(a), st), "vdqn_net_td_forward")
+            err_ready = None
+            if self._err_ready is not None:  # step(td_error=...): the loss launch has written this rank's errors on `st`
+                err_ready = torch.cuda.Event()
+                err_ready.record()
             if next_frames is not None:
                 # next_frames that ALIAS this call's tensors (same storage) are packed ahead only under the caller's explicit promise
                 # that the content stays as it is — a fourth element True: a loop that replays one resident minibatch.  Without the
@@ -459,6 +467,9 @@ class TDStepper:
                         self.allreduce(self.grads[b:e], stage)
                         if stage == 2 and self.allreduce_loss is not None:
                             self.allreduce_loss(self.loss)
+                        if stage == 2 and err_ready is not None:
+                            torch.cuda.current_stream().wait_event(err_ready)
+                            self.allreduce_errors()
                     if _DIST_EARLY_ADAM and stage < 2 and self.allreduce_wait is not None and n.extra_capacity and self._dist_early_ok():
                         b4, e4 = (b + 3) // 4 * 4, e // 4 * 4
                         if e4 > b4:
@@ -514,7 +525,8 @@ class TDStepper:
                 pos = max(pos, e)
         n.mark_dirty()
 
-    def step(self, before, after, src_kind, act, rew, term, valid=None, gt=None, finish_allreduce=None, next_frames=None) -> torch.Tensor:
+    def step(self, before, after, src_kind, act, rew, term, valid=None, gt=None, finish_allreduce=None, next_frames=None,
+             weights=None, td_error=None) -> torch.Tensor:
         """One iteration of the reference loop body (train_q_network.py:213-227).  Returns the device loss scalar
         (no host sync).
 
@@ -525,7 +537,30 @@ class TDStepper:
         that they are replayed unchanged); a call whose frames are not the ones announced packs its own, as always.  Same arithmetic, same results — and, measured, a SLOWER update (5.81 against 5.74 ms,
         profiles/r03w_ab_pack_ahead.txt: the HBM-bound pack beside layer4 and the head costs more than the start of the update
         gains), so neither bench.py nor the trainer uses it by default; it stays for callers whose frames arrive packed
-        (vdqn_step_args.packed_frames)."""
+        (vdqn_step_args.packed_frames).
+
+        weights (prioritized replay): f32 [B] importance weights on the device — the loss launch scales each sample's loss terms and
+        dQ row by them (vdqn_net_set_sample_weights; ones give the unweighted update bit for bit).  td_error: f32 [B] on the device,
+        where that launch writes each sample's mean |TD error| over the categories; under data parallelism `allreduce_errors` is
+        then queued behind the loss exchange.  TD branch only."""
+        if td_error is not None and weights is None:
+            raise _lib.VdqnError("TDStepper.step: td_error needs weights (it is written by the weighted loss launch)")
+        if weights is not None:
+            if self.gtb:
+                raise _lib.VdqnError("TDStepper.step: sample weights apply to the TD branch only (TRAIN_ON_GROUND_TRUTH has no weighted loss)")
+            for name, t in (("weights", weights), ("td_error", td_error)):
+                if t is not None and (t.dtype != torch.float32 or t.numel() != self.B or not t.is_contiguous() or not t.is_cuda):
+                    raise _lib.VdqnError(f"TDStepper.step: {name} must be a contiguous f32 [{self.B}] device tensor")
+            _lib.check(self.lib.vdqn_net_set_sample_weights(self.net.handle, _ptr(weights), _ptr(td_error)), "vdqn_net_set_sample_weights")
+            self._err_ready = True if (td_error is not None and self.allreduce_errors is not None) else None
+        try:
+            return self._step(before, after, src_kind, act, rew, term, valid, gt, finish_allreduce, next_frames)
+        finally:
+            if weights is not None:
+                self._err_ready = None
+                _lib.check(self.lib.vdqn_net_set_sample_weights(self.net.handle, None, None), "vdqn_net_set_sample_weights")
+
+    def _step(self, before, after, src_kind, act, rew, term, valid, gt, finish_allreduce, next_frames) -> torch.Tensor:
         self.sample_number += 1
         if self.sample_number % self.tui == 0:
             self.sync_target()

@@ -273,6 +273,19 @@ class DeviceFrameStore:
             epoch += 1
             print("reset iterator")
 
+    def prioritized_batches(self, sampler, start_step: int):
+        """Endless stream for prioritized replay (video_dqn_amd.replay.PrioritizedSampler over len(self) samples): update
+        start_step + 1, + 2, ... draws this rank's indices and importance weights on the device and gathers them; yields the
+        `gather` tuple followed by the weights.  Each draw is queued when the caller asks for the batch, i.e. behind the previous
+        update's priority update."""
+        if sampler.n != len(self):
+            raise ValueError(f"prioritized replay: the sampler's table has {sampler.n} entries, the dataset {len(self)} samples")
+        step = start_step
+        while True:
+            step += 1
+            idx, weight = sampler.sample(step)
+            yield self.gather(idx) + (weight,)
+
 
 class RankShardedFrameStore:
     """HBM-resident frames under data parallelism WITHOUT a full copy per rank (round-4 review: eight ranks each holding the whole

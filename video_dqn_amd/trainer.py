@@ -75,10 +75,32 @@ def load_optimizer_state_dict(stepper: TDStepper, sd: dict) -> None:
     stepper.lr, stepper.betas, stepper.eps = g["lr"], tuple(g["betas"]), g["eps"]
 
 
-def save_checkpoint(path, sample_number, model, stepper):
-    torch.save({"sample_number": sample_number,
-                "model_state_dict": model.state_dict(),
-                "optimizer_state_dict": optimizer_state_dict(stepper)}, path)
+def save_checkpoint(path, sample_number, model, stepper, replay_state=None):
+    """replay_state (PRIORITIZED_REPLAY): {'priorities': f32 CPU tensor [N]}, stored under its own key next to the reference's
+    three, which stay as they are (load_model_number and the reference class read the file as before)."""
+    ckpt = {"sample_number": sample_number,
+            "model_state_dict": model.state_dict(),
+            "optimizer_state_dict": optimizer_state_dict(stepper)}
+    if replay_state is not None:
+        ckpt["replay_state"] = replay_state
+    torch.save(ckpt, path)
+
+
+def check_prioritized_replay(config, world_size: int = 1) -> None:
+    """PRIORITIZED_REPLAY applies to the TD branch on a decoded-frame shard dataset held in HBM: raise (before any device work)
+    for every configuration it does not cover, naming the reason (the dataset's size and HBM fit are checked once it is opened)."""
+    from .replay import check_config
+    check_config(float(config.PER_ALPHA), float(config.PER_BETA), int(config.BATCH_SIZE) * world_size)
+    if config.TRAIN_ON_GROUND_TRUTH:
+        raise ValueError("PRIORITIZED_REPLAY needs the TD branch: TRAIN_ON_GROUND_TRUTH has no TD error to prioritise samples by")
+    if config.SYNTHETIC_DATA or config.DATASET in ("none", "synthetic"):
+        raise ValueError("PRIORITIZED_REPLAY needs a fixed dataset: SYNTHETIC_DATA generates its tuples on the fly")
+    if not is_shard_dir(config.DATASET):
+        raise ValueError("PRIORITIZED_REPLAY needs a decoded-frame shard dataset held in HBM, not a feather+JPEG dataset "
+                         "(build one with python -m video_dqn_amd.shards)")
+    if str(getattr(config, "DEVICE_RESIDENT_DATA", "auto")).lower() == "off":
+        raise ValueError("PRIORITIZED_REPLAY draws any sample at any update: it needs the frames in HBM, "
+                         "and DEVICE_RESIDENT_DATA is 'off'")
 
 
 def _to_device_batch(batch, device, num_classes=5):
@@ -131,6 +153,9 @@ class DevicePrefetcher:
 
 def run_train(config, resume_from=-1, max_steps=None, rank=0, world_size=1, log=print):
     """train_q_network.py:84-250."""
+    per = bool(getattr(config, "PRIORITIZED_REPLAY", False))
+    if per:
+        check_prioritized_replay(config, world_size)
     torch.manual_seed(config.SEED)
     np.random.seed(config.SEED)
     log(f"Using: {config.device}")
@@ -153,7 +178,23 @@ def run_train(config, resume_from=-1, max_steps=None, rank=0, world_size=1, log=
             sharded = world_size > 1 and bool(getattr(config, "RANK_SHARDED_DATA", True))
             gather_threads = int(getattr(config, "HOST_GATHER_THREADS", 0))
             headroom = 32 << 30  # activations, workspaces, allocator slack
-            if sharded and resident != "off":
+            if per:
+                # prioritized replay may draw any sample at any update: the full store on every rank, whatever RANK_SHARDED_DATA says
+                from .replay import check_config
+                check_config(float(config.PER_ALPHA), float(config.PER_BETA), B * world_size, len(dataset))
+                need = sum(np.load(p_, mmap_mode="r").shape[0] for p_ in dataset._paths) * 224 * 224 * 3
+                free, _ = torch.cuda.mem_get_info(torch.device(config.device))
+                fits = need + headroom < free
+                if world_size > 1:
+                    fits = agree_all(fits, device=config.device)
+                if not fits:
+                    raise ValueError(f"PRIORITIZED_REPLAY needs the dataset in HBM: its frames ({need / 2**30:.1f} GiB + {headroom >> 30} GiB "
+                                     f"of headroom) do not fit in {free / 2**30:.1f} GiB of free HBM" + (" on every rank" if world_size > 1 else ""))
+                if sharded:
+                    log("PRIORITIZED_REPLAY: every rank holds the full dataset in HBM (RANK_SHARDED_DATA does not apply: "
+                        "any sample may be drawn at any update)")
+                resident = True
+            elif sharded and resident != "off":
                 # N ranks: each holds only the frames its samples of the current epoch reference (re-uploaded per epoch), not a full
                 # copy of the dataset; same minibatch sequence as the full per-rank copy.  Residency is decided from THIS rank's
                 # subset (epoch 0's distinct frames + 10 % for later epochs), one decision for the whole job: a rank on another
@@ -213,16 +254,25 @@ def run_train(config, resume_from=-1, max_steps=None, rank=0, world_size=1, log=
 
     model = build_model(config, max_batch=2 * B)
     comm = BucketAllReduce(world_size) if world_size > 1 else None
+    replay = None
+    if per:
+        from .replay import PrioritizedSampler
+        replay = PrioritizedSampler(len(store), B, model.engine.device, alpha=float(config.PER_ALPHA), beta=float(config.PER_BETA),
+                                     num_steps=int(config.NUM_STEPS), seed=int(config.SEED), rank=rank, world_size=world_size)
+        log(f"prioritized replay over {len(store)} samples: alpha {replay.alpha}, beta {replay.beta0} -> 1.0 at {replay.num_steps}")
     stepper = TDStepper(model.engine, B, lr=config.LEARNING_RATE, gamma=config.GAMMA,
                         clip_rect=(config.LOSS_CLIP == "rect"), linear=config.LINEAR,
                         remove_before_reward=config.REMOVE_BEFORE_REWARD,
                         train_on_ground_truth=config.TRAIN_ON_GROUND_TRUTH, value_learning=config.VALUE_LEARNING,
                         target_update_interval=config.TARGET_UPDATE_INTERVAL, world_size=world_size,
                         allreduce=(comm.launch if comm else None), loss_kind=getattr(config, "LOSS_KIND", "l2"),
-                        allreduce_loss=(comm.launch_loss if comm else None), allreduce_wait=(comm.wait_last if comm else None))
+                        allreduce_loss=(comm.launch_loss if comm else None), allreduce_wait=(comm.wait_last if comm else None),
+                        allreduce_errors=((lambda: comm.launch_errors(replay.err_all)) if comm and replay else None))
     if world_size > 1 and config.ARCHITECTURE != "extra_capacity" and getattr(config, "SYNC_BN", True):
         model.engine.set_bn_sync(world_size)  # train-mode BatchNorm over the global batch, as the single-GPU reference sees it
-    if store is not None:  # minibatches are gathered on the device; no loader, no host copies
+    if replay is not None:
+        iterator = None  # store.prioritized_batches, from the update after the resume point (below)
+    elif store is not None:  # minibatches are gathered on the device; no loader, no host copies
         from .shards import RankShardedFrameStore as _RS
         iterator = store.batches(B, config.SEED) if isinstance(store, _RS) else store.batches(B, config.SEED, rank, world_size)
     elif stream is not None:
@@ -237,6 +287,12 @@ def run_train(config, resume_from=-1, max_steps=None, rank=0, world_size=1, log=
         log(f"Loading model from: {model_loc}")
         model.load_state_dict(snapshot["model_state_dict"])
         load_optimizer_state_dict(stepper, snapshot["optimizer_state_dict"])
+        if replay is not None:
+            if "replay_state" in snapshot:
+                replay.load_state_dict(snapshot["replay_state"])
+                log("prioritized replay: priorities restored from the checkpoint")
+            else:
+                log("prioritized replay: the checkpoint has no replay_state, starting from the uniform table")
     if config.BOOTSTRAP:  # :200-206 — start from a network trained on ground truth (model AND optimiser state)
         log("\n\nBOOTSTRAP\n\n")
         model_loc = getattr(config, "BOOTSTRAP_CHECKPOINT", "") or "logs/trained_gt_0.99/models/epoch99.torch"  # :202
@@ -257,6 +313,9 @@ def run_train(config, resume_from=-1, max_steps=None, rank=0, world_size=1, log=
         eng.mark_dirty()
     stepper.sync_target()  # :208
     stepper.sample_number = sample_number
+    stepper.replay = replay  # the run's PrioritizedSampler (PRIORITIZED_REPLAY), None otherwise: returned with the stepper
+    if replay is not None:
+        iterator = store.prioritized_batches(replay, sample_number)
 
     running_loss = None
     host_loss = torch.zeros(2, dtype=torch.float32).pin_memory()
@@ -275,12 +334,17 @@ def run_train(config, resume_from=-1, max_steps=None, rank=0, world_size=1, log=
         while sample_number < num_steps:
             sample_number += 1
             model.set_train()  # :221 (flags only; the engine's BatchNorm is always in eval mode in extra_capacity)
-            before, after, src_kind, act, rew, term, valid, gt = next(iterator)
+            item = next(iterator)
+            before, after, src_kind, act, rew, term, valid, gt = item[:8]
             # the stepper performs the :215-216 target refresh itself (sample_number % TARGET_UPDATE_INTERVAL == 0)
             loss = stepper.step(before, after, src_kind, act, rew, term,
                                 valid if config.REMOVE_BEFORE_REWARD else None,
                                 gt if config.TRAIN_ON_GROUND_TRUTH else None,
-                                finish_allreduce=(comm.finish if comm else None))
+                                finish_allreduce=(comm.finish if comm else None),
+                                weights=(item[8] if replay is not None else None),
+                                td_error=(replay.err if replay is not None else None))
+            if replay is not None:
+                replay.update()  # behind the loss launch (and, with N ranks, the error exchange that finish_allreduce joined)
             # every rank's `loss` is its share of the global mean (the TD kernel divides by the global batch): their SUM is the
             # batch-mean loss the reference feeds into its running average every update (:228-231).  The stepper has queued that
             # 4-byte all-reduce on the gradient stream behind the last gradient bucket (dist.launch_loss); it is waited for and
@@ -312,9 +376,12 @@ def run_train(config, resume_from=-1, max_steps=None, rank=0, world_size=1, log=
                 print(f"\rbatch:{sample_number}/{config.NUM_STEPS} avg_loss: {running_loss}", end="")
             if log_now and running_loss is not None:
                 config.writer.add_scalar("avg_q_loss/train", running_loss, sample_number)  # :236-238
+            if log_now and replay is not None:
+                config.writer.add_scalar("per/beta", replay.beta(sample_number), sample_number)  # (host arithmetic: nothing read back)
             if sample_number % config.CHECKPOINT_INTERVAL == 0 and rank == 0:  # :241-247
                 torch.cuda.synchronize()
-                save_checkpoint(f"{config.folder}/models/sample{sample_number}.torch", sample_number, model, stepper)
+                save_checkpoint(f"{config.folder}/models/sample{sample_number}.torch", sample_number, model, stepper,
+                                replay_state=(replay.state_dict() if replay is not None else None))
         if pending is not None:
             consume(pending)
         torch.cuda.synchronize()
