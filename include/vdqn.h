@@ -454,6 +454,35 @@ int vdqn_per_sample(const float* prio, int64_t n, int32_t global_batch, uint64_t
 int vdqn_per_update(float* prio, int64_t n, const int64_t* idx, const float* err, int32_t global_batch, double alpha, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Random shift + left-right mirror augmentation of the training minibatch (DrQ / RAD style), fused into the input pack.  The
+ * reference's only transform is Resize + CenterCrop + Normalize (util/torch.py:5-12), which vdqn_pack_input fuses; these entries
+ * extend that call site and the batch hand-over of train_q_network.py:127-131.  One int32 {sx, sy, flip, 0} per SAMPLE, shared by
+ * its frames and by s and s'.  Output pixel (Y, X) of a frame reads source pixel
+ *   Ys = clamp(Y + sy, 0, 223), Xs = clamp(X + sx, 0, 223), Xs = 223 - Xs if flip != 0
+ * (mirror the source, pad by edge replication, crop at the offset): an index remap of uint8 pixels, so the packed operand equals
+ * vdqn_pack_input of the augmented frames bit for bit.  Any int32 sx, sy is safe.  The arithmetic of the draw is written out in
+ * video_dqn_amd/csrc/augment.hip.
+ * ------------------------------------------------------------------------------------------------ */
+/* params[i] (int32 [n][4], 16-byte aligned) = the draw of sample first + i of a global batch of `global_batch` samples at update
+ * `step`: sx, sy uniform in [-pad, pad] (pad in 0 .. 32), flip a fair bit when `flip` != 0, else 0.  A rank of a data-parallel
+ * job passes first = rank * B, n = B and gets its slice of the one-process draw. */
+int vdqn_aug_draw(uint64_t seed, uint64_t step, int32_t global_batch, int32_t first, int32_t n, int32_t pad, int32_t flip,
+                  int32_t* params, void* stream);
+/* act_out[b] = act[b] with a0 <-> a1 exchanged where params[b].flip != 0 (a mirrored left turn is a right turn), a copy elsewhere.
+ * int64 [n]; a0 != a1, both in 0 .. 2.  act_out may be act. */
+int vdqn_aug_swap_actions(const int64_t* act, const int32_t* params, int32_t n, int32_t a0, int32_t a1, int64_t* act_out,
+                          void* stream);
+/* vdqn_pack_input for uint8 NHWC frames (src_kind 0) with the remap: frame i takes params[(i / frames_per_sample) % n_params].
+ * src, dst and params 16-byte aligned.  All-zero params give vdqn_pack_input's output. */
+int vdqn_pack_input_aug(const void* src, void* dst, int32_t n_img, int32_t frames_per_sample, const int32_t* params,
+                        int32_t n_params, int32_t dtype, void* stream);
+/* While set (params != NULL: device int32 [batch][4]), vdqn_net_td_forward packs `before` and `after` with vdqn_pack_input_aug
+ * (the same params for both) where it calls vdqn_pack_input otherwise; it then fails for src_kind != 0 and for
+ * vdqn_step_args.packed_frames.  NULL restores the plain pack.  The pointer is read at every vdqn_net_td_forward call until it is
+ * changed. */
+int vdqn_net_set_augment(vdqn_net* net, const int32_t* params);
+
+/* ------------------------------------------------------------------------------------------------
  * Data-parallel exchange: one process per GPU, the flat f32 gradient SUM-all-reduced over RCCL (xGMI)
  * in the three stage buckets of vdqn_net_stage_range, each issued on vdqn_net_grad_stream(net) when its stage's
  * vdqn_net_backward_stage call has returned; the caller's stream waits for the three collectives (hipStreamWaitEvent) before

@@ -138,6 +138,10 @@ _SIGS = {
     "vdqn_per_workspace_bytes": (c_i64, [c_i64]),
     "vdqn_per_sample": (C.c_int, [c_vp, c_i64, c_i32, C.c_uint64, C.c_uint64, C.c_double, c_vp, c_vp, c_vp, c_vp]),
     "vdqn_per_update": (C.c_int, [c_vp, c_i64, c_vp, c_vp, c_i32, C.c_double, c_vp]),
+    "vdqn_aug_draw": (C.c_int, [C.c_uint64, C.c_uint64, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp]),
+    "vdqn_aug_swap_actions": (C.c_int, [c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp]),
+    "vdqn_pack_input_aug": (C.c_int, [c_vp, c_vp, c_i32, c_i32, c_vp, c_i32, c_i32, c_vp]),
+    "vdqn_net_set_augment": (C.c_int, [c_vp, c_vp]),
 }
 COMM_UID_BYTES = 128
 EXPORTS = tuple(_SIGS)

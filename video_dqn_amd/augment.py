@@ -1,0 +1,94 @@
+"""Random shift and left-right mirror augmentation of the training minibatch, fused into the input pack.
+
+The reference shows the network every frame as the same 224 x 224 centre crop (``Resize + CenterCrop + Normalize``,
+util/torch.py:5-12).  With ``AUG_SHIFT_PAD`` > 0 and / or ``AUG_FLIP`` the trainer draws one ``(sx, sy, flip)`` per update and
+per sample on the device — shared by the sample's frames and by s and s', because the action label is the camera motion between
+the two — and the engine packs the frames through ``vdqn_pack_input_aug``: mirror the source, pad it by edge replication, crop
+at the drawn offset.  Both are index remaps of uint8 pixels, so the stem operand equals ``vdqn_pack_input`` of the augmented
+frames bit for bit (video_dqn_amd/csrc/augment.hip has the arithmetic, tests/aug_oracle.py restates it in numpy).  A mirrored
+sample's action label has ``AUG_FLIP_ACTIONS`` exchanged (a left turn becomes a right turn).  Three small launches and no host
+round trip per update.
+
+Data parallelism keeps N ranks == one process on the big batch: every rank draws its slice of the one global draw.
+"""
+from __future__ import annotations
+
+import torch
+
+from . import _lib
+
+MAX_PAD = 32  # vdqn_aug_draw (include/vdqn.h)
+
+
+def check_config(pad, flip, flip_actions) -> None:
+    """Raise ValueError, naming the config key, for values the augmentation does not take (host only: no device work)."""
+    if isinstance(pad, bool) or not isinstance(pad, int) or not 0 <= pad <= MAX_PAD:
+        raise ValueError(f"AUG_SHIFT_PAD must be an integer in [0, {MAX_PAD}] (got {pad!r})")
+    if not isinstance(flip, bool):
+        raise ValueError(f"AUG_FLIP must be True or False (got {flip!r})")
+    fa = list(flip_actions) if isinstance(flip_actions, (list, tuple)) else None
+    if (fa is None or len(fa) != 2 or any(isinstance(a, bool) or not isinstance(a, int) for a in fa)
+            or fa[0] == fa[1] or not all(0 <= a <= 2 for a in fa)):
+        raise ValueError(f"AUG_FLIP_ACTIONS must be two different actions out of 0, 1, 2 (got {flip_actions!r})")
+
+
+def _u64(v: int) -> int:
+    return int(v) & (2**64 - 1)
+
+
+def aug_draw(seed: int, step: int, global_batch: int, first: int, n: int, pad: int, flip: bool, device="cuda",
+             out: torch.Tensor = None) -> torch.Tensor:
+    """vdqn_aug_draw on the current stream -> int32 [n][4] {sx, sy, flip, 0} of samples first .. first + n of the global batch."""
+    dev = torch.device(device) if out is None else out.device
+    with torch.cuda.device(dev):
+        if out is None:
+            out = torch.empty((n, 4), dtype=torch.int32, device=dev)
+        _lib.check(_lib.load().vdqn_aug_draw(_u64(seed), _u64(step), global_batch, first, n, pad, int(bool(flip)), out.data_ptr(),
+                                             torch.cuda.current_stream().cuda_stream), "vdqn_aug_draw")
+    return out
+
+
+def pack_input_aug(src: torch.Tensor, params: torch.Tensor, frames_per_sample: int, dtype: torch.dtype) -> torch.Tensor:
+    """uint8 NHWC [n][224][224][3] frames + int32 [*][4] params -> the augmented stem operand [n][115][115][16]."""
+    if src.dtype != torch.uint8 or not src.is_contiguous() or params.dtype != torch.int32 or not params.is_contiguous():
+        raise _lib.VdqnError("pack_input_aug: src must be contiguous uint8 NHWC frames and params contiguous int32 [*][4]")
+    n_img = src.numel() // (224 * 224 * 3)
+    with torch.cuda.device(src.device):
+        dst = torch.empty((n_img, 115, 115, 16), dtype=dtype, device=src.device)
+        code = _lib.VDQN_BF16 if dtype == torch.bfloat16 else _lib.VDQN_F32
+        _lib.check(_lib.load().vdqn_pack_input_aug(src.data_ptr(), dst.data_ptr(), n_img, frames_per_sample, params.data_ptr(),
+                                                   params.numel() // 4, code, torch.cuda.current_stream().cuda_stream), "vdqn_pack_input_aug")
+    return dst
+
+
+class Augmenter:
+    """The per-update draw of one rank: ``draw(step)`` -> this rank's int32 [B][4] on the device (valid until the next call),
+    ``actions(act)`` -> the action labels with ``flip_actions`` exchanged for the mirrored samples of that draw."""
+
+    def __init__(self, batch: int, device, pad: int = 0, flip: bool = False, flip_actions=(1, 2), seed: int = 0, rank: int = 0,
+                 world_size: int = 1):
+        check_config(pad, flip, flip_actions)
+        self.lib = _lib.load()
+        self.B, self.rank, self.world = int(batch), int(rank), int(world_size)
+        self.G = self.B * self.world
+        self.pad, self.flip, self.flip_actions, self.seed = int(pad), bool(flip), tuple(int(a) for a in flip_actions), int(seed)
+        self.device = torch.device(device)
+        with torch.cuda.device(self.device):
+            self.params = torch.zeros((self.B, 4), dtype=torch.int32, device=self.device)
+            self._act = torch.zeros(self.B, dtype=torch.int64, device=self.device)
+        self.last_step = None  # the update number of the draw `params` holds
+
+    def draw(self, step: int) -> torch.Tensor:
+        aug_draw(self.seed, step, self.G, self.rank * self.B, self.B, self.pad, self.flip, out=self.params)
+        self.last_step = int(step)
+        return self.params
+
+    def actions(self, act: torch.Tensor) -> torch.Tensor:
+        if not self.flip:
+            return act
+        if act.dtype != torch.int64 or act.numel() != self.B or not act.is_contiguous() or act.device != self.params.device:
+            raise _lib.VdqnError(f"Augmenter.actions: act must be a contiguous int64 [{self.B}] tensor on {self.params.device}")
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.vdqn_aug_swap_actions(act.data_ptr(), self.params.data_ptr(), self.B, self.flip_actions[0], self.flip_actions[1],
+                                                      self._act.data_ptr(), torch.cuda.current_stream().cuda_stream), "vdqn_aug_swap_actions")
+        return self._act

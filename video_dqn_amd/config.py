@@ -22,7 +22,12 @@ archs/HabitatDQNMultiAction.py:11, which needs a download this build cannot make
 BOOTSTRAP branch loads; default = the path hard-coded at train_q_network.py:202), PRIORITIZED_REPLAY (False: draw every
 minibatch by priority — prioritized experience replay, sampled and updated on the GPU — instead of in shuffled epochs; the TD
 branch on an HBM-resident decoded-frame shard dataset only), PER_ALPHA (0.6: priority exponent, p = (|TD error| + 1e-6)^alpha),
-PER_BETA (0.4: importance-sampling exponent at step 0, annealed linearly to 1.0 at NUM_STEPS).
+PER_BETA (0.4: importance-sampling exponent at step 0, annealed linearly to 1.0 at NUM_STEPS), AUG_SHIFT_PAD (0 = off, 0..32: random
+shift augmentation — every update shows each sample padded by this many edge-replicated pixels and cropped at a random offset, one
+draw per sample shared by its frames and by s and s', fused into the input pack on the GPU), AUG_FLIP (False: mirror each sample
+left-right with probability 1/2, s and s' together), AUG_FLIP_ACTIONS ([1, 2]: the two action labels a mirror exchanges — turn left
+and turn right; from dataloaders/gibson.py:76 and habitat_test_env.py:242 under Habitat-API 0.1.3's STOP 0 / FORWARD 1 / LEFT 2 /
+RIGHT 3, unverified here, hence a key).
 """
 from __future__ import annotations
 
@@ -148,6 +153,9 @@ def get_cfg_defaults() -> CfgNode:
     c.PRIORITIZED_REPLAY = False  # sample minibatches by priority (PER, on the device) instead of shuffled epochs
     c.PER_ALPHA = 0.6             # priority exponent: p = (|TD error| + 1e-6) ^ PER_ALPHA
     c.PER_BETA = 0.4              # importance-sampling exponent at step 0, annealed linearly to 1.0 at NUM_STEPS
+    c.AUG_SHIFT_PAD = 0           # random-shift augmentation: pad by this many replicated edge pixels, crop at a random offset (0 = off, <= 32)
+    c.AUG_FLIP = False            # random left-right mirror of a sample (s and s' together), with its action label exchanged
+    c.AUG_FLIP_ACTIONS = [1, 2]   # the two action labels a mirror exchanges (turn left, turn right)
     return c
 
 

@@ -1,0 +1,182 @@
+// Random shift + left-right mirror augmentation (DrQ / RAD style), fused into the input pack: both transforms are index remaps of
+// uint8 pixels, so the augmented stem operand is EXACTLY vdqn_pack_input of the augmented frames (tests/aug_oracle.py restates
+// everything below in numpy; the tests are bit for bit).  No host round trip: the draw, the action swap and the pack are launches
+// on the caller's stream.
+//
+// One triple (sx, sy, flip) per update and per SAMPLE, shared by the sample's F frames and by s and s' (the action label is the
+// camera motion between s and s': a relative shift between the two would look like a small turn).
+//
+// Draw of sample j of the global batch G at update `step`, P = pad (uint64 arithmetic, wrapping):
+//   key  = splitmix64(seed ^ 0x4155474D454E5431)          "AUGMENT1": a stream of its own, not prioritized replay's splitmix64(seed)
+//   h    = splitmix64(key ^ (step * G + j))
+//   sx   = (((h         & 0xFFFF) * (2P + 1)) >> 16) - P
+//   sy   = ((((h >> 16) & 0xFFFF) * (2P + 1)) >> 16) - P
+//   flip = flip_on ? (h >> 32) & 1 : 0
+//   params[j] = int32 {sx, sy, flip, 0}
+// Transform of one frame, output pixel (Y, X), 0 <= Y, X < 224:
+//   Xs = clamp(X + sx, 0, 223);  Ys = clamp(Y + sy, 0, 223);  if flip: Xs = 223 - Xs;   out[Y][X][c] = in[Ys][Xs][c]
+// i.e. mirror the source, pad it by edge replication, crop at the drawn offset.  The packed operand's zero border (the
+// convolution's padding) stays zero.  The clamps hold for ANY int32 sx, sy and flip != 0 means 1: no parameter value makes the
+// kernel read outside the frame.
+#include "common.h"
+
+namespace {
+
+constexpr uint64_t kAugStream = 0x4155474D454E5431ull;
+constexpr int kMaxPad = 32;
+
+__host__ __device__ inline uint64_t splitmix64(uint64_t x) {
+  uint64_t z = x + 0x9E3779B97F4A7C15ull;
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  return z ^ (z >> 31);
+}
+
+// ---- aug_draw: one thread per sample ------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void aug_draw_kernel(uint64_t seed, uint64_t step, int G, int first, int n, int pad, int flip_on,
+                                                       int4* __restrict__ params) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const uint64_t key = splitmix64(seed ^ kAugStream);
+  const uint64_t h = splitmix64(key ^ (step * (uint64_t)G + (uint64_t)(first + i)));
+  const uint32_t span = 2u * (uint32_t)pad + 1u;
+  const int sx = (int)((((uint32_t)h & 0xFFFFu) * span) >> 16) - pad;
+  const int sy = (int)((((uint32_t)(h >> 16) & 0xFFFFu) * span) >> 16) - pad;
+  params[i] = make_int4(sx, sy, flip_on ? (int)((h >> 32) & 1) : 0, 0);
+}
+
+// ---- aug_swap_actions: a0 <-> a1 for the flipped samples, a copy otherwise -------------------------------------------------------
+__global__ __launch_bounds__(256) void aug_swap_actions_kernel(const int64_t* __restrict__ act, const int4* __restrict__ params, int n,
+                                                               int64_t a0, int64_t a1, int64_t* __restrict__ act_out) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= n) return;
+  int64_t a = act[b];
+  if (params[b].z != 0) a = a == a0 ? a1 : a == a1 ? a0 : a;
+  act_out[b] = a;
+}
+
+// ---- pack_input_aug: pack_input_rows_kernel (pointwise.hip) with the remap ------------------------------------------------------
+// A block walks kPackPairs pairs of packed rows of one frame.  A pair covers the four output rows Y0 .. Y0 + 3 (Y0 a multiple of 4:
+// a pair lies entirely inside the frame or entirely in the zero border); their source rows clamp(Y0 + r + sy) are non-decreasing in
+// r and at most 3 apart, so the DISTINCT ones are Ys0 .. Ys3 and output row r reads LDS slot Ys_r - Ys0: every source row of the
+// pair comes from HBM once, as 42 16-byte vectors.  The X remap and the mirror pick which 3 LDS bytes a pixel reads.  The
+// normalisation table is built with the expression of pack_input_rows_kernel: same bits.
+constexpr int kPackPairs = 4;
+__device__ __forceinline__ int clamp223(int v) { return min(max(v, 0), 223); }
+
+template <typename T>
+__global__ __launch_bounds__(256) void pack_input_aug_kernel(const uint8_t* __restrict__ src, T* __restrict__ dst, int frames_per_sample,
+                                                             const int4* __restrict__ params, int n_params) {
+  __shared__ uint4 rows[4][42];
+  __shared__ T lut[3][256];
+  const int n = blockIdx.y;
+  const int tid = threadIdx.x;
+  {
+    const float mean[3] = {0.485f, 0.456f, 0.406f};
+    const float stdv[3] = {0.229f, 0.224f, 0.225f};
+#pragma unroll
+    for (int c = 0; c < 3; ++c) lut[c][tid] = from_f32<T>((((float)tid / 255.0f) - mean[c]) / stdv[c]);
+  }
+  const int4 p = params[(n / frames_per_sample) % n_params];
+  // |shift| > 223 already selects the edge pixel everywhere: clamping the shift first gives the same pixels without int overflow
+  const int sx = min(max(p.x, -224), 224), sy = min(max(p.y, -224), 224);
+  const bool flip = p.z != 0;
+  const int yy = tid / 115, x = tid - yy * 115;
+  // byte offsets of this thread's two source pixels inside a row (the same for every pair)
+  int o0 = 0, o1 = 0;
+  {
+    const int xs = x - 2;
+    int X0 = clamp223(2 * xs + sx), X1 = clamp223(2 * xs + 1 + sx);
+    if (flip) {
+      X0 = 223 - X0;
+      X1 = 223 - X1;
+    }
+    o0 = 3 * X0;
+    o1 = 3 * X1;
+  }
+  for (int pr = 0; pr < kPackPairs; ++pr) {
+    const int y0 = 2 * ((int)blockIdx.x * kPackPairs + pr);  // packed rows y0, y0 + 1 -> output rows 2 (y0 - 2) .. + 3
+    if (y0 >= 115) break;
+    const int Y0 = 2 * (y0 - 2);
+    const bool inside = (unsigned)Y0 < 224u;  // Y0 % 4 == 0: Y0 .. Y0 + 3 are all inside, or the pair is zero border
+    const int Ys0 = clamp223(Y0 + sy), Ys3 = clamp223(Y0 + 3 + sy);
+    __syncthreads();  // the previous pair's readers are done (first pass: the table is written)
+    if (tid < 168 && inside) {
+      const int s = tid / 42, c = tid - s * 42;
+      if (Ys0 + s <= Ys3) rows[s][c] = reinterpret_cast<const uint4*>(src + ((size_t)n * 224 + (Ys0 + s)) * 672)[c];
+    }
+    __syncthreads();
+    const int y = y0 + yy;
+    if (tid >= 230 || y >= 115) continue;
+    const int ys = y - 2, xs = x - 2;
+    __attribute__((aligned(16))) T v[16];
+#pragma unroll
+    for (int e = 0; e < 16; ++e) v[e] = from_f32<T>(0.f);
+    if (inside && (unsigned)ys < 112u && (unsigned)xs < 112u) {
+      const int r0 = clamp223(Y0 + 2 * yy + sy) - Ys0, r1 = clamp223(Y0 + 2 * yy + 1 + sy) - Ys0;  // LDS slots, 0 .. 3
+      const uint8_t* b0 = reinterpret_cast<const uint8_t*>(rows[r0]);
+      const uint8_t* b1 = reinterpret_cast<const uint8_t*>(rows[r1]);
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        v[c] = lut[c][b0[o0 + c]];
+        v[3 + c] = lut[c][b0[o1 + c]];
+        v[6 + c] = lut[c][b1[o0 + c]];
+        v[9 + c] = lut[c][b1[o1 + c]];
+      }
+    }
+    T* d = dst + ((size_t)n * 115 * 115 + (size_t)y * 115 + x) * 16;
+    constexpr int V16 = (int)(16 * sizeof(T) / 16);
+#pragma unroll
+    for (int q = 0; q < V16; ++q) reinterpret_cast<uint4*>(d)[q] = reinterpret_cast<const uint4*>(v)[q];
+  }
+}
+
+}  // namespace
+
+extern "C" int vdqn_aug_draw(uint64_t seed, uint64_t step, int32_t global_batch, int32_t first, int32_t n, int32_t pad, int32_t flip,
+                             int32_t* params, void* stream) {
+  VDQN_CHECK(params, "vdqn_aug_draw: null params");
+  VDQN_CHECK(n > 0, "vdqn_aug_draw: n = %d", n);
+  VDQN_CHECK(global_batch >= 1 && first >= 0 && (int64_t)first + n <= (int64_t)global_batch,
+             "vdqn_aug_draw: samples %d .. %lld outside the global batch of %d", first, (long long)first + n, global_batch);
+  VDQN_CHECK(pad >= 0 && pad <= kMaxPad, "vdqn_aug_draw: pad %d outside [0, %d]", pad, kMaxPad);
+  VDQN_CHECK(((uintptr_t)params & 15) == 0, "vdqn_aug_draw: params must be 16-byte aligned");
+  ProfScope ps_("aug_draw", 0.0, (double)n * 16.0, (hipStream_t)stream);
+  hipLaunchKernelGGL(aug_draw_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, seed, step, (int)global_batch, (int)first, (int)n,
+                     (int)pad, (int)(flip != 0), (int4*)params);
+  VDQN_LAUNCH_CHECK();
+  return VDQN_OK;
+}
+
+extern "C" int vdqn_aug_swap_actions(const int64_t* act, const int32_t* params, int32_t n, int32_t a0, int32_t a1, int64_t* act_out,
+                                     void* stream) {
+  VDQN_CHECK(act && params && act_out, "vdqn_aug_swap_actions: null arg");
+  VDQN_CHECK(n > 0, "vdqn_aug_swap_actions: n = %d", n);
+  VDQN_CHECK(a0 != a1 && a0 >= 0 && a0 <= 2 && a1 >= 0 && a1 <= 2, "vdqn_aug_swap_actions: actions (%d, %d) must be two different values of 0 .. 2",
+             a0, a1);
+  VDQN_CHECK(((uintptr_t)params & 15) == 0, "vdqn_aug_swap_actions: params must be 16-byte aligned");
+  ProfScope ps_("aug_swap_actions", 0.0, (double)n * 32.0, (hipStream_t)stream);
+  hipLaunchKernelGGL(aug_swap_actions_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, act, (const int4*)params, (int)n,
+                     (int64_t)a0, (int64_t)a1, act_out);
+  VDQN_LAUNCH_CHECK();
+  return VDQN_OK;
+}
+
+extern "C" int vdqn_pack_input_aug(const void* src, void* dst, int32_t n_img, int32_t frames_per_sample, const int32_t* params,
+                                   int32_t n_params, int32_t dtype, void* stream) {
+  VDQN_CHECK(src && dst && params, "vdqn_pack_input_aug: null arg");
+  VDQN_CHECK(n_img > 0 && frames_per_sample > 0 && n_params > 0, "vdqn_pack_input_aug: n_img %d, frames_per_sample %d, n_params %d must be > 0",
+             n_img, frames_per_sample, n_params);
+  VDQN_CHECK(dtype == VDQN_F32 || dtype == VDQN_BF16, "vdqn_pack_input_aug: bad dtype");
+  VDQN_CHECK((((uintptr_t)src | (uintptr_t)dst | (uintptr_t)params) & 15) == 0, "vdqn_pack_input_aug: src, dst and params must be 16-byte aligned");
+  ProfScope ps_("pack_input_aug", 0.0, (double)n_img * (224.0 * 224 * 3 + 115.0 * 115 * 16 * (dtype == VDQN_BF16 ? 2 : 4)), (hipStream_t)stream);
+  const dim3 grid((58 + kPackPairs - 1) / kPackPairs, n_img);
+  if (dtype == VDQN_BF16)
+    hipLaunchKernelGGL((pack_input_aug_kernel<bf16raw>), grid, dim3(256), 0, (hipStream_t)stream, (const uint8_t*)src, (bf16raw*)dst,
+                       (int)frames_per_sample, (const int4*)params, (int)n_params);
+  else
+    hipLaunchKernelGGL((pack_input_aug_kernel<float>), grid, dim3(256), 0, (hipStream_t)stream, (const uint8_t*)src, (float*)dst,
+                       (int)frames_per_sample, (const int4*)params, (int)n_params);
+  VDQN_LAUNCH_CHECK();
+  return VDQN_OK;
+}

@@ -132,6 +132,7 @@ struct vdqn_net {
   int bwd_samples = 0;  // batch of the update in flight (set by vdqn_net_td_forward; sizes the bwd workspace layout)
   const float* sample_w = nullptr;  // vdqn_net_set_sample_weights: [B] importance weights of the TD loss (NULL: the reference loss)
   float* sample_err = nullptr;      // ... and where that launch writes the [B] per-sample TD errors (may be NULL)
+  const int32_t* aug = nullptr;     // vdqn_net_set_augment: int32 [B][4] shift / mirror of each sample (NULL: the plain pack)
   hipStream_t side = nullptr;
   hipStream_t side2 = nullptr;  // the second half of the online forward pass
   std::vector<hipEvent_t> events;
@@ -1175,6 +1176,13 @@ extern "C" int vdqn_net_set_sample_weights(vdqn_net* net, const float* weight, f
   return VDQN_OK;
 }
 
+extern "C" int vdqn_net_set_augment(vdqn_net* net, const int32_t* params) {
+  VDQN_CHECK(net, "vdqn_net_set_augment: null net");
+  VDQN_CHECK(((uintptr_t)params & 15) == 0, "vdqn_net_set_augment: params must be 16-byte aligned");
+  net->aug = params;
+  return VDQN_OK;
+}
+
 extern "C" void vdqn_net_destroy(vdqn_net* net) {
   if (!net) return;
   if (net->side) {
@@ -1349,6 +1357,8 @@ extern "C" int vdqn_net_td_forward(vdqn_net* net, const vdqn_step_args* a, void*
   VDQN_CHECK(B >= 1 && 2 * B <= net->cfg.max_batch, "vdqn_net_td_forward: batch %d needs max_batch >= %d", B, 2 * B);
   VDQN_CHECK(gtb ? (a->gt != nullptr) : (a->after && a->packed_target && a->rew && a->term), "vdqn_net_td_forward: missing inputs for this loss branch");
   VDQN_CHECK(gtb || a->acts_target, "vdqn_net_td_forward: acts_target is NULL");
+  VDQN_CHECK(!net->aug || a->src_kind == 0, "vdqn_net_td_forward: augmentation is set (vdqn_net_set_augment): it takes uint8 NHWC frames (src_kind 0), not src_kind %d", a->src_kind);
+  VDQN_CHECK(!net->aug || !a->packed_frames, "vdqn_net_td_forward: augmentation is set (vdqn_net_set_augment): packed_frames were packed without it");
   hipStream_t st = (hipStream_t)stream;
   const int F = net->cfg.num_frames, dt = net->cfg.dtype;
   const int ns_online = step_layout_samples(net, a);
@@ -1367,7 +1377,10 @@ extern "C" int vdqn_net_td_forward(vdqn_net* net, const vdqn_step_args* a, void*
   // (tried and measured slower, experiments/: the s' frames packed first with the target pass right behind them; the two packs
   // on two streams; a split weight fold with layer3+ beside the stem; stage folds behind their early Adam; online and target
   // forward as one chain of grouped launches; the online pass as two half-batch passes on two streams)
-  if (!a->packed_frames) {
+  if (net->aug) {  // the same [B][4] shift / mirror for s and s' (vdqn_net_set_augment)
+    RC(vdqn_pack_input_aug(a->before, ao + A.t_in, B * F, F, net->aug, B, dt, tst));
+    if (!gtb) RC(vdqn_pack_input_aug(a->after, ao + A.t_in + (int64_t)B * F * frame_bytes, B * F, F, net->aug, B, dt, tst));
+  } else if (!a->packed_frames) {
     RC(vdqn_pack_input(a->before, a->src_kind, ao + A.t_in, B * F, dt, tst));
     if (!gtb) RC(vdqn_pack_input(a->after, a->src_kind, ao + A.t_in + (int64_t)B * F * frame_bytes, B * F, dt, tst));
   }

@@ -526,7 +526,7 @@ class TDStepper:
         n.mark_dirty()
 
     def step(self, before, after, src_kind, act, rew, term, valid=None, gt=None, finish_allreduce=None, next_frames=None,
-             weights=None, td_error=None) -> torch.Tensor:
+             weights=None, td_error=None, augment=None) -> torch.Tensor:
         """One iteration of the reference loop body (train_q_network.py:213-227).  Returns the device loss scalar
         (no host sync).
 
@@ -542,7 +542,17 @@ class TDStepper:
         weights (prioritized replay): f32 [B] importance weights on the device — the loss launch scales each sample's loss terms and
         dQ row by them (vdqn_net_set_sample_weights; ones give the unweighted update bit for bit).  td_error: f32 [B] on the device,
         where that launch writes each sample's mean |TD error| over the categories; under data parallelism `allreduce_errors` is
-        then queued behind the loss exchange.  TD branch only."""
+        then queued behind the loss exchange.  TD branch only.
+
+        augment (video_dqn_amd/augment.py): int32 [B][4] {sx, sy, flip, 0} on the device — this update's frames (uint8 NHWC, src_kind
+        0) are packed through vdqn_pack_input_aug with them, the same for `before` and `after` (vdqn_net_set_augment, cleared after
+        the update).  The caller passes the action labels that go with the mirrored samples (Augmenter.actions)."""
+        if augment is not None:
+            if augment.dtype != torch.int32 or tuple(augment.shape) != (self.B, 4) or not augment.is_contiguous() or not augment.is_cuda:
+                raise _lib.VdqnError(f"TDStepper.step: augment must be a contiguous int32 [{self.B}][4] device tensor")
+            if next_frames is not None:
+                raise _lib.VdqnError("TDStepper.step: next_frames are packed ahead without the augmentation; pass one or the other")
+            self._ahead = None  # frames packed ahead by an earlier call were packed without it: this call packs its own
         if td_error is not None and weights is None:
             raise _lib.VdqnError("TDStepper.step: td_error needs weights (it is written by the weighted loss launch)")
         if weights is not None:
@@ -554,8 +564,12 @@ class TDStepper:
             _lib.check(self.lib.vdqn_net_set_sample_weights(self.net.handle, _ptr(weights), _ptr(td_error)), "vdqn_net_set_sample_weights")
             self._err_ready = True if (td_error is not None and self.allreduce_errors is not None) else None
         try:
+            if augment is not None:
+                _lib.check(self.lib.vdqn_net_set_augment(self.net.handle, _ptr(augment)), "vdqn_net_set_augment")
             return self._step(before, after, src_kind, act, rew, term, valid, gt, finish_allreduce, next_frames)
         finally:
+            if augment is not None:
+                _lib.check(self.lib.vdqn_net_set_augment(self.net.handle, None), "vdqn_net_set_augment")
             if weights is not None:
                 self._err_ready = None
                 _lib.check(self.lib.vdqn_net_set_sample_weights(self.net.handle, None, None), "vdqn_net_set_sample_weights")

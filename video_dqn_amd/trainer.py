@@ -103,6 +103,12 @@ def check_prioritized_replay(config, world_size: int = 1) -> None:
                          "and DEVICE_RESIDENT_DATA is 'off'")
 
 
+def check_augment(pad, flip, flip_actions) -> None:
+    """AUG_SHIFT_PAD / AUG_FLIP / AUG_FLIP_ACTIONS: raise ValueError naming the key (before any device work)."""
+    from .augment import check_config
+    check_config(pad, flip, flip_actions)
+
+
 def _to_device_batch(batch, device, num_classes=5):
     before, after, act, rew, term, gt, valid = batch
     nb = dict(non_blocking=True)
@@ -153,6 +159,9 @@ class DevicePrefetcher:
 
 def run_train(config, resume_from=-1, max_steps=None, rank=0, world_size=1, log=print):
     """train_q_network.py:84-250."""
+    aug_pad, aug_flip = getattr(config, "AUG_SHIFT_PAD", 0), getattr(config, "AUG_FLIP", False)
+    aug_actions = getattr(config, "AUG_FLIP_ACTIONS", [1, 2])
+    check_augment(aug_pad, aug_flip, aug_actions)
     per = bool(getattr(config, "PRIORITIZED_REPLAY", False))
     if per:
         check_prioritized_replay(config, world_size)
@@ -268,6 +277,15 @@ def run_train(config, resume_from=-1, max_steps=None, rank=0, world_size=1, log=
                         allreduce=(comm.launch if comm else None), loss_kind=getattr(config, "LOSS_KIND", "l2"),
                         allreduce_loss=(comm.launch_loss if comm else None), allreduce_wait=(comm.wait_last if comm else None),
                         allreduce_errors=((lambda: comm.launch_errors(replay.err_all)) if comm and replay else None))
+    augmenter = None
+    if aug_pad > 0 or aug_flip:
+        from .augment import Augmenter
+        augmenter = Augmenter(B, model.engine.device, pad=aug_pad, flip=aug_flip, flip_actions=aug_actions, seed=int(config.SEED),
+                              rank=rank, world_size=world_size)
+        swap = aug_flip and model.engine.action_dim == 3  # (one action column: nothing to exchange)
+        log(f"augmentation: random shift of up to {aug_pad} pixels" + (", random left-right mirror" if aug_flip else "") +
+            (f" with actions {aug_actions[0]} <-> {aug_actions[1]} exchanged" if swap else "") +
+            ", one draw per sample and update, shared by s and s'")
     if world_size > 1 and config.ARCHITECTURE != "extra_capacity" and getattr(config, "SYNC_BN", True):
         model.engine.set_bn_sync(world_size)  # train-mode BatchNorm over the global batch, as the single-GPU reference sees it
     if replay is not None:
@@ -314,6 +332,7 @@ def run_train(config, resume_from=-1, max_steps=None, rank=0, world_size=1, log=
     stepper.sync_target()  # :208
     stepper.sample_number = sample_number
     stepper.replay = replay  # the run's PrioritizedSampler (PRIORITIZED_REPLAY), None otherwise: returned with the stepper
+    stepper.augmenter = augmenter  # the run's Augmenter (AUG_SHIFT_PAD / AUG_FLIP), None otherwise
     if replay is not None:
         iterator = store.prioritized_batches(replay, sample_number)
 
@@ -336,13 +355,18 @@ def run_train(config, resume_from=-1, max_steps=None, rank=0, world_size=1, log=
             model.set_train()  # :221 (flags only; the engine's BatchNorm is always in eval mode in extra_capacity)
             item = next(iterator)
             before, after, src_kind, act, rew, term, valid, gt = item[:8]
+            aug_params = None
+            if augmenter is not None:  # this update's draw and the mirrored samples' action labels: two launches, nothing read back
+                aug_params = augmenter.draw(sample_number)
+                if swap:
+                    act = augmenter.actions(act.contiguous())
             # the stepper performs the :215-216 target refresh itself (sample_number % TARGET_UPDATE_INTERVAL == 0)
             loss = stepper.step(before, after, src_kind, act, rew, term,
                                 valid if config.REMOVE_BEFORE_REWARD else None,
                                 gt if config.TRAIN_ON_GROUND_TRUTH else None,
                                 finish_allreduce=(comm.finish if comm else None),
                                 weights=(item[8] if replay is not None else None),
-                                td_error=(replay.err if replay is not None else None))
+                                td_error=(replay.err if replay is not None else None), augment=aug_params)
             if replay is not None:
                 replay.update()  # behind the loss launch (and, with N ranks, the error exchange that finish_allreduce joined)
             # every rank's `loss` is its share of the global mean (the TD kernel divides by the global batch): their SUM is the
