@@ -245,6 +245,28 @@ int vdqn_axpy(float* y, const float* x, float alpha, int64_t n, void* stream);
 int vdqn_adam(float* p, const float* g, float* m, float* v, int64_t n, int32_t step, double lr, double beta1,
               double beta2, double eps, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Gradient-norm clipping and AdamW on the device (video_dqn_amd/csrc/optim.hip): the clip coefficient goes from the norm kernels
+ * to the Adam launch through device memory, nothing is read back.  The reference itself trains with plain Adam(lr=1e-3)
+ * (train_q_network.py:124); these replace what a torch loop would add around it.
+ * ------------------------------------------------------------------------------------------------ */
+/* Bytes of the norm workspace for up to n_ranges (1..8) ranges; -1 outside that.  Host only. */
+int64_t vdqn_clip_workspace_bytes(int32_t n_ranges);
+/* torch.nn.utils.clip_grad_norm_, part 1: the f64 sum of squares of g[0, n) (any 4-byte aligned start, n >= 1) as per-block
+ * partials into slot `slot` (0..7) of the workspace (8-byte aligned).  Fixed order, no atomics: the grid depends on n alone and
+ * block b writes partial b, so the result is bit-identical run to run; the order is written out in optim.hip. */
+int vdqn_grad_sumsq(const float* g, int64_t n, void* workspace, int32_t slot, void* stream);
+/* torch.nn.utils.clip_grad_norm_, part 2: one block adds the partials of slots 0 .. n_ranges-1 (each written by a
+ * vdqn_grad_sumsq ordered in front of this launch) in index order in f64 and writes out[0] = norm = sqrt(sum),
+ * out[1] = coef = min(1, max_norm / (norm + 1e-6)), computed in f64 and rounded to f32 once.  max_norm > 0.  A non-finite norm
+ * is not special-cased (a NaN norm gives a NaN coef, as torch's does). */
+int vdqn_clip_finalize(const void* workspace, int32_t n_ranges, double max_norm, float* out, void* stream);
+/* torch.optim.AdamW step on gradients scaled by a device-side coefficient (the multiply clip_grad_norm_ does in place):
+ *   gs = g * coef[0] (coef == NULL: 1);  p = p * (1 - lr * weight_decay);  then vdqn_adam's update with gs for g.
+ * With coef[0] == 1 and weight_decay == 0 it writes vdqn_adam's bits.  g itself is left as it is. */
+int vdqn_adam_scaled(float* p, const float* g, float* m, float* v, int64_t n, int32_t step, double lr, double beta1,
+                     double beta2, double eps, double weight_decay, const float* coef, void* stream);
+
 /* torch.nn.BatchNorm2d in train mode over an NHWC conv output y[n_img][hw][c] (ARCHITECTURE='basic':
  * archs/HabitatDQNMultiAction.py:32-34,37-40 keeps the ResNet in train mode).  Images are sample-major, frame-minor;
  * image i belongs to statistic group (i / imgs_per_half) * num_frames + i % num_frames — one group per model call and

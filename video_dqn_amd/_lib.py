@@ -142,6 +142,10 @@ _SIGS = {
     "vdqn_aug_swap_actions": (C.c_int, [c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp]),
     "vdqn_pack_input_aug": (C.c_int, [c_vp, c_vp, c_i32, c_i32, c_vp, c_i32, c_i32, c_vp]),
     "vdqn_net_set_augment": (C.c_int, [c_vp, c_vp]),
+    "vdqn_clip_workspace_bytes": (c_i64, [c_i32]),
+    "vdqn_grad_sumsq": (C.c_int, [c_vp, c_i64, c_vp, c_i32, c_vp]),
+    "vdqn_clip_finalize": (C.c_int, [c_vp, c_i32, C.c_double, c_vp, c_vp]),
+    "vdqn_adam_scaled": (C.c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i32, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, c_vp, c_vp]),
 }
 COMM_UID_BYTES = 128
 EXPORTS = tuple(_SIGS)

@@ -292,13 +292,26 @@ class TDStepper:
     def __init__(self, net: NetEngine, batch: int, lr: float, gamma: float, clip_rect: bool, linear: bool = False,
                  remove_before_reward: bool = False, train_on_ground_truth: bool = False, value_learning: bool = False,
                  target_update_interval: int = 8000, betas=(0.9, 0.999), eps: float = 1e-8, world_size: int = 1,
-                 allreduce=None, loss_kind: str = "l2", allreduce_loss=None, allreduce_wait=None, allreduce_errors=None):
+                 allreduce=None, loss_kind: str = "l2", allreduce_loss=None, allreduce_wait=None, allreduce_errors=None,
+                 grad_clip_norm: float = 0.0, weight_decay: float = 0.0, lr_fn=None):
         net._need_gpu()
         self.net, self.B = net, batch
         self.lib = net.lib
         if 2 * batch > net.max_batch:
             raise _lib.VdqnError(f"TDStepper(batch={batch}) needs NetEngine(max_batch>={2 * batch})")
         self.lr, self.gamma, self.betas, self.eps = lr, gamma, betas, eps
+        # grad_clip_norm > 0 (torch.nn.utils.clip_grad_norm_): the f64 norm of the whole flat gradient and the clip coefficient are
+        # computed on the device (vdqn_grad_sumsq / vdqn_clip_finalize) and the coefficient reaches the Adam launch through device
+        # memory — `clip_out` = {norm, coef} of the last update, never read back for the update itself.  No Adam launch may run
+        # before that norm is known, so both early-Adam paths are off under clipping.  weight_decay: decoupled, as torch.optim.AdamW.
+        # lr_fn(t) (optim.lr_at): host arithmetic, evaluated once per update from `sample_number` and passed to every Adam launch
+        # of that update; `initial_lr` keeps the base rate for the checkpoint.  All three off: vdqn_adam, launched as ever.
+        if not (grad_clip_norm >= 0.0) or not (weight_decay >= 0.0) or weight_decay == float("inf"):
+            raise _lib.VdqnError("TDStepper: grad_clip_norm and weight_decay must be >= 0 (0 = off)")
+        self.grad_clip_norm, self.weight_decay, self.lr_fn = float(grad_clip_norm), float(weight_decay), lr_fn
+        self.initial_lr = lr
+        self.clip_ws = self.clip_out = None
+        self._clip_slots = 0  # norm partials of this update already queued by forward_backward (one slot per stage)
         self.clip_rect, self.linear, self.rbr = clip_rect, linear, remove_before_reward
         self.gtb, self.value_learning = train_on_ground_truth, value_learning
         if loss_kind not in LOSS_KINDS:
@@ -337,12 +350,18 @@ class TDStepper:
             self.loss = torch.zeros(1, dtype=torch.float32, device=dev)
             self.q_before = torch.zeros((batch, net.num_classes * net.action_dim), dtype=torch.float32, device=dev)
             self._ones = torch.ones((batch, net.num_classes), dtype=torch.float32, device=dev)
+            if self.grad_clip_norm > 0:
+                self.clip_ws = torch.zeros(self.lib.vdqn_clip_workspace_bytes(3) // 8, dtype=torch.float64, device=dev)
+                self.clip_out = torch.zeros(2, dtype=torch.float32, device=dev)
         self.adam_step = 0
         self.sample_number = 0
         self._grad_stream = None  # torch view of the engine's side stream (vdqn_net_grad_stream)
         self._adam_done = []
         self._packed_bufs, self._ahead = [None, None], None
         self.stage_ranges = [net.stage_range(s) for s in range(3)]
+        # the three stage ranges tile [0, trainable_numel) (in whatever order): a norm taken stage by stage covers every element once
+        r = sorted(self.stage_ranges)
+        self._stages_tile = r[0][0] == 0 and r[-1][1] == nt and all(e > b for b, e in r) and all(r[i][1] == r[i + 1][0] for i in range(2))
         self.sync_target()
 
     def sync_target(self):
@@ -430,6 +449,7 @@ class TDStepper:
         the packed copies); `optimizer_step` then only covers what is left.  Same arithmetic, same results."""
         n = self.net
         self._adam_done = []
+        self._clip_slots = 0
         keep = (before, after, act, rew, term, valid, gt)  # keep inputs alive until the launches are queued
         with torch.cuda.device(n.device):
             a = self._args(before, after, src_kind, act, rew, term, valid if valid is not None else self._ones, gt)
@@ -470,7 +490,8 @@ class TDStepper:
                         if stage == 2 and err_ready is not None:
                             torch.cuda.current_stream().wait_event(err_ready)
                             self.allreduce_errors()
-                    if _DIST_EARLY_ADAM and stage < 2 and self.allreduce_wait is not None and n.extra_capacity and self._dist_early_ok():
+                    if _DIST_EARLY_ADAM and stage < 2 and self.allreduce_wait is not None and n.extra_capacity and self.grad_clip_norm == 0 \
+                            and self._dist_early_ok():
                         b4, e4 = (b + 3) // 4 * 4, e // 4 * 4
                         if e4 > b4:
                             if self._post_stream is None:
@@ -485,7 +506,16 @@ class TDStepper:
                             if _DIST_EARLY_ADAM_MODE != "3":
                                 self._adam_done.append((b4, e4))
                             self._post_used = True
-                elif early_adam and stage < 2:
+                elif self.grad_clip_norm > 0 and self._stages_tile:
+                    # single process: this stage's share of the norm right behind its gradient unpack, under the rest of the backward
+                    # pass (stage 2's unpack has been joined back into `st`); finalise and Adam follow the last stage (optimizer_step).
+                    # Under an exchange the norm is that of the REDUCED gradient, taken in optimizer_step behind `finish_allreduce`
+                    b, e = self.stage_ranges[stage]
+                    with (self._grad_stream_ctx() if stage < 2 else contextlib.nullcontext()):
+                        _lib.check(self.lib.vdqn_grad_sumsq(self.grads.data_ptr() + 4 * b, e - b, self.clip_ws.data_ptr(), stage, _stream()),
+                                   "vdqn_grad_sumsq")
+                    self._clip_slots = stage + 1
+                elif early_adam and stage < 2 and self.grad_clip_norm == 0:
                     b, e = self.stage_ranges[stage]
                     b, e = (b + 3) // 4 * 4, e // 4 * 4  # vdqn_adam wants 16-byte aligned ranges; the rest is left to optimizer_step
                     if e > b:
@@ -505,6 +535,12 @@ class TDStepper:
     def _adam_range(self, b: int, e: int, step: int):
         """Adam (train_q_network.py:227) over the flat element range [b, e) on the current stream."""
         n = self.net
+        if self.grad_clip_norm > 0 or self.weight_decay != 0:
+            coef = self.clip_out.data_ptr() + 4 if self.grad_clip_norm > 0 else None
+            _lib.check(self.lib.vdqn_adam_scaled(n.params.data_ptr() + 4 * b, self.grads.data_ptr() + 4 * b, self.exp_avg.data_ptr() + 4 * b,
+                                                 self.exp_avg_sq.data_ptr() + 4 * b, e - b, step, self.lr, self.betas[0], self.betas[1],
+                                                 self.eps, self.weight_decay, coef, _stream()), "vdqn_adam_scaled")
+            return
         _lib.check(self.lib.vdqn_adam(n.params.data_ptr() + 4 * b, self.grads.data_ptr() + 4 * b, self.exp_avg.data_ptr() + 4 * b,
                                       self.exp_avg_sq.data_ptr() + 4 * b, e - b, step, self.lr, self.betas[0], self.betas[1],
                                       self.eps, _stream()), "vdqn_adam")
@@ -518,6 +554,14 @@ class TDStepper:
             if self._post_used:  # per-bucket updates under an exchange ran on their own stream: join it
                 torch.cuda.current_stream().wait_stream(self._post_stream)
                 self._post_used = False
+            if self.grad_clip_norm > 0:
+                slots, self._clip_slots = self._clip_slots, 0
+                if slots != 3:  # an exchange (or a caller's own gradient): the whole range as it stands on this stream, one slot
+                    _lib.check(self.lib.vdqn_grad_sumsq(self.grads.data_ptr(), n.trainable_numel, self.clip_ws.data_ptr(), 0, _stream()),
+                               "vdqn_grad_sumsq")
+                    slots = 1
+                _lib.check(self.lib.vdqn_clip_finalize(self.clip_ws.data_ptr(), slots, self.grad_clip_norm, self.clip_out.data_ptr(), _stream()),
+                           "vdqn_clip_finalize")
             pos = 0  # everything of [0, trainable_numel) that `forward_backward(early_adam=True)` has not updated already
             for b, e in done + [(n.trainable_numel, n.trainable_numel)]:
                 if b > pos:
@@ -578,11 +622,14 @@ class TDStepper:
         self.sample_number += 1
         if self.sample_number % self.tui == 0:
             self.sync_target()
+        if self.lr_fn is not None:
+            self.lr = float(self.lr_fn(self.sample_number))
         # (single process only: behind each RCCL bucket on a stream of its own it measured 7.22 vs 5.96 ms per update with one rank,
         # profiles/r03s_ab_rccl_early_adam.txt — with an exchange the whole optimiser update stays behind `finish_allreduce`)
-        early = _EARLY_ADAM and self.net.extra_capacity and self.allreduce is None and finish_allreduce is None
+        early = _EARLY_ADAM and self.net.extra_capacity and self.allreduce is None and finish_allreduce is None and self.grad_clip_norm == 0
         self.forward_backward(before, after, src_kind, act, rew, term, valid, gt, early_adam=early, next_frames=next_frames)
         if finish_allreduce is not None:
             finish_allreduce()
+            self._clip_slots = 0  # the gradient has just been reduced: its norm is taken from what `grads` holds now
         self.optimizer_step()
         return self.loss

@@ -207,6 +207,35 @@ def adam(p, g, m, v, step, lr, beta1=0.9, beta2=0.999, eps=1e-8):
     _lib.check(lib.vdqn_adam(_ptr(p), _ptr(g), _ptr(m), _ptr(v), p.numel(), step, lr, beta1, beta2, eps, _stream()), "vdqn_adam")
 
 
+def clip_workspace(device, n_ranges: int = 1) -> torch.Tensor:
+    """The norm workspace for up to n_ranges (1..8) ranges: slot s = int64 count + 512 f64 partials (csrc/optim.hip)."""
+    nbytes = _lib.load().vdqn_clip_workspace_bytes(n_ranges)
+    if nbytes < 0:
+        raise _lib.VdqnError(f"clip_workspace: n_ranges {n_ranges} (1..8)")
+    return torch.zeros(nbytes // 8, dtype=torch.float64, device=device)
+
+
+def grad_sumsq(g: torch.Tensor, workspace: torch.Tensor, slot: int = 0) -> None:
+    """f64 sum of squares of the contiguous f32 range g (any 4-byte aligned start) as per-block partials into `slot` of the workspace."""
+    _lib.check(_lib.load().vdqn_grad_sumsq(_ptr(g), g.numel(), _ptr(workspace), slot, _stream()), "vdqn_grad_sumsq")
+
+
+def clip_finalize(workspace: torch.Tensor, n_ranges: int, max_norm: float, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """-> f32 [2] on the device: {global L2 norm over slots 0 .. n_ranges-1, min(1, max_norm / (norm + 1e-6))}
+    (torch.nn.utils.clip_grad_norm_); nothing is read back."""
+    if out is None:
+        out = torch.zeros(2, dtype=torch.float32, device=workspace.device)
+    _lib.check(_lib.load().vdqn_clip_finalize(_ptr(workspace), n_ranges, max_norm, _ptr(out), _stream()), "vdqn_clip_finalize")
+    return out
+
+
+def adam_scaled(p, g, m, v, step, lr, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.0, coef: Optional[torch.Tensor] = None):
+    """torch.optim.AdamW on g * coef[0] (coef: f32 device tensor, e.g. clip_finalize(..)[1:]; None = 1)."""
+    lib = _lib.load()
+    _lib.check(lib.vdqn_adam_scaled(_ptr(p), _ptr(g), _ptr(m), _ptr(v), p.numel(), step, lr, beta1, beta2, eps, weight_decay, _ptr(coef),
+                                    _stream()), "vdqn_adam_scaled")
+
+
 def bn_train_fwd(y: torch.Tensor, gamma, beta, running_mean=None, running_var=None, *, resid=None, relu=False,
                  num_frames=1, imgs_per_half=None, momentum=0.1, eps=1e-5, deterministic=False):
     """Train-mode BatchNorm2d over NHWC y [n, h, w, c] (statistic groups: see include/vdqn.h).

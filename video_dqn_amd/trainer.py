@@ -21,6 +21,7 @@ from .dataset import QLearningRealDataset, SyntheticTupleDataset
 from .dist import BucketAllReduce, agree_all, broadcast_replica_state
 from .engine import TDStepper
 from .model import build_model
+from .optim import lr_at, schedule_active
 from .shards import ShardDataset, is_shard_dir
 
 
@@ -54,8 +55,13 @@ def optimizer_state_dict(stepper: TDStepper) -> dict:
                                  "exp_avg": stepper.exp_avg[sl].view(s.shape).clone(),
                                  "exp_avg_sq": stepper.exp_avg_sq[sl].view(s.shape).clone()}
     n_params = sum(1 for s in net.slots.values() if s.kind in (0, 1))
-    group = {"lr": stepper.lr, "betas": tuple(stepper.betas), "eps": stepper.eps, "weight_decay": 0, "amsgrad": False,
-             "params": list(range(n_params))}
+    # (GRAD_CLIP_NORM / WEIGHT_DECAY / LR_*: `lr` is the rate of the last update, `weight_decay` the AdamW factor, and `initial_lr`
+    # — the key torch's schedulers add — is there only while a schedule is active: a default-config checkpoint keeps its exact keys)
+    group = {"lr": stepper.lr, "betas": tuple(stepper.betas), "eps": stepper.eps, "weight_decay": getattr(stepper, "weight_decay", 0) or 0,
+             "amsgrad": False}
+    if getattr(stepper, "lr_fn", None) is not None:
+        group["initial_lr"] = stepper.initial_lr
+    group["params"] = list(range(n_params))
     return {"state": dict(sorted(state.items())), "param_groups": [group]}
 
 
@@ -107,6 +113,14 @@ def check_augment(pad, flip, flip_actions) -> None:
     """AUG_SHIFT_PAD / AUG_FLIP / AUG_FLIP_ACTIONS: raise ValueError naming the key (before any device work)."""
     from .augment import check_config
     check_config(pad, flip, flip_actions)
+
+
+def check_optim(config) -> None:
+    """GRAD_CLIP_NORM / WEIGHT_DECAY / LR_WARMUP_STEPS / LR_SCHEDULE / LR_FINAL_FRACTION: raise ValueError naming the key (before any
+    device work)."""
+    from .optim import check_config
+    check_config(getattr(config, "GRAD_CLIP_NORM", 0.0), getattr(config, "WEIGHT_DECAY", 0.0), getattr(config, "LR_WARMUP_STEPS", 0),
+                 getattr(config, "LR_SCHEDULE", "constant"), getattr(config, "LR_FINAL_FRACTION", 0.0), int(config.NUM_STEPS))
 
 
 def _to_device_batch(batch, device, num_classes=5):
@@ -162,6 +176,14 @@ def run_train(config, resume_from=-1, max_steps=None, rank=0, world_size=1, log=
     aug_pad, aug_flip = getattr(config, "AUG_SHIFT_PAD", 0), getattr(config, "AUG_FLIP", False)
     aug_actions = getattr(config, "AUG_FLIP_ACTIONS", [1, 2])
     check_augment(aug_pad, aug_flip, aug_actions)
+    check_optim(config)
+    clip_norm, weight_decay = float(getattr(config, "GRAD_CLIP_NORM", 0.0)), float(getattr(config, "WEIGHT_DECAY", 0.0))
+    lr_fn = None
+    if schedule_active(getattr(config, "LR_WARMUP_STEPS", 0), getattr(config, "LR_SCHEDULE", "constant")):
+        lr_args = (float(config.LEARNING_RATE), int(config.LR_WARMUP_STEPS), config.LR_SCHEDULE, float(config.LR_FINAL_FRACTION), int(config.NUM_STEPS))
+
+        def lr_fn(t):  # host arithmetic on the update number alone: a resumed run uses the uninterrupted run's rates
+            return lr_at(t, *lr_args)
     per = bool(getattr(config, "PRIORITIZED_REPLAY", False))
     if per:
         check_prioritized_replay(config, world_size)
@@ -276,7 +298,13 @@ def run_train(config, resume_from=-1, max_steps=None, rank=0, world_size=1, log=
                         target_update_interval=config.TARGET_UPDATE_INTERVAL, world_size=world_size,
                         allreduce=(comm.launch if comm else None), loss_kind=getattr(config, "LOSS_KIND", "l2"),
                         allreduce_loss=(comm.launch_loss if comm else None), allreduce_wait=(comm.wait_last if comm else None),
-                        allreduce_errors=((lambda: comm.launch_errors(replay.err_all)) if comm and replay else None))
+                        allreduce_errors=((lambda: comm.launch_errors(replay.err_all)) if comm and replay else None),
+                        grad_clip_norm=clip_norm, weight_decay=weight_decay, lr_fn=lr_fn)
+    if clip_norm > 0 or weight_decay > 0 or lr_fn is not None:
+        log("optimiser:" + (f" gradient clipped to a global norm of {clip_norm:g}" if clip_norm > 0 else "") +
+            (f" decoupled weight decay {weight_decay:g}" if weight_decay > 0 else "") +
+            (f" learning rate {config.LR_SCHEDULE} to {float(config.LR_FINAL_FRACTION):g} x LEARNING_RATE at {int(config.NUM_STEPS)}, "
+             f"{int(config.LR_WARMUP_STEPS)} warm-up updates" if lr_fn is not None else ""))
     augmenter = None
     if aug_pad > 0 or aug_flip:
         from .augment import Augmenter
@@ -339,6 +367,9 @@ def run_train(config, resume_from=-1, max_steps=None, rank=0, world_size=1, log=
     running_loss = None
     host_loss = torch.zeros(2, dtype=torch.float32).pin_memory()
     pending = None  # (slot, event) of the previous step's loss copy
+    # GRAD_CLIP_NORM: the gradient norm is read back the same way (pinned, two slots, one update late) for the `grad_norm/train` scalar
+    host_norm = torch.zeros(2, dtype=torch.float32).pin_memory() if clip_norm > 0 else None
+    pending_norm, grad_norm = None, None
     loss_stream = None  # N > 1: where the all-reduced loss is waited for and copied to the host
     num_steps = config.NUM_STEPS if max_steps is None else min(config.NUM_STEPS, sample_number + max_steps)
 
@@ -348,6 +379,10 @@ def run_train(config, resume_from=-1, max_steps=None, rank=0, world_size=1, log=
         ev.synchronize()
         v = float(host_loss[slot])
         running_loss = v if running_loss is None else running_loss * 0.99 + v * 0.01  # :228-231
+
+    def consume_norm(p):
+        p[1].synchronize()
+        return float(host_norm[p[0]])
 
     try:  # (the streaming input path owns a thread, pinned buffers and a prefetch stream: released on every exit)
         while sample_number < num_steps:
@@ -392,6 +427,13 @@ def run_train(config, resume_from=-1, max_steps=None, rank=0, world_size=1, log=
             if pending is not None:
                 consume(pending)
             pending = (slot, ev)
+            if host_norm is not None:
+                host_norm[slot:slot + 1].copy_(stepper.clip_out[:1], non_blocking=True)
+                ev_n = torch.cuda.Event()
+                ev_n.record()
+                if pending_norm is not None:  # the previous update's: complete long ago, the GPU is busy with this one
+                    grad_norm = (sample_number - 1, consume_norm(pending_norm))
+                pending_norm = (slot, ev_n)
             log_now = sample_number % 100 == 0 and rank == 0 and hasattr(config, "writer")
             if log_now:  # the reference logs the average INCLUDING this update's loss (:228-238): take it in before writing
                 consume(pending)
@@ -400,6 +442,8 @@ def run_train(config, resume_from=-1, max_steps=None, rank=0, world_size=1, log=
                 print(f"\rbatch:{sample_number}/{config.NUM_STEPS} avg_loss: {running_loss}", end="")
             if log_now and running_loss is not None:
                 config.writer.add_scalar("avg_q_loss/train", running_loss, sample_number)  # :236-238
+            if log_now and grad_norm is not None:  # the norm BEFORE clipping, as clip_grad_norm_ returns it; non-finite values show here
+                config.writer.add_scalar("grad_norm/train", grad_norm[1], grad_norm[0])  # (the update it was measured at: one late)
             if log_now and replay is not None:
                 config.writer.add_scalar("per/beta", replay.beta(sample_number), sample_number)  # (host arithmetic: nothing read back)
             if sample_number % config.CHECKPOINT_INTERVAL == 0 and rank == 0:  # :241-247
