@@ -430,6 +430,13 @@ typedef struct vdqn_step_args {
   int32_t acts_samples;       /* 0: `acts_online` is laid out as vdqn_net_td_forward leaves it (2B samples, B on the
                                  ground-truth branch).  > 0: `acts_online` is the workspace of ONE vdqn_net_forward call over that
                                  many samples (== batch) — the backward of a single model call, vdqn_net_backward_begin below. */
+  const float* sample_weight; /* optional [batch] importance weights (prioritized replay): vdqn_net_td_forward launches
+                                 vdqn_td_loss_weighted with them instead of vdqn_td_loss (TD branch only: the ground-truth branch
+                                 then fails).  NULL: the reference loss. */
+  float* sample_err;          /* optional [batch] per-sample error output of that launch; must be NULL when sample_weight is */
+  const int32_t* aug_params;  /* optional device int32 [batch][4], 16-byte aligned: vdqn_net_td_forward packs `before` and `after`
+                                 with vdqn_pack_input_aug (the same params for both) where it calls vdqn_pack_input otherwise; it
+                                 then fails for src_kind != 0 and for packed_frames.  NULL: the plain pack. */
 } vdqn_step_args;
 int vdqn_net_td_forward(vdqn_net* net, const vdqn_step_args* a, void* stream);
 /* Stage s of the backward pass (0: head + layer4, 1: layer3, 2: layer2, layer1, stem).  With the overlap on, the stage's weight
@@ -450,10 +457,6 @@ int vdqn_net_backward_begin(vdqn_net* net, const vdqn_step_args* a, const float*
 /* The HIP stream (hipStream_t) on which a stage's gradients become complete; NULL when the overlap is off (then it is the
  * stream passed to vdqn_net_backward_stage). */
 void* vdqn_net_grad_stream(vdqn_net* net);
-/* While set (weight != NULL), vdqn_net_td_forward launches vdqn_td_loss_weighted with these [batch] weights and per-sample
- * error output instead of vdqn_td_loss (TD branch only: the ground-truth branch then fails).  NULL, NULL restores the reference
- * loss.  The pointers are read at every vdqn_net_td_forward call until they are changed. */
-int vdqn_net_set_sample_weights(vdqn_net* net, const float* weight, float* err_out);
 
 /* ------------------------------------------------------------------------------------------------
  * Prioritized experience replay (Schaul et al., ICLR 2016), sampled and updated on the device: no host round trip.
@@ -498,11 +501,6 @@ int vdqn_aug_swap_actions(const int64_t* act, const int32_t* params, int32_t n, 
  * src, dst and params 16-byte aligned.  All-zero params give vdqn_pack_input's output. */
 int vdqn_pack_input_aug(const void* src, void* dst, int32_t n_img, int32_t frames_per_sample, const int32_t* params,
                         int32_t n_params, int32_t dtype, void* stream);
-/* While set (params != NULL: device int32 [batch][4]), vdqn_net_td_forward packs `before` and `after` with vdqn_pack_input_aug
- * (the same params for both) where it calls vdqn_pack_input otherwise; it then fails for src_kind != 0 and for
- * vdqn_step_args.packed_frames.  NULL restores the plain pack.  The pointer is read at every vdqn_net_td_forward call until it is
- * changed. */
-int vdqn_net_set_augment(vdqn_net* net, const int32_t* params);
 
 /* ------------------------------------------------------------------------------------------------
  * Data-parallel exchange: one process per GPU, the flat f32 gradient SUM-all-reduced over RCCL (xGMI)

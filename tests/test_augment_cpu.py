@@ -183,5 +183,5 @@ def test_c_entries_refuse_bad_arguments():
                dict(dtype=7)):
         assert pack(**kw) != 0, kw
         assert b"vdqn_pack_input_aug" in lib.vdqn_last_error()
-    assert lib.vdqn_net_set_augment(None, p) != 0
-    assert lib.vdqn_abi_version() == 15
+    assert lib.vdqn_net_td_forward(None, C.byref(_lib.StepArgs()), None) != 0  # (null net: refused before anything is read)
+    assert lib.vdqn_abi_version() == 16

@@ -188,14 +188,14 @@ def test_hook_refuses_f32_frames_and_packed_frames():
         stp.step(*f32, augment=params)
     fb, fa, act, rew, term = _u8_batch(503, B)
     before, after = torch.from_numpy(fb).to(DEV), torch.from_numpy(fa).to(DEV)
-    a = stp._args(before, after, 0, torch.from_numpy(act).to(DEV), rew.to(DEV), term.to(DEV), stp._ones, None)
+    a = stp._args(before, after, 0, torch.from_numpy(act).to(DEV), rew.to(DEV), term.to(DEV), stp._ones, None, augment=params)
     a.packed_frames = stp._packed_buffer(0).data_ptr()
-    _lib.check(lib.vdqn_net_set_augment(net.handle, params.data_ptr()), "vdqn_net_set_augment")
-    try:
-        assert lib.vdqn_net_td_forward(net.handle, C.byref(a), _st()) != 0
-        assert b"packed_frames" in lib.vdqn_last_error()
-    finally:
-        _lib.check(lib.vdqn_net_set_augment(net.handle, None), "vdqn_net_set_augment")
+    assert lib.vdqn_net_td_forward(net.handle, C.byref(a), _st()) != 0
+    assert b"packed_frames" in lib.vdqn_last_error()
+    a.packed_frames = None
+    a.aug_params = params.data_ptr() + 4  # not 16-byte aligned: refused before any launch (nothing ever reads the address)
+    assert lib.vdqn_net_td_forward(net.handle, C.byref(a), _st()) != 0
+    assert b"aug_params" in lib.vdqn_last_error() and b"aligned" in lib.vdqn_last_error()
     torch.cuda.synchronize()
     for bad in (params[:2], params.to(torch.int64), params.cpu()):
         with pytest.raises(_lib.VdqnError, match="augment must be"):

@@ -605,6 +605,58 @@ def test_deterministic_mode_is_bit_identical_run_to_run(dtype, B):
     assert abs(a[2][0] - c[2][0]) <= 1e-6 * abs(c[2][0])
 
 
+def test_an_update_is_described_by_its_step_args_alone():
+    """Two steppers on ONE NetEngine (f32, deterministic, F = 1; A at B = 4, B at B = 2): what an update computes comes from the
+    vdqn_step_args it is given, never from what another update left on the net.
+    1. Raw ABI: vdqn_net_td_forward(A), vdqn_net_td_forward(B), then stages 0..2 of A.  Every weight gradient of A's stages takes
+       its deterministic workspace from the layout of A's own batch (4).  Were that batch remembered on the net by the last
+       vdqn_net_td_forward instead, A's stages would use the workspace offset and size of B's layout (batch 2) inside A's `bwd`:
+       an offset that lies inside A's gradient tensors, or a size the two-stage kernel refuses.  A's gradient equals, bit for bit,
+       that of a twin engine and stepper that ran the same batch alone.
+    2. A is stepped with sample weights, an error output and augmentation; B's plain step behind it on the same net equals a
+       plain twin's bit for bit (nothing of A's options outlives A's update)."""
+    import ctypes as C
+    from video_dqn_amd import _lib
+    from video_dqn_amd.engine import NetEngine, TDStepper, _stream
+
+    def batch(seed, B):
+        (tup, raw) = synth.make_batch(seed, B, 1, structured=True, reward_p=0.3)
+        return (torch.from_numpy(raw[0]).to(DEV), torch.from_numpy(raw[1]).to(DEV), 0, tup[2].to(DEV), tup[3].float().to(DEV), tup[4].float().to(DEV))
+
+    nets = [make_engine("f32", max_batch=8, deterministic=True) for _ in range(2)]
+    (net, twin) = nets
+    stp_a, stp_b, twin_a, twin_b = [TDStepper(n, B, lr=1e-4, gamma=0.99, clip_rect=True) for n in nets for B in (4, 2)]
+    args_a, args_b = batch(901, 4), batch(902, 2)
+
+    lib = net.lib
+    a = stp_a._args(*args_a, stp_a._ones, None)
+    b = stp_b._args(*args_b, stp_b._ones, None)
+    _lib.check(lib.vdqn_net_td_forward(net.handle, C.byref(a), _stream()), "vdqn_net_td_forward")
+    _lib.check(lib.vdqn_net_td_forward(net.handle, C.byref(b), _stream()), "vdqn_net_td_forward")
+    for stage in range(3):
+        _lib.check(lib.vdqn_net_backward_stage(net.handle, C.byref(a), stage, _stream()), "vdqn_net_backward_stage")
+    twin_a.forward_backward(*args_a)
+    torch.cuda.synchronize()
+    assert twin_a.grads.abs().sum().item() > 0
+    assert torch.equal(stp_a.loss, twin_a.loss)
+    assert torch.equal(stp_a.grads, twin_a.grads)
+
+    weights = torch.linspace(0.25, 1.0, 4, device=DEV)
+    td_error = torch.zeros(4, device=DEV)
+    augment = torch.tensor([(8, -5, 1, 0), (0, 0, 0, 0), (-3, 2, 0, 0), (0, 6, 1, 0)], dtype=torch.int32, device=DEV)
+    stp_a.step(*args_a, weights=weights, td_error=td_error, augment=augment)
+    torch.cuda.synchronize()
+    assert td_error.abs().sum().item() > 0 and not torch.equal(stp_a.grads, twin_a.grads)  # both options reached A's update
+    twin.params.copy_(net.params)  # (A's optimiser step moved the shared parameters: the twin starts B's update from the same ones)
+    twin.mark_dirty()
+    stp_b.step(*args_b)
+    twin_b.step(*args_b)
+    torch.cuda.synchronize()
+    for name in ("loss", "q_before", "grads"):
+        assert torch.equal(getattr(stp_b, name), getattr(twin_b, name)), name
+    assert torch.equal(net.params, twin.params)
+
+
 def test_update_replays_bit_identically_as_a_hip_graph():
     """One update is kernels, stream waits and event records only — no host synchronisation, no allocation inside the library — so
     it can be captured into a hipGraph through the caller's stream (the engine's side streams join the capture through the fork /

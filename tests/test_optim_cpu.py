@@ -135,7 +135,7 @@ def test_library_exports_the_optimiser_symbols_at_abi_15():
         assert hasattr(lib, name), name
         assert name in _lib.EXPORTS
     loaded = _lib.load()
-    assert loaded.vdqn_abi_version() == 15 == _lib.ABI_VERSION
+    assert loaded.vdqn_abi_version() == 16 == _lib.ABI_VERSION
     assert loaded.vdqn_clip_workspace_bytes(1) == optim_oracle.CLIP_SLOT_DOUBLES * 8
     assert loaded.vdqn_clip_workspace_bytes(3) == 3 * optim_oracle.CLIP_SLOT_DOUBLES * 8
     assert loaded.vdqn_clip_workspace_bytes(0) == -1 and loaded.vdqn_clip_workspace_bytes(9) == -1

@@ -16,7 +16,7 @@ def test_f32x3_constant_matches_header():
     m = re.search(r"#define\s+VDQN_F32X3\s+(\d+)", hdr)
     assert m is not None, "VDQN_F32X3 missing from include/vdqn.h"
     assert int(m.group(1)) == _lib.VDQN_F32X3 == 2
-    assert _lib.load().vdqn_abi_version() == _lib.ABI_VERSION == 15
+    assert _lib.load().vdqn_abi_version() == _lib.ABI_VERSION == 16
 
 
 @pytest.mark.parametrize("extra_capacity,frames", [(True, 1), (True, 4), (False, 4)])

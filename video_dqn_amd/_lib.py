@@ -12,7 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", f"libvdqn{'_' + os.environ['VDQN_LIB'] if os.environ.get('VDQN_LIB') else ''}.so")
 
 VDQN_F32, VDQN_BF16, VDQN_F32X3 = 0, 1, 2
-ABI_VERSION = 15
+ABI_VERSION = 16
 
 c_i32, c_i64, c_f32, c_vp = C.c_int32, C.c_int64, C.c_float, C.c_void_p
 
@@ -68,7 +68,8 @@ class StepArgs(C.Structure):
                 ("clip_rect", c_i32), ("linear", c_i32), ("use_valid", c_i32), ("train_on_ground_truth", c_i32),
                 ("value_learning", c_i32),
                 ("acts_online", c_vp), ("acts_target", c_vp), ("bwd", c_vp), ("grads", c_vp), ("loss", c_vp),
-                ("q_before", c_vp), ("loss_kind", c_i32), ("packed_frames", c_vp), ("acts_samples", c_i32)]
+                ("q_before", c_vp), ("loss_kind", c_i32), ("packed_frames", c_vp), ("acts_samples", c_i32),
+                ("sample_weight", c_vp), ("sample_err", c_vp), ("aug_params", c_vp)]
 
 
 ALLREDUCE_FN = C.CFUNCTYPE(None, c_vp, c_vp, c_i64, c_vp)  # vdqn_allreduce_fn(user, buf, count, stream)
@@ -134,14 +135,12 @@ _SIGS = {
     "vdqn_comm_destroy": (C.c_int, [c_vp]),
     "vdqn_host_gather": (C.c_int, [c_vp, c_vp, c_i64, c_i64, c_i32]),
     "vdqn_td_loss_weighted": (C.c_int, [C.POINTER(TdArgs), c_vp, c_vp, c_vp]),
-    "vdqn_net_set_sample_weights": (C.c_int, [c_vp, c_vp, c_vp]),
     "vdqn_per_workspace_bytes": (c_i64, [c_i64]),
     "vdqn_per_sample": (C.c_int, [c_vp, c_i64, c_i32, C.c_uint64, C.c_uint64, C.c_double, c_vp, c_vp, c_vp, c_vp]),
     "vdqn_per_update": (C.c_int, [c_vp, c_i64, c_vp, c_vp, c_i32, C.c_double, c_vp]),
     "vdqn_aug_draw": (C.c_int, [C.c_uint64, C.c_uint64, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp]),
     "vdqn_aug_swap_actions": (C.c_int, [c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp]),
     "vdqn_pack_input_aug": (C.c_int, [c_vp, c_vp, c_i32, c_i32, c_vp, c_i32, c_i32, c_vp]),
-    "vdqn_net_set_augment": (C.c_int, [c_vp, c_vp]),
     "vdqn_clip_workspace_bytes": (c_i64, [c_i32]),
     "vdqn_grad_sumsq": (C.c_int, [c_vp, c_i64, c_vp, c_i32, c_vp]),
     "vdqn_clip_finalize": (C.c_int, [c_vp, c_i32, C.c_double, c_vp, c_vp]),

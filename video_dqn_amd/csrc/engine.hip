@@ -29,7 +29,7 @@ void vdqn_set_error(const char* fmt, ...) {
   va_end(ap);
 }
 extern "C" const char* vdqn_last_error(void) { return g_err; }
-extern "C" int vdqn_abi_version(void) { return 15; }
+extern "C" int vdqn_abi_version(void) { return 16; }
 extern "C" int32_t vdqn_abi_struct_size(int32_t which) {
   switch (which) {
     case 0: return (int32_t)sizeof(vdqn_conv_args);
@@ -129,10 +129,6 @@ struct vdqn_net {
   BnSync bn_sync = {nullptr, nullptr, nullptr, 1};  // SyncBN hook ('basic' under data parallelism)
   int wgrad_rr = 0;                                  // VDQN_WGRAD_STREAMS=2: which side stream took the last weight gradient
   int overlap = 1;
-  int bwd_samples = 0;  // batch of the update in flight (set by vdqn_net_td_forward; sizes the bwd workspace layout)
-  const float* sample_w = nullptr;  // vdqn_net_set_sample_weights: [B] importance weights of the TD loss (NULL: the reference loss)
-  float* sample_err = nullptr;      // ... and where that launch writes the [B] per-sample TD errors (may be NULL)
-  const int32_t* aug = nullptr;     // vdqn_net_set_augment: int32 [B][4] shift / mirror of each sample (NULL: the plain pack)
   hipStream_t side = nullptr;
   hipStream_t side2 = nullptr;  // the second half of the online forward pass
   std::vector<hipEvent_t> events;
@@ -985,15 +981,14 @@ int run_dgrad(const vdqn_net* net, const Layer& L, const unsigned char* packed, 
   return vdqn_conv2d(&a, st);
 }
 
-int run_wgrad(const vdqn_net* net, const Layer& L, unsigned char* bwd, const void* gy, const void* x, int n_units, hipStream_t st,
-              bool colsum_kernel = false) {
+int run_wgrad(const vdqn_net* net, const Layer& L, unsigned char* bwd, const BwdLayout& W, const void* gy, const void* x, int n_units,
+              hipStream_t st, bool colsum_kernel = false) {
   vdqn_wgrad_args a = wgrad_shape_args(net, L, n_units);
   a.gy = gy;
   a.x = x;
   a.dw = reinterpret_cast<float*>(bwd + L.dw_off);
   a.dbias = colsum_kernel ? reinterpret_cast<float*>(bwd + L.db_off) : nullptr;  // else: dgrad-epilogue partials
   if (net->cfg.deterministic || wgrad_two_stage()) {  // all weight gradients of an update run on ONE stream, so they can share the workspace
-    const BwdLayout W = bwd_layout(net, net->bwd_samples);
     a.workspace = bwd + W.det_ws;
     a.workspace_bytes = W.det_ws_bytes;
   }
@@ -1165,21 +1160,6 @@ extern "C" int vdqn_net_set_bn_sync(vdqn_net* net, vdqn_allreduce_fn fn, void* u
   net->bn_sync.fn = (fn && world_size > 1) ? fn : nullptr;
   net->bn_sync.user = user;
   net->bn_sync.world = world_size > 1 ? world_size : 1;
-  return VDQN_OK;
-}
-
-extern "C" int vdqn_net_set_sample_weights(vdqn_net* net, const float* weight, float* err_out) {
-  VDQN_CHECK(net, "vdqn_net_set_sample_weights: null net");
-  VDQN_CHECK(weight || !err_out, "vdqn_net_set_sample_weights: err_out without weights");
-  net->sample_w = weight;
-  net->sample_err = weight ? err_out : nullptr;
-  return VDQN_OK;
-}
-
-extern "C" int vdqn_net_set_augment(vdqn_net* net, const int32_t* params) {
-  VDQN_CHECK(net, "vdqn_net_set_augment: null net");
-  VDQN_CHECK(((uintptr_t)params & 15) == 0, "vdqn_net_set_augment: params must be 16-byte aligned");
-  net->aug = params;
   return VDQN_OK;
 }
 
@@ -1357,14 +1337,16 @@ extern "C" int vdqn_net_td_forward(vdqn_net* net, const vdqn_step_args* a, void*
   VDQN_CHECK(B >= 1 && 2 * B <= net->cfg.max_batch, "vdqn_net_td_forward: batch %d needs max_batch >= %d", B, 2 * B);
   VDQN_CHECK(gtb ? (a->gt != nullptr) : (a->after && a->packed_target && a->rew && a->term), "vdqn_net_td_forward: missing inputs for this loss branch");
   VDQN_CHECK(gtb || a->acts_target, "vdqn_net_td_forward: acts_target is NULL");
-  VDQN_CHECK(!net->aug || a->src_kind == 0, "vdqn_net_td_forward: augmentation is set (vdqn_net_set_augment): it takes uint8 NHWC frames (src_kind 0), not src_kind %d", a->src_kind);
-  VDQN_CHECK(!net->aug || !a->packed_frames, "vdqn_net_td_forward: augmentation is set (vdqn_net_set_augment): packed_frames were packed without it");
+  VDQN_CHECK(a->sample_weight || !a->sample_err, "vdqn_net_td_forward: sample_err without sample_weight");
+  VDQN_CHECK(!a->sample_weight || !gtb, "vdqn_net_td_forward: sample_weight is given, but the ground-truth branch has no weighted loss");
+  VDQN_CHECK(((uintptr_t)a->aug_params & 15) == 0, "vdqn_net_td_forward: aug_params must be 16-byte aligned");
+  VDQN_CHECK(!a->aug_params || a->src_kind == 0, "vdqn_net_td_forward: aug_params take uint8 NHWC frames (src_kind 0), not src_kind %d", a->src_kind);
+  VDQN_CHECK(!a->aug_params || !a->packed_frames, "vdqn_net_td_forward: aug_params are given, but packed_frames were packed without them");
   hipStream_t st = (hipStream_t)stream;
   const int F = net->cfg.num_frames, dt = net->cfg.dtype;
   const int ns_online = step_layout_samples(net, a);
   const ActLayout A = act_layout(net, ns_online);
   const BwdLayout W = bwd_layout(net, B);
-  net->bwd_samples = B;
   unsigned char* ao = (unsigned char*)a->acts_online;
   unsigned char* bw = (unsigned char*)a->bwd;
 
@@ -1377,9 +1359,9 @@ extern "C" int vdqn_net_td_forward(vdqn_net* net, const vdqn_step_args* a, void*
   // (tried and measured slower, experiments/: the s' frames packed first with the target pass right behind them; the two packs
   // on two streams; a split weight fold with layer3+ beside the stem; stage folds behind their early Adam; online and target
   // forward as one chain of grouped launches; the online pass as two half-batch passes on two streams)
-  if (net->aug) {  // the same [B][4] shift / mirror for s and s' (vdqn_net_set_augment)
-    RC(vdqn_pack_input_aug(a->before, ao + A.t_in, B * F, F, net->aug, B, dt, tst));
-    if (!gtb) RC(vdqn_pack_input_aug(a->after, ao + A.t_in + (int64_t)B * F * frame_bytes, B * F, F, net->aug, B, dt, tst));
+  if (a->aug_params) {  // the same [B][4] shift / mirror for s and s'
+    RC(vdqn_pack_input_aug(a->before, ao + A.t_in, B * F, F, a->aug_params, B, dt, tst));
+    if (!gtb) RC(vdqn_pack_input_aug(a->after, ao + A.t_in + (int64_t)B * F * frame_bytes, B * F, F, a->aug_params, B, dt, tst));
   } else if (!a->packed_frames) {
     RC(vdqn_pack_input(a->before, a->src_kind, ao + A.t_in, B * F, dt, tst));
     if (!gtb) RC(vdqn_pack_input(a->after, a->src_kind, ao + A.t_in + (int64_t)B * F * frame_bytes, B * F, dt, tst));
@@ -1421,10 +1403,9 @@ extern "C" int vdqn_net_td_forward(vdqn_net* net, const vdqn_step_args* a, void*
     t.loss_kind = a->loss_kind;
     t.deterministic = net->cfg.deterministic;
     t.q_copy = a->q_before;  // (the compact copy of Q(s) rides in the loss launch: no 2-D copy between the loss and the first data gradient)
-    if (net->sample_w) RC(vdqn_td_loss_weighted(&t, net->sample_w, net->sample_err, st));
+    if (a->sample_weight) RC(vdqn_td_loss_weighted(&t, a->sample_weight, a->sample_err, st));
     else RC(vdqn_td_loss(&t, st));
   } else {
-    VDQN_CHECK(!net->sample_w, "vdqn_net_td_forward: sample weights are set, but the ground-truth branch has no weighted loss");
     RC(vdqn_gt_loss(qf_online, a->act, a->gt, a->loss, bw + W.dq, nullptr, B, net->cfg.num_classes, net->cfg.action_dim, 64, a->inv_count,
                     a->value_learning, dt, st));
   }
@@ -1450,11 +1431,11 @@ int block_backward(vdqn_net* net, const vdqn_step_args* a, int b, const ActLayou
   const void* g_out = bw + W.g_o[b];
   // conv2: weight gradient, then data gradient into g_h masked by relu(h)
   hipStream_t ws = wgrad_stream(net, st);  // g_out is complete on `st`
-  RC(run_wgrad(net, c2, bw, g_out, ao + A.h[b], n, ws));
-  if (net->l_b_ds[b] >= 0) RC(run_wgrad(net, net->layers[net->l_b_ds[b]], bw, g_out, x, n, ws));
+  RC(run_wgrad(net, c2, bw, W, g_out, ao + A.h[b], n, ws));
+  if (net->l_b_ds[b] >= 0) RC(run_wgrad(net, net->layers[net->l_b_ds[b]], bw, W, g_out, x, n, ws));
   RC(run_dgrad(net, c2, pk, g_out, bw + W.g_h[b], n, nullptr, ao + A.h[b], st, bw + W.p_h[b]));
   ws = wgrad_stream(net, st);  // g_h is complete
-  RC(run_wgrad(net, c1, bw, bw + W.g_h[b], x, n, ws));
+  RC(run_wgrad(net, c1, bw, W, bw + W.g_h[b], x, n, ws));
   const void* resid = g_out;  // identity shortcut
   if (net->l_b_ds[b] >= 0) {
     const Layer& ds = net->layers[net->l_b_ds[b]];
@@ -1496,16 +1477,16 @@ int block_backward_train(vdqn_net* net, const vdqn_step_args* a, int b, const Ac
   const void* g_out = bw + W.g_o[b];
   RC(run_bn_bwd(net, a, i2, A, g_out, ao + A.r_o[b], bw + W.g_or[b], n, st));
   hipStream_t ws = fork_side(net, st);
-  RC(run_wgrad(net, c2, bw, bw + W.g_or[b], ao + A.h[b], n, ws));
+  RC(run_wgrad(net, c2, bw, W, bw + W.g_or[b], ao + A.h[b], n, ws));
   if (ids >= 0) {
     RC(run_bn_bwd(net, a, ids, A, g_out, ao + A.r_ds[b], bw + W.g_dsr[b], n, st));
     ws = fork_side(net, st);
-    RC(run_wgrad(net, net->layers[ids], bw, bw + W.g_dsr[b], x, n, ws));
+    RC(run_wgrad(net, net->layers[ids], bw, W, bw + W.g_dsr[b], x, n, ws));
   }
   RC(run_dgrad(net, c2, pk, bw + W.g_or[b], bw + W.g_h[b], n, nullptr, ao + A.h[b], st));
   RC(run_bn_bwd(net, a, i1, A, bw + W.g_h[b], ao + A.r_h[b], bw + W.g_h[b], n, st));
   ws = fork_side(net, st);
-  RC(run_wgrad(net, c1, bw, bw + W.g_h[b], x, n, ws));
+  RC(run_wgrad(net, c1, bw, W, bw + W.g_h[b], x, n, ws));
   const void* resid = g_out;
   if (ids >= 0) {
     RC(run_dgrad(net, net->layers[ids], pk, bw + W.g_dsr[b], bw + W.dsg[b], n, nullptr, nullptr, st));
@@ -1535,7 +1516,6 @@ extern "C" int vdqn_net_backward_begin(vdqn_net* net, const vdqn_step_args* a, c
   hipStream_t st = (hipStream_t)stream;
   const int B = a->batch;
   const BwdLayout W = bwd_layout(net, B);
-  net->bwd_samples = B;
   unsigned char* bw = (unsigned char*)a->bwd;
   hipError_t e = hipMemsetAsync(bw + W.zero_begin, 0, (size_t)W.zero_bytes, st);
   VDQN_CHECK(e == hipSuccess, "vdqn_net_backward_begin: memset failed: %s", hipGetErrorString(e));
@@ -1571,7 +1551,7 @@ extern "C" int vdqn_net_backward_stage(vdqn_net* net, const vdqn_step_args* a, i
   if (net->basic()) {
     if (stage == 0) {
       const Layer& top = net->layers[net->l_top4];
-      RC(run_wgrad(net, top, bw, bw + W.dq, ao + A.avg, B, wgrad_stream(net, st), true));
+      RC(run_wgrad(net, top, bw, W, bw + W.dq, ao + A.avg, B, wgrad_stream(net, st), true));
       RC(run_dgrad(net, top, pk, bw + W.dq, bw + W.g_avg, B, nullptr, nullptr, st));
       RC(vdqn_avgpool_bwd(bw + W.g_avg, ao + A.o[7], bw + W.g_o[7], n, 49, 512, dt, st));
       RC(block_backward_train(net, a, 7, A, W, n, st));
@@ -1583,20 +1563,20 @@ extern "C" int vdqn_net_backward_stage(vdqn_net* net, const vdqn_step_args* a, i
       for (int b = 3; b >= 0; --b) RC(block_backward_train(net, a, b, A, W, n, st));
       RC(vdqn_maxpool_bwd(bw + W.g_pool, ao + A.idx, nullptr, bw + W.g_c1, n, 112, 112, 64, dt, st));
       RC(run_bn_bwd(net, a, net->l_conv1, A, bw + W.g_c1, ao + A.r_c1, bw + W.g_c1, n, st));
-      RC(run_wgrad(net, net->layers[net->l_conv1], bw, bw + W.g_c1, a->packed_frames ? a->packed_frames : ao + A.t_in, n, wgrad_stream(net, st)));
+      RC(run_wgrad(net, net->layers[net->l_conv1], bw, W, bw + W.g_c1, a->packed_frames ? a->packed_frames : ao + A.t_in, n, wgrad_stream(net, st)));
     }
   } else if (stage == 0) {
     const Layer& t4 = net->layers[net->l_top4];
     const Layer& t2 = net->layers[net->l_top2];
     const Layer& t0 = net->layers[net->l_top0];
     const Layer& f8 = net->layers[net->l_f8];
-    RC(run_wgrad(net, t4, bw, bw + W.dq, ao + A.l1, B, wgrad_stream(net, st), true));
+    RC(run_wgrad(net, t4, bw, W, bw + W.dq, ao + A.l1, B, wgrad_stream(net, st), true));
     RC(run_dgrad(net, t4, pk, bw + W.dq, bw + W.g_l1, B, nullptr, ao + A.l1, st, bw + W.p_l1, nullptr, nullptr, &pr_l1));
-    RC(run_wgrad(net, t2, bw, bw + W.g_l1, ao + A.l0, B, wgrad_stream(net, st)));
+    RC(run_wgrad(net, t2, bw, W, bw + W.g_l1, ao + A.l0, B, wgrad_stream(net, st)));
     RC(run_dgrad(net, t2, pk, bw + W.g_l1, bw + W.g_l0, B, nullptr, ao + A.l0, st, bw + W.p_l0, nullptr, nullptr, &pr_l0));
-    RC(run_wgrad(net, t0, bw, bw + W.g_l0, ao + A.f8, B, wgrad_stream(net, st)));
+    RC(run_wgrad(net, t0, bw, W, bw + W.g_l0, ao + A.f8, B, wgrad_stream(net, st)));
     RC(run_dgrad(net, t0, pk, bw + W.g_l0, bw + W.g_f8, B, nullptr, ao + A.f8, st, bw + W.p_f8, nullptr, nullptr, &pr_f8));
-    RC(run_wgrad(net, f8, bw, bw + W.g_f8, ao + A.o[7], n, wgrad_stream(net, st)));
+    RC(run_wgrad(net, f8, bw, W, bw + W.g_f8, ao + A.o[7], n, wgrad_stream(net, st)));
     RC(run_dgrad(net, f8, pk, bw + W.g_f8, bw + W.g_o[7], n, nullptr, ao + A.o[7], st, bw + W.p_o[7]));
     RC(block_backward(net, a, 7, A, W, n, st));
     RC(block_backward(net, a, 6, A, W, n, st));
@@ -1663,7 +1643,7 @@ extern "C" int vdqn_net_backward_stage(vdqn_net* net, const vdqn_step_args* a, i
     }
     // max-pool backward on the caller's stream, the weight gradient behind it on the side stream
     RC(vdqn_maxpool_bwd(bw + W.g_pool, ao + A.idx, nullptr, bw + W.g_c1, n, 112, 112, 64, dt, st));
-    RC(run_wgrad(net, L1, bw, bw + W.g_c1, a->packed_frames ? a->packed_frames : ao + A.t_in, n, wgrad_stream(net, st)));
+    RC(run_wgrad(net, L1, bw, W, bw + W.g_c1, a->packed_frames ? a->packed_frames : ao + A.t_in, n, wgrad_stream(net, st)));
     return VDQN_OK;
   };
   if (stem_tail && !split_conv1) RC(conv1_chain());

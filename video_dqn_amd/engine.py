@@ -330,7 +330,6 @@ class TDStepper:
         # callable() or None: with step(td_error=...) under data parallelism, queued behind the loss exchange on the gradient stream
         # (dist.launch_errors: the SUM of the ranks' slices of the prioritized-replay error buffer; `finish_allreduce` waits for it)
         self.allreduce_errors = allreduce_errors
-        self._err_ready = None
         self._post_stream = None
         self._post_used = False
         dev = net.device
@@ -370,7 +369,7 @@ class TDStepper:
         with torch.cuda.device(self.net.device):
             self.net.pack_weights(self.packed_target, with_dgrad=False)
 
-    def _args(self, before, after, src_kind, act, rew, term, valid, gt) -> _lib.StepArgs:
+    def _args(self, before, after, src_kind, act, rew, term, valid, gt, weights=None, td_error=None, augment=None) -> _lib.StepArgs:
         n = self.net
         a = _lib.StepArgs()
         a.params, a.bnstats = _ptr(n.params), _ptr(n.bnstats)
@@ -385,6 +384,7 @@ class TDStepper:
         a.grads, a.loss, a.q_before = _ptr(self.grads), _ptr(self.loss), _ptr(self.q_before)
         a.loss_kind = LOSS_KINDS[self.loss_kind]
         a.packed_frames = None
+        a.sample_weight, a.sample_err, a.aug_params = _ptr(weights), _ptr(td_error), _ptr(augment)
         return a
 
     # ---- frames packed one update ahead (vdqn_step_args.packed_frames) -----------------------------------------------------
@@ -440,19 +440,22 @@ class TDStepper:
                 _lib.check(self.lib.vdqn_pack_input(_ptr(na), int(nk), buf.data_ptr() + half, nf, dt, _stream()), "vdqn_pack_input")
         self._ahead = (self._frames_key(nb, na, nk), slot, (nb, na))  # (the tensors are kept alive until they are consumed)
 
-    def forward_backward(self, before, after, src_kind, act, rew, term, valid=None, gt=None, early_adam: bool = False, next_frames=None):
+    def forward_backward(self, before, after, src_kind, act, rew, term, valid=None, gt=None, early_adam: bool = False, next_frames=None,
+                         *, weights=None, td_error=None, augment=None):
         """Everything of one update up to (and including) the gradient all-reduce; no optimiser step.
 
         early_adam (only `step` passes it: single process, no exchange, eval-mode BatchNorm): the optimiser update of stage 0 and stage 1 is
         queued on the engine's gradient stream right behind that stage's gradient unpack, so it runs under the remaining data /
         weight gradients instead of behind them (nothing later in the update reads those master parameters: the kernels work on
-        the packed copies); `optimizer_step` then only covers what is left.  Same arithmetic, same results."""
+        the packed copies); `optimizer_step` then only covers what is left.  Same arithmetic, same results.
+
+        weights, td_error, augment: as `step` describes and validates them (vdqn_step_args.sample_weight / sample_err / aug_params)."""
         n = self.net
         self._adam_done = []
         self._clip_slots = 0
-        keep = (before, after, act, rew, term, valid, gt)  # keep inputs alive until the launches are queued
+        keep = (before, after, act, rew, term, valid, gt, weights, td_error, augment)  # keep inputs alive until the launches are queued
         with torch.cuda.device(n.device):
-            a = self._args(before, after, src_kind, act, rew, term, valid if valid is not None else self._ones, gt)
+            a = self._args(before, after, src_kind, act, rew, term, valid if valid is not None else self._ones, gt, weights, td_error, augment)
             st = _stream()
             ahead, self._ahead = self._ahead, None
             slot = None
@@ -461,7 +464,7 @@ class TDStepper:
                 a.packed_frames = self._packed_buffer(slot).data_ptr()
             _lib.check(self.lib.vdqn_net_td_forward(n.handle, C.byref(a), st), "vdqn_net_td_forward")
             err_ready = None
-            if self._err_ready is not None:  # step(td_error=...): the loss launch has written this rank's errors on `st`
+            if td_error is not None and self.allreduce_errors is not None:  # the loss launch has written this rank's errors on `st`
                 err_ready = torch.cuda.Event()
                 err_ready.record()
             if next_frames is not None:
@@ -584,13 +587,13 @@ class TDStepper:
         (vdqn_step_args.packed_frames).
 
         weights (prioritized replay): f32 [B] importance weights on the device — the loss launch scales each sample's loss terms and
-        dQ row by them (vdqn_net_set_sample_weights; ones give the unweighted update bit for bit).  td_error: f32 [B] on the device,
+        dQ row by them (vdqn_step_args.sample_weight; ones give the unweighted update bit for bit).  td_error: f32 [B] on the device,
         where that launch writes each sample's mean |TD error| over the categories; under data parallelism `allreduce_errors` is
         then queued behind the loss exchange.  TD branch only.
 
         augment (video_dqn_amd/augment.py): int32 [B][4] {sx, sy, flip, 0} on the device — this update's frames (uint8 NHWC, src_kind
-        0) are packed through vdqn_pack_input_aug with them, the same for `before` and `after` (vdqn_net_set_augment, cleared after
-        the update).  The caller passes the action labels that go with the mirrored samples (Augmenter.actions)."""
+        0) are packed through vdqn_pack_input_aug with them, the same for `before` and `after` (vdqn_step_args.aug_params, this
+        update only).  The caller passes the action labels that go with the mirrored samples (Augmenter.actions)."""
         if augment is not None:
             if augment.dtype != torch.int32 or tuple(augment.shape) != (self.B, 4) or not augment.is_contiguous() or not augment.is_cuda:
                 raise _lib.VdqnError(f"TDStepper.step: augment must be a contiguous int32 [{self.B}][4] device tensor")
@@ -605,20 +608,6 @@ class TDStepper:
             for name, t in (("weights", weights), ("td_error", td_error)):
                 if t is not None and (t.dtype != torch.float32 or t.numel() != self.B or not t.is_contiguous() or not t.is_cuda):
                     raise _lib.VdqnError(f"TDStepper.step: {name} must be a contiguous f32 [{self.B}] device tensor")
-            _lib.check(self.lib.vdqn_net_set_sample_weights(self.net.handle, _ptr(weights), _ptr(td_error)), "vdqn_net_set_sample_weights")
-            self._err_ready = True if (td_error is not None and self.allreduce_errors is not None) else None
-        try:
-            if augment is not None:
-                _lib.check(self.lib.vdqn_net_set_augment(self.net.handle, _ptr(augment)), "vdqn_net_set_augment")
-            return self._step(before, after, src_kind, act, rew, term, valid, gt, finish_allreduce, next_frames)
-        finally:
-            if augment is not None:
-                _lib.check(self.lib.vdqn_net_set_augment(self.net.handle, None), "vdqn_net_set_augment")
-            if weights is not None:
-                self._err_ready = None
-                _lib.check(self.lib.vdqn_net_set_sample_weights(self.net.handle, None, None), "vdqn_net_set_sample_weights")
-
-    def _step(self, before, after, src_kind, act, rew, term, valid, gt, finish_allreduce, next_frames) -> torch.Tensor:
         self.sample_number += 1
         if self.sample_number % self.tui == 0:
             self.sync_target()
@@ -627,7 +616,8 @@ class TDStepper:
         # (single process only: behind each RCCL bucket on a stream of its own it measured 7.22 vs 5.96 ms per update with one rank,
         # profiles/r03s_ab_rccl_early_adam.txt — with an exchange the whole optimiser update stays behind `finish_allreduce`)
         early = _EARLY_ADAM and self.net.extra_capacity and self.allreduce is None and finish_allreduce is None and self.grad_clip_norm == 0
-        self.forward_backward(before, after, src_kind, act, rew, term, valid, gt, early_adam=early, next_frames=next_frames)
+        self.forward_backward(before, after, src_kind, act, rew, term, valid, gt, early_adam=early, next_frames=next_frames,
+                              weights=weights, td_error=td_error, augment=augment)
         if finish_allreduce is not None:
             finish_allreduce()
             self._clip_slots = 0  # the gradient has just been reduced: its norm is taken from what `grads` holds now
