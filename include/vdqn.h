@@ -194,6 +194,19 @@ int vdqn_td_loss(const vdqn_td_args* a, void* stream);
  * TD error sum_c |d_bc| * valid_bc / n_cat, from the raw d under either loss kind.  No atomics for err_out; `deterministic` keeps
  * its one-block loss sum.  With weight == 1 the loss and dq are bit-identical to vdqn_td_loss. */
 int vdqn_td_loss_weighted(const vdqn_td_args* a, const float* weight, float* err_out, void* stream);
+/* The same loss with the discrete conservative Q-learning penalty (CQL; Kumar et al., NeurIPS 2020) for training from logged
+ * data only, added to the loss of train_q_network.py:167,180 in the same launch:
+ *   pen_bc = logsumexp_a q_before[b,c,:] - q_before[b,c,act[b]]   (the maximum is subtracted before anything is exponentiated)
+ *   s_bc = weight[b] * valid_bc;  loss += inv_count * sum s_bc * (l(d_bc) + cql_alpha * pen_bc)
+ *   penalty += inv_count * sum s_bc * pen_bc                      (not scaled by cql_alpha)
+ *   dq[b, c*A+a] = inv_count * s_bc * ([a == act[b]] * dl(d_bc) + cql_alpha * (softmax_a(q_before[b,c,:]) - [a == act[b]]))
+ * so dq is dense over the actions of every category (padding columns 0).  d, l, dl, weight and err_out are those of
+ * vdqn_td_loss_weighted (err_out is the raw TD error: priorities do not follow the penalty); weight may be NULL (= 1), err_out and
+ * penalty (a pre-zeroed f32 scalar) may be NULL.  dtype VDQN_F32 or VDQN_BF16.  cql_alpha must be finite and > 0 and n_act >= 2
+ * (with one action the penalty is identically zero): both fail by name, like every other check, before any launch.
+ * `deterministic` sums loss and penalty in one block in a fixed order. */
+int vdqn_td_loss_cql(const vdqn_td_args* a, const float* weight /* NULL = 1 */, float* err_out /* NULL ok */, float cql_alpha,
+                     float* penalty /* pre-zeroed f32 scalar, NULL ok */, void* stream);
 
 /* Ground-truth branch (train_q_network.py:170-178): l = 0.5 (Qb*mask - gt)^2, mask = !isnan(gt) when
  * value_learning, else l = 0.5 (Qb - gt)^2.  gt is f32 [batch][n_cat] (NaN allowed). */
@@ -439,6 +452,12 @@ typedef struct vdqn_step_args {
                                  then fails for src_kind != 0 and for packed_frames.  NULL: the plain pack. */
 } vdqn_step_args;
 int vdqn_net_td_forward(vdqn_net* net, const vdqn_step_args* a, void* stream);
+/* vdqn_net_td_forward with the conservative penalty (train_q_network.py:167,180): with cql_alpha > 0 the loss launch is
+ * vdqn_td_loss_cql (sample_weight / sample_err passed through, NULL = unweighted) and cql_penalty (device f32 scalar, may be
+ * NULL) is cleared beside `loss` and receives this call's share of the penalty; `loss` is then the full objective.  cql_alpha
+ * == 0 is vdqn_net_td_forward: the same launches and bits.  Fails by name for a negative or non-finite cql_alpha, and with
+ * cql_alpha > 0 for train_on_ground_truth and for action_dim == 1.  Either architecture, every compute mode. */
+int vdqn_net_td_forward_cql(vdqn_net* net, const vdqn_step_args* a, float cql_alpha, float* cql_penalty, void* stream);
 /* Stage s of the backward pass (0: head + layer4, 1: layer3, 2: layer2, layer1, stem).  With the overlap on, the stage's weight
  * gradients and the kernel that writes its range of `grads` run on the engine's side stream: after the call returns that range is
  * complete on vdqn_net_grad_stream(net), NOT on `stream`, which goes straight on to the next stage's data gradients.  The call

@@ -145,6 +145,8 @@ _SIGS = {
     "vdqn_grad_sumsq": (C.c_int, [c_vp, c_i64, c_vp, c_i32, c_vp]),
     "vdqn_clip_finalize": (C.c_int, [c_vp, c_i32, C.c_double, c_vp, c_vp]),
     "vdqn_adam_scaled": (C.c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i32, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, c_vp, c_vp]),
+    "vdqn_td_loss_cql": (C.c_int, [C.POINTER(TdArgs), c_vp, c_vp, c_f32, c_vp, c_vp]),
+    "vdqn_net_td_forward_cql": (C.c_int, [c_vp, C.POINTER(StepArgs), c_f32, c_vp, c_vp]),
 }
 COMM_UID_BYTES = 128
 EXPORTS = tuple(_SIGS)

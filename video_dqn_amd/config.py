@@ -33,7 +33,10 @@ and never read back for the update), WEIGHT_DECAY (0.0: decoupled, as torch.opti
 Adam update, over every trainable element; resnet.fc, which never receives a gradient, stays untouched), LR_WARMUP_STEPS (0:
 the rate of update t, the 1-based sample_number, is multiplied by min(1, t / W)), LR_SCHEDULE ('constant' | 'linear' | 'cosine': after
 the warm-up the rate goes from LEARNING_RATE to LEARNING_RATE * LR_FINAL_FRACTION at NUM_STEPS, progress = clamp((t - W) /
-(NUM_STEPS - W), 0, 1); cosine is f + (1 - f) * (1 + cos(pi * progress)) / 2), LR_FINAL_FRACTION (0.0).
+(NUM_STEPS - W), 0, 1); cosine is f + (1 - f) * (1 + cos(pi * progress)) / 2), LR_FINAL_FRACTION (0.0), CQL_ALPHA (0.0 = off; > 0:
+conservative Q-learning for training from logged data, Kumar et al. 2020 — CQL_ALPHA * (logsumexp_a Q(s, .) - Q(s, a_data)), averaged
+like the TD loss, is added to it inside the loss launch on the GPU, which pulls down the values of actions the data never shows;
+1.0 is the usual discrete setting; the TD branch with more than one action column only).
 """
 from __future__ import annotations
 
@@ -168,6 +171,7 @@ def get_cfg_defaults() -> CfgNode:
     c.LR_WARMUP_STEPS = 0         # the learning rate of update t is multiplied by min(1, t / LR_WARMUP_STEPS)
     c.LR_SCHEDULE = "constant"    # 'constant' | 'linear' | 'cosine': from LEARNING_RATE to LEARNING_RATE * LR_FINAL_FRACTION at NUM_STEPS
     c.LR_FINAL_FRACTION = 0.0
+    c.CQL_ALPHA = 0.0             # > 0: conservative Q-learning penalty CQL_ALPHA * (logsumexp_a Q(s, .) - Q(s, a_data)) in the loss launch; 0 = off
     return c
 
 

@@ -1329,7 +1329,8 @@ static int step_layout_samples(const vdqn_net* net, const vdqn_step_args* a) {
   return 2 * a->batch;
 }
 
-extern "C" int vdqn_net_td_forward(vdqn_net* net, const vdqn_step_args* a, void* stream) {
+// vdqn_net_td_forward (cql_alpha == 0: the launches and bits it always had) and vdqn_net_td_forward_cql (cql_alpha > 0)
+static int td_forward_impl(vdqn_net* net, const vdqn_step_args* a, float cql_alpha, float* cql_penalty, void* stream) {
   VDQN_CHECK(net && a, "vdqn_net_td_forward: null arg");
   VDQN_CHECK(a->params && a->bnstats && a->packed_online && a->before && a->act && a->acts_online && a->bwd && a->loss, "vdqn_net_td_forward: null buffer");
   const int B = a->batch;
@@ -1384,6 +1385,10 @@ extern "C" int vdqn_net_td_forward(vdqn_net* net, const vdqn_step_args* a, void*
   VDQN_CHECK(e == hipSuccess, "vdqn_net_td_forward: memset failed: %s", hipGetErrorString(e));
   e = hipMemsetAsync(a->loss, 0, 4, st);
   VDQN_CHECK(e == hipSuccess, "vdqn_net_td_forward: memset failed: %s", hipGetErrorString(e));
+  if (cql_alpha > 0.f && cql_penalty) {
+    e = hipMemsetAsync(cql_penalty, 0, 4, st);
+    VDQN_CHECK(e == hipSuccess, "vdqn_net_td_forward_cql: memset failed: %s", hipGetErrorString(e));
+  }
 
   const float* qf_online = reinterpret_cast<const float*>(ao + A.qf);
   if (!gtb) {
@@ -1403,7 +1408,8 @@ extern "C" int vdqn_net_td_forward(vdqn_net* net, const vdqn_step_args* a, void*
     t.loss_kind = a->loss_kind;
     t.deterministic = net->cfg.deterministic;
     t.q_copy = a->q_before;  // (the compact copy of Q(s) rides in the loss launch: no 2-D copy between the loss and the first data gradient)
-    if (a->sample_weight) RC(vdqn_td_loss_weighted(&t, a->sample_weight, a->sample_err, st));
+    if (cql_alpha > 0.f) RC(vdqn_td_loss_cql(&t, a->sample_weight, a->sample_err, cql_alpha, cql_penalty, st));
+    else if (a->sample_weight) RC(vdqn_td_loss_weighted(&t, a->sample_weight, a->sample_err, st));
     else RC(vdqn_td_loss(&t, st));
   } else {
     RC(vdqn_gt_loss(qf_online, a->act, a->gt, a->loss, bw + W.dq, nullptr, B, net->cfg.num_classes, net->cfg.action_dim, 64, a->inv_count,
@@ -1415,6 +1421,18 @@ extern "C" int vdqn_net_td_forward(vdqn_net* net, const vdqn_step_args* a, void*
     VDQN_CHECK(e == hipSuccess, "vdqn_net_td_forward: q copy failed: %s", hipGetErrorString(e));
   }
   return VDQN_OK;
+}
+
+extern "C" int vdqn_net_td_forward(vdqn_net* net, const vdqn_step_args* a, void* stream) { return td_forward_impl(net, a, 0.f, nullptr, stream); }
+
+extern "C" int vdqn_net_td_forward_cql(vdqn_net* net, const vdqn_step_args* a, float cql_alpha, float* cql_penalty, void* stream) {
+  VDQN_CHECK(net && a, "vdqn_net_td_forward_cql: null arg");
+  VDQN_CHECK(isfinite(cql_alpha) && cql_alpha >= 0.f, "vdqn_net_td_forward_cql: cql_alpha %g must be finite and >= 0 (0 = vdqn_net_td_forward)", (double)cql_alpha);
+  if (cql_alpha > 0.f) {
+    VDQN_CHECK(!a->train_on_ground_truth, "vdqn_net_td_forward_cql: the ground-truth branch regresses Q(s, a) on given targets and has no conservative penalty (train_on_ground_truth with cql_alpha > 0)");
+    VDQN_CHECK(net->cfg.action_dim >= 2, "vdqn_net_td_forward_cql: action_dim is 1: with one action the penalty is identically zero");
+  }
+  return td_forward_impl(net, a, cql_alpha, cql_penalty, stream);
 }
 
 namespace {

@@ -413,6 +413,102 @@ __global__ __launch_bounds__(256) void td_loss_w_kernel(const td_w_args a) {
   }
 }
 
+// The TD loss with the discrete conservative Q-learning penalty (Kumar et al., NeurIPS 2020; vdqn_td_loss_cql), for training from
+// logged data only (train_q_network.py:167,180 is the loss it extends).  For sample b and category c, with q = q_before[b, c*A ..
+// c*A+A) in f32 and a* = act[b]:
+//   m      = max_a q_a          sum = sum_a expf(q_a - m)  (a = 0 .. A-1, in that order)          p_a = expf(q_a - m) / sum
+//   pen_bc = logf(sum) + (m - q_{a*})    == logsumexp_a q_a - q_{a*}; the max is subtracted before anything is exponentiated, and
+//            m - q_{a*} is taken before the logarithm is added, so a row such as [1e4, -1e4, 0] loses nothing to the size of m
+//   d, l(d), dl(d)  exactly as td_loss_w_kernel (td_error_of; loss kinds 0 / 1)
+//   s_bc   = w_b * vm_bc                                  (w_b = 1 without weights; vm_bc = valid or 1)
+//   loss    += inv_count * sum_bc s_bc * (l(d_bc) + alpha * pen_bc)
+//   penalty += inv_count * sum_bc s_bc * pen_bc           (not scaled by alpha)
+//   dq[b, c*A+a] = (([a == a*] ? dl(d_bc) : 0) + alpha * (p_a - [a == a*])) * s_bc * inv_count;  padding columns 0
+// so dq is dense over the actions of every category, where the two kernels above write one column per category.  err[b] stays
+// the raw mean |d| (priorities follow the TD error, not the penalty).  One thread per (sample, padded column), as above: each
+// thread of a category recomputes that category's m and sum from A loads (A is 3 here; the row is in cache), and the thread of
+// the taken action adds the loss terms.  A third kernel rather than a flag, for the reason td_loss_w_kernel gives.
+// Blocks are 256 threads, or ONE block of 1024 for a deterministic launch: the same fixed order (thread t takes elements t,
+// t + 1024, ..; a shuffle tree per wave; the waves' partial sums added first to last by thread 0) with a quarter of the serial
+// passes of a 256-thread block.  __launch_bounds__(1024) is there for that launch alone, and it budgets the 256-thread launches
+// too: 128 VGPRs per thread.  The kernel takes 38; should it grow, it has to stay under that.
+struct td_cql_args : vdqn_td_args {
+  const float* w;  // [batch] or NULL (= 1)
+  float* err;      // [batch] or NULL
+  float* penalty;  // f32 scalar or NULL
+  float alpha;
+};
+template <typename T>
+__global__ __launch_bounds__(1024) void td_loss_cql_kernel(const td_cql_args a) {
+  const int total = a.batch * a.ldq;
+  float my_loss = 0.f, my_pen = 0.f;
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
+    const int b = i / a.ldq, col = i - b * a.ldq;
+    float g = 0.f;
+    if (col < a.n_cat * a.n_act) {
+      const int c = col / a.n_act, ac = col - c * a.n_act;
+      const int act = (int)a.act[b];
+      const float* q = a.q_before + (size_t)b * a.ldq + c * a.n_act;
+      if (a.q_copy) a.q_copy[(size_t)b * (a.n_cat * a.n_act) + col] = q[ac];
+      float m = q[0];
+      for (int k = 1; k < a.n_act; ++k) m = fmaxf(m, q[k]);
+      float sum = 0.f;
+      for (int k = 0; k < a.n_act; ++k) sum += expf(q[k] - m);
+      const float p = expf(q[ac] - m) / sum;
+      const float vm = a.use_valid ? a.valid[b * a.n_cat + c] : 1.0f;
+      const float s = (a.w ? a.w[b] : 1.0f) * vm;
+      if (ac == act) {
+        const float d = td_error_of(a, b, c, col);
+        float l, dl;
+        if (a.loss_kind == 1) {  // Huber, beta = 1 (torch.nn.functional.smooth_l1_loss)
+          const float ad = fabsf(d);
+          l = ad < 1.0f ? 0.5f * d * d : ad - 0.5f;
+          dl = fminf(fmaxf(d, -1.0f), 1.0f);
+        } else {
+          l = 0.5f * d * d;
+          dl = d;
+        }
+        const float pen = logf(sum) + (m - q[ac]);
+        my_loss += s * (l + a.alpha * pen);
+        my_pen += s * pen;
+        g = dl + a.alpha * (p - 1.0f);
+      } else {
+        g = a.alpha * p;
+      }
+      g = g * s * a.inv_count;
+    }
+    if (col == 0 && a.err) {
+      float e = 0.f;
+      for (int c = 0; c < a.n_cat; ++c) e += fabsf(td_error_of(a, b, c, c * a.n_act + (int)a.act[b])) * (a.use_valid ? a.valid[b * a.n_cat + c] : 1.0f);
+      a.err[b] = e / (float)a.n_cat;
+    }
+    if (a.dq) ((T*)a.dq)[i] = from_f32<T>(g);
+    if (a.dq_f32) a.dq_f32[i] = g;
+  }
+  // block reduction of the loss and the penalty: 4 waves, or 16 in the one block of a deterministic launch
+  __shared__ float red[2][16];
+  float v = my_loss, u = my_pen;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    v += __shfl_down(v, o, 64);
+    u += __shfl_down(u, o, 64);
+  }
+  if ((threadIdx.x & 63) == 0) {
+    red[0][threadIdx.x >> 6] = v;
+    red[1][threadIdx.x >> 6] = u;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float sl = 0.f, sp = 0.f;
+    for (int w = 0; w < (int)(blockDim.x >> 6); ++w) {
+      sl += red[0][w];
+      sp += red[1][w];
+    }
+    if (sl != 0.f) atomicAdd(a.loss, sl * a.inv_count);
+    if (a.penalty && sp != 0.f) atomicAdd(a.penalty, sp * a.inv_count);
+  }
+}
+
 // ground-truth branch (train_q_network.py:170-178)
 template <typename T>
 __global__ __launch_bounds__(256) void gt_loss_kernel(const float* __restrict__ q_before, const int64_t* __restrict__ act,
@@ -662,6 +758,29 @@ extern "C" int vdqn_td_loss_weighted(const vdqn_td_args* a, const float* weight,
   k.err = err_out;
   if (a->dtype == VDQN_BF16) hipLaunchKernelGGL((td_loss_w_kernel<bf16raw>), dim3(g), dim3(256), 0, (hipStream_t)stream, k);
   else hipLaunchKernelGGL((td_loss_w_kernel<float>), dim3(g), dim3(256), 0, (hipStream_t)stream, k);
+  VDQN_LAUNCH_CHECK();
+  return VDQN_OK;
+}
+
+extern "C" int vdqn_td_loss_cql(const vdqn_td_args* a, const float* weight, float* err_out, float cql_alpha, float* penalty, void* stream) {
+  VDQN_CHECK(a && a->q_before && a->q_after_online && a->q_after_target && a->act && a->rew && a->term && a->loss, "vdqn_td_loss_cql: null arg");
+  VDQN_CHECK(!a->use_valid || a->valid, "vdqn_td_loss_cql: use_valid without valid mask");
+  VDQN_CHECK(a->batch > 0 && a->n_cat > 0 && a->n_act > 0 && a->ldq >= a->n_cat * a->n_act, "vdqn_td_loss_cql: bad dims");
+  VDQN_CHECK(a->n_act >= 2, "vdqn_td_loss_cql: n_act is 1: with one action logsumexp_a Q - Q(a) is identically zero; use vdqn_td_loss");
+  VDQN_CHECK(a->dtype == VDQN_F32 || a->dtype == VDQN_BF16, "vdqn_td_loss_cql: bad dtype");
+  VDQN_CHECK(a->loss_kind == 0 || a->loss_kind == 1, "vdqn_td_loss_cql: loss_kind %d (0 = half squared error, 1 = Huber)", a->loss_kind);
+  VDQN_CHECK(isfinite(cql_alpha) && cql_alpha > 0.f, "vdqn_td_loss_cql: cql_alpha %g must be finite and > 0 (without the penalty: vdqn_td_loss)", (double)cql_alpha);
+  const int threads = a->deterministic ? 1024 : 256;
+  const int g = a->deterministic ? 1 : (a->batch * a->ldq + 255) / 256;
+  ProfScope ps_("td_loss_cql", 0.0, (double)a->batch * a->ldq * 16.0 + (double)a->batch * 8.0, (hipStream_t)stream);
+  td_cql_args k;
+  static_cast<vdqn_td_args&>(k) = *a;
+  k.w = weight;
+  k.err = err_out;
+  k.penalty = penalty;
+  k.alpha = cql_alpha;
+  if (a->dtype == VDQN_BF16) hipLaunchKernelGGL((td_loss_cql_kernel<bf16raw>), dim3(g), dim3(threads), 0, (hipStream_t)stream, k);
+  else hipLaunchKernelGGL((td_loss_cql_kernel<float>), dim3(g), dim3(threads), 0, (hipStream_t)stream, k);
   VDQN_LAUNCH_CHECK();
   return VDQN_OK;
 }

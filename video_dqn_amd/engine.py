@@ -293,7 +293,7 @@ class TDStepper:
                  remove_before_reward: bool = False, train_on_ground_truth: bool = False, value_learning: bool = False,
                  target_update_interval: int = 8000, betas=(0.9, 0.999), eps: float = 1e-8, world_size: int = 1,
                  allreduce=None, loss_kind: str = "l2", allreduce_loss=None, allreduce_wait=None, allreduce_errors=None,
-                 grad_clip_norm: float = 0.0, weight_decay: float = 0.0, lr_fn=None):
+                 grad_clip_norm: float = 0.0, weight_decay: float = 0.0, lr_fn=None, cql_alpha: float = 0.0):
         net._need_gpu()
         self.net, self.B = net, batch
         self.lib = net.lib
@@ -317,6 +317,17 @@ class TDStepper:
         if loss_kind not in LOSS_KINDS:
             raise _lib.VdqnError(f"loss_kind must be one of {sorted(LOSS_KINDS)} (reference: 'l2', train_q_network.py:167)")
         self.loss_kind = loss_kind
+        # cql_alpha > 0 (conservative Q-learning for logged data): the loss launch is vdqn_td_loss_cql — alpha * (logsumexp_a Q(s, .) -
+        # Q(s, a_data)) added to the TD loss, dq dense over the actions — and `cql_penalty` receives this rank's share of the
+        # unscaled penalty.  0: vdqn_net_td_forward, launched as ever.
+        cql_alpha = float(cql_alpha)
+        if not (cql_alpha >= 0.0) or cql_alpha == float("inf"):
+            raise _lib.VdqnError(f"TDStepper: cql_alpha must be finite and >= 0 (0 = off), not {cql_alpha}")
+        if cql_alpha > 0 and train_on_ground_truth:
+            raise _lib.VdqnError("TDStepper: cql_alpha applies to the TD branch only (train_on_ground_truth regresses on given targets)")
+        if cql_alpha > 0 and net.action_dim < 2:
+            raise _lib.VdqnError("TDStepper: cql_alpha needs action_dim >= 2 (with one action the penalty is identically zero)")
+        self.cql_alpha = cql_alpha
         self.tui = target_update_interval
         self.world_size = world_size
         self.allreduce = allreduce  # callable(tensor_slice, stage) or None
@@ -347,6 +358,7 @@ class TDStepper:
             self.exp_avg = torch.zeros(nt, dtype=torch.float32, device=dev)
             self.exp_avg_sq = torch.zeros(nt, dtype=torch.float32, device=dev)
             self.loss = torch.zeros(1, dtype=torch.float32, device=dev)
+            self.cql_penalty = torch.zeros(1, dtype=torch.float32, device=dev)
             self.q_before = torch.zeros((batch, net.num_classes * net.action_dim), dtype=torch.float32, device=dev)
             self._ones = torch.ones((batch, net.num_classes), dtype=torch.float32, device=dev)
             if self.grad_clip_norm > 0:
@@ -462,7 +474,11 @@ class TDStepper:
             if ahead is not None and ahead[0] == self._frames_key(before, after, src_kind):
                 slot = ahead[1]  # these frames were packed during the previous update (ordered in front of `st` by its last stage)
                 a.packed_frames = self._packed_buffer(slot).data_ptr()
-            _lib.check(self.lib.vdqn_net_td_forward(n.handle, C.byref(a), st), "vdqn_net_td_forward")
+            if self.cql_alpha > 0:
+                _lib.check(self.lib.vdqn_net_td_forward_cql(n.handle, C.byref(a), self.cql_alpha, self.cql_penalty.data_ptr(), st),
+                           "vdqn_net_td_forward_cql")
+            else:
+                _lib.check(self.lib.vdqn_net_td_forward(n.handle, C.byref(a), st), "vdqn_net_td_forward")
             err_ready = None
             if td_error is not None and self.allreduce_errors is not None:  # the loss launch has written this rank's errors on `st`
                 err_ready = torch.cuda.Event()

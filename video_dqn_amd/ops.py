@@ -190,6 +190,34 @@ def td_loss(q_before, q_after_online, q_after_target, act, rew, term, valid=None
     return loss, dq, dq32
 
 
+def td_loss_cql(q_before, q_after_online, q_after_target, act, rew, term, valid=None, *, cql_alpha, weights=None, with_err=False,
+                n_cat=5, n_act=3, gamma=0.99, inv_count=None, clip_rect=True, linear=False, out_dtype=torch.float32, loss_kind="l2",
+                deterministic=False):
+    """td_loss with the conservative Q-learning penalty (vdqn_td_loss_cql): cql_alpha * (logsumexp_a Q(s, .) - Q(s, act)) per sample
+    and category, dq dense over the actions.  weights: optional f32 [B].  Returns (loss[1], dq[B, ldq] out_dtype, dq_f32,
+    penalty[1], err[B] or None)."""
+    lib = _lib.load()
+    B, ldq = q_before.shape
+    dev = q_before.device
+    loss = torch.zeros(1, dtype=torch.float32, device=dev)
+    penalty = torch.zeros(1, dtype=torch.float32, device=dev)
+    err = torch.empty(B, dtype=torch.float32, device=dev) if with_err else None
+    dq = torch.empty((B, ldq), dtype=out_dtype, device=dev)
+    dq32 = torch.empty((B, ldq), dtype=torch.float32, device=dev)
+    a = _lib.TdArgs()
+    a.q_before, a.q_after_online, a.q_after_target = _ptr(q_before), _ptr(q_after_online), _ptr(q_after_target)
+    a.act, a.rew, a.term, a.valid = _ptr(act), _ptr(rew), _ptr(term), _ptr(valid)
+    a.loss, a.dq, a.dq_f32 = _ptr(loss), _ptr(dq), _ptr(dq32)
+    a.batch, a.n_cat, a.n_act, a.ldq = B, n_cat, n_act, ldq
+    a.gamma = gamma
+    a.inv_count = (1.0 / (B * n_cat)) if inv_count is None else inv_count
+    a.clip_rect, a.linear, a.use_valid, a.dtype = int(clip_rect), int(linear), int(valid is not None), dtype_code(dq)
+    a.loss_kind = LOSS_KINDS[loss_kind]
+    a.deterministic = int(deterministic)
+    _lib.check(lib.vdqn_td_loss_cql(C.byref(a), _ptr(weights), _ptr(err), float(cql_alpha), _ptr(penalty), _stream()), "vdqn_td_loss_cql")
+    return loss, dq, dq32, penalty, err
+
+
 def gt_loss(q_before, act, gt, *, n_cat=5, n_act=3, inv_count=None, value_learning=False):
     lib = _lib.load()
     B, ldq = q_before.shape

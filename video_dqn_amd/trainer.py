@@ -123,6 +123,22 @@ def check_optim(config) -> None:
                  getattr(config, "LR_SCHEDULE", "constant"), getattr(config, "LR_FINAL_FRACTION", 0.0), int(config.NUM_STEPS))
 
 
+def check_cql(config) -> None:
+    """CQL_ALPHA: raise ValueError naming the key (before any device work) for a value that is not a finite number >= 0 and, when it
+    is on, for the configurations the penalty does not cover: the ground-truth branch and a network with one action column."""
+    import math
+    alpha = getattr(config, "CQL_ALPHA", 0.0)
+    if isinstance(alpha, bool) or not isinstance(alpha, (int, float)) or not math.isfinite(alpha) or alpha < 0:
+        raise ValueError(f"CQL_ALPHA must be a finite number >= 0 (0 = off), not {alpha!r}")
+    if alpha > 0:
+        if getattr(config, "TRAIN_ON_GROUND_TRUTH", False):
+            raise ValueError("CQL_ALPHA needs the TD branch: TRAIN_ON_GROUND_TRUTH regresses Q(s, a) on given targets and bootstraps nothing")
+        for key in ("VALUE_LEARNING", "ONE_ACTION"):
+            if getattr(config, key, False):
+                raise ValueError(f"CQL_ALPHA needs more than one action: {key} builds a network with one action column, "
+                                 "where logsumexp_a Q(s, .) - Q(s, a) is identically zero")
+
+
 def _to_device_batch(batch, device, num_classes=5):
     before, after, act, rew, term, gt, valid = batch
     nb = dict(non_blocking=True)
@@ -177,6 +193,8 @@ def run_train(config, resume_from=-1, max_steps=None, rank=0, world_size=1, log=
     aug_actions = getattr(config, "AUG_FLIP_ACTIONS", [1, 2])
     check_augment(aug_pad, aug_flip, aug_actions)
     check_optim(config)
+    check_cql(config)
+    cql_alpha = float(getattr(config, "CQL_ALPHA", 0.0))
     clip_norm, weight_decay = float(getattr(config, "GRAD_CLIP_NORM", 0.0)), float(getattr(config, "WEIGHT_DECAY", 0.0))
     lr_fn = None
     if schedule_active(getattr(config, "LR_WARMUP_STEPS", 0), getattr(config, "LR_SCHEDULE", "constant")):
@@ -299,7 +317,9 @@ def run_train(config, resume_from=-1, max_steps=None, rank=0, world_size=1, log=
                         allreduce=(comm.launch if comm else None), loss_kind=getattr(config, "LOSS_KIND", "l2"),
                         allreduce_loss=(comm.launch_loss if comm else None), allreduce_wait=(comm.wait_last if comm else None),
                         allreduce_errors=((lambda: comm.launch_errors(replay.err_all)) if comm and replay else None),
-                        grad_clip_norm=clip_norm, weight_decay=weight_decay, lr_fn=lr_fn)
+                        grad_clip_norm=clip_norm, weight_decay=weight_decay, lr_fn=lr_fn, cql_alpha=cql_alpha)
+    if cql_alpha > 0:
+        log(f"conservative Q-learning: {cql_alpha:g} * (logsumexp_a Q(s, .) - Q(s, a_data)) added to the TD loss in the loss launch")
     if clip_norm > 0 or weight_decay > 0 or lr_fn is not None:
         log("optimiser:" + (f" gradient clipped to a global norm of {clip_norm:g}" if clip_norm > 0 else "") +
             (f" decoupled weight decay {weight_decay:g}" if weight_decay > 0 else "") +
@@ -370,6 +390,10 @@ def run_train(config, resume_from=-1, max_steps=None, rank=0, world_size=1, log=
     # GRAD_CLIP_NORM: the gradient norm is read back the same way (pinned, two slots, one update late) for the `grad_norm/train` scalar
     host_norm = torch.zeros(2, dtype=torch.float32).pin_memory() if clip_norm > 0 else None
     pending_norm, grad_norm = None, None
+    # CQL_ALPHA: and the penalty, for the `cql_penalty/train` scalar.  This rank's share of the global mean (the kernel divides by the
+    # global batch) times the world size is the mean over its own samples: what rank 0 logs, with no collective
+    host_pen = torch.zeros(2, dtype=torch.float32).pin_memory() if cql_alpha > 0 else None
+    pending_pen, cql_pen = None, None
     loss_stream = None  # N > 1: where the all-reduced loss is waited for and copied to the host
     num_steps = config.NUM_STEPS if max_steps is None else min(config.NUM_STEPS, sample_number + max_steps)
 
@@ -383,6 +407,10 @@ def run_train(config, resume_from=-1, max_steps=None, rank=0, world_size=1, log=
     def consume_norm(p):
         p[1].synchronize()
         return float(host_norm[p[0]])
+
+    def consume_pen(p):
+        p[1].synchronize()
+        return float(host_pen[p[0]]) * world_size
 
     try:  # (the streaming input path owns a thread, pinned buffers and a prefetch stream: released on every exit)
         while sample_number < num_steps:
@@ -434,6 +462,13 @@ def run_train(config, resume_from=-1, max_steps=None, rank=0, world_size=1, log=
                 if pending_norm is not None:  # the previous update's: complete long ago, the GPU is busy with this one
                     grad_norm = (sample_number - 1, consume_norm(pending_norm))
                 pending_norm = (slot, ev_n)
+            if host_pen is not None:
+                host_pen[slot:slot + 1].copy_(stepper.cql_penalty, non_blocking=True)
+                ev_p = torch.cuda.Event()
+                ev_p.record()
+                if pending_pen is not None:
+                    cql_pen = (sample_number - 1, consume_pen(pending_pen))
+                pending_pen = (slot, ev_p)
             log_now = sample_number % 100 == 0 and rank == 0 and hasattr(config, "writer")
             if log_now:  # the reference logs the average INCLUDING this update's loss (:228-238): take it in before writing
                 consume(pending)
@@ -444,6 +479,8 @@ def run_train(config, resume_from=-1, max_steps=None, rank=0, world_size=1, log=
                 config.writer.add_scalar("avg_q_loss/train", running_loss, sample_number)  # :236-238
             if log_now and grad_norm is not None:  # the norm BEFORE clipping, as clip_grad_norm_ returns it; non-finite values show here
                 config.writer.add_scalar("grad_norm/train", grad_norm[1], grad_norm[0])  # (the update it was measured at: one late)
+            if log_now and cql_pen is not None:  # the unscaled penalty of the update one back; avg_q_loss/train is the full objective
+                config.writer.add_scalar("cql_penalty/train", cql_pen[1], cql_pen[0])
             if log_now and replay is not None:
                 config.writer.add_scalar("per/beta", replay.beta(sample_number), sample_number)  # (host arithmetic: nothing read back)
             if sample_number % config.CHECKPOINT_INTERVAL == 0 and rank == 0:  # :241-247
