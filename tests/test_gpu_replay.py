@@ -102,7 +102,8 @@ def _td_inputs(B, seed, ldq=64, n_cat=5, n_act=3):
     return [t.to(DEV) for t in q + [act, rew, term, valid]]
 
 
-def _td(inputs, dtype, loss_kind, use_valid, weight=None, with_err=True, linear=0, clip_rect=1, gamma=0.9):
+def _td(inputs, dtype, loss_kind, use_valid, weight=None, with_err=True, linear=0, clip_rect=1, gamma=0.9, deterministic=1, q_copy=False):
+    """vdqn_td_loss (weight None) or vdqn_td_loss_weighted through the raw ABI -> (loss, dq as f32, dq_f32, err, q_copy) on the CPU."""
     from video_dqn_amd import _lib
     lib = _lib.load()
     qb, qo, qt, act, rew, term, valid = inputs
@@ -117,14 +118,16 @@ def _td(inputs, dtype, loss_kind, use_valid, weight=None, with_err=True, linear=
     a.loss, a.dq, a.dq_f32 = loss.data_ptr(), dq.data_ptr(), dq32.data_ptr()
     a.batch, a.n_cat, a.n_act, a.ldq = B, 5, 3, ldq
     a.gamma, a.inv_count = gamma, 1.0 / (5 * B)
-    a.clip_rect, a.linear, a.use_valid, a.dtype, a.loss_kind, a.deterministic = clip_rect, linear, int(use_valid), dtype, loss_kind, 1
+    a.clip_rect, a.linear, a.use_valid, a.dtype, a.loss_kind, a.deterministic = clip_rect, linear, int(use_valid), dtype, loss_kind, deterministic
+    qc = torch.full((B, 15), -7.0, device=DEV) if q_copy else None
+    a.q_copy = qc.data_ptr() if q_copy else None
     st = torch.cuda.current_stream().cuda_stream
     if weight is None:
         _lib.check(lib.vdqn_td_loss(C.byref(a), st), "vdqn_td_loss")
     else:
         _lib.check(lib.vdqn_td_loss_weighted(C.byref(a), weight.data_ptr(), err.data_ptr() if with_err else None, st), "vdqn_td_loss_weighted")
     torch.cuda.synchronize()
-    return loss.cpu(), dq.float().cpu(), dq32.cpu(), (err.cpu() if with_err else None)
+    return loss.cpu(), dq.float().cpu(), dq32.cpu(), (err.cpu() if with_err else None), (qc.cpu() if q_copy else None)
 
 
 def _td_f64(inputs, loss_kind, use_valid):
@@ -156,7 +159,7 @@ def test_td_loss_weighted(loss_kind, use_valid):
         ones = _td(inputs, dtype, loss_kind, use_valid, weight=torch.ones(B, device=DEV))
         assert torch.equal(ref[0], ones[0]) and torch.equal(ref[1], ones[1]) and torch.equal(ref[2], ones[2])
     w = torch.rand(B, generator=torch.Generator().manual_seed(3)) * 0.9 + 0.1
-    loss, _, dq32, err = _td(inputs, _lib.VDQN_F32, loss_kind, use_valid, weight=w.to(DEV))
+    loss, _, dq32, err, _ = _td(inputs, _lib.VDQN_F32, loss_kind, use_valid, weight=w.to(DEV))
     l, dl, d, vm = _td_f64(inputs, loss_kind, use_valid)
     inv = 1.0 / (5 * B)
     wl = w.double().view(B, 1)
@@ -175,8 +178,9 @@ def test_td_loss_weighted(loss_kind, use_valid):
 
 
 def test_td_loss_weighted_unit_weights_every_target_option():
-    """td_loss_w_kernel states the Double-DQN target once (td_error_of) and td_loss_kernel keeps its own inline copy (its ISA must
-    not move): with w = 1 the two agree bit for bit over every option of the target and the loss, in both dtypes."""
+    """vdqn_td_loss and vdqn_td_loss_weighted launch two instances of one kernel template (plain and weighted) that share the one
+    statement of the Double-DQN target (td_error_of): with w = 1 the two agree bit for bit over every option of the target and the
+    loss, in both dtypes."""
     from video_dqn_amd import _lib
     B = 70
     inputs = _td_inputs(B, 29)
@@ -189,6 +193,65 @@ def test_td_loss_weighted_unit_weights_every_target_option():
                     ref = _td(inputs, dtype, loss_kind, use_valid, **kw)
                     ones = _td(inputs, dtype, loss_kind, use_valid, weight=torch.ones(B, device=DEV), **kw)
                     assert torch.equal(ref[0], ones[0]) and torch.equal(ref[1], ones[1]) and torch.equal(ref[2], ones[2]), (dtype, loss_kind, use_valid, kw)
+
+
+# The plain and the weighted entry at the shapes where the shared element loop and block sum can go wrong: (B, ldq)
+EDGE_SHAPES = [(1, 64),    # one block, one wave, 64 of 256 threads live
+               (5, 64),    # two blocks, the second a quarter full
+               (17, 15),   # no padding columns; 255 elements, one short of a block
+               (16, 16),   # exactly one block, one padding column per row
+               (96, 64)]   # the size the other tests use
+
+
+@pytest.mark.parametrize("B,ldq", EDGE_SHAPES, ids=[f"B{b}_ld{l}" for b, l in EDGE_SHAPES])
+@pytest.mark.parametrize("loss_kind", [0, 1], ids=["l2", "huber"])
+@pytest.mark.parametrize("use_valid", [False, True], ids=["all", "valid"])
+def test_td_loss_plain_and_weighted_edge_shapes(use_valid, loss_kind, B, ldq):
+    """Both entries, both dtypes, against the float64 restatement with test_td_loss_weighted's tolerances (loss 1e-5 relative — an
+    f32 sum of 5 B terms —, dq and err 1e-6 of their largest element); padding columns and non-taken actions of dq exactly 0;
+    q_copy is q_before[:, :15]; a multi-block launch writes the deterministic launch's dq bit for bit and its loss within the same
+    1e-5; the two entries agree bit for bit at w = 1."""
+    from video_dqn_amd import _lib
+    inputs = _td_inputs(B, 11 + loss_kind + 2 * use_valid, ldq=ldq)
+    inputs[0] = inputs[0] * 2.5  # |d| beyond 1: both Huber branches
+    inputs[6][0, 0] = 1.0  # (B = 1: at least one valid term)
+    w = torch.rand(B, generator=torch.Generator().manual_seed(3)) * 0.9 + 0.1
+    l, dl, d, vm = _td_f64(inputs, loss_kind, use_valid)
+    inv = 1.0 / (5 * B)
+    act = inputs[3].cpu()
+    cols = (torch.arange(5).view(1, 5) * 3 + act.view(B, 1))
+    zero = torch.ones(B, ldq, dtype=torch.bool)
+    zero.scatter_(1, cols, False)
+    exp_err = (d.abs() * vm).sum(1) / 5
+    for dtype in (_lib.VDQN_F32, _lib.VDQN_BF16):
+        for weight in (None, torch.ones(B), w):
+            wl = torch.ones(B, 1, dtype=torch.float64) if weight is None else weight.double().view(B, 1)
+            exp_loss, exp_dq = ((l * wl).sum() * inv).item(), dl * wl * inv
+            kw = dict(weight=None if weight is None else weight.to(DEV), q_copy=True)
+            det = _td(inputs, dtype, loss_kind, use_valid, deterministic=1, **kw)
+            free = _td(inputs, dtype, loss_kind, use_valid, deterministic=0, **kw)
+            for name, (loss, dq, dq32, err, qc) in (("deterministic", det), ("multi-block", free)):
+                e_loss = abs(loss.item() - exp_loss) / abs(exp_loss)
+                e_dq = (dq32.double().gather(1, cols) - exp_dq).abs().max().item() / exp_dq.abs().max().item()
+                print(f"dtype {dtype} {name} weight {'none' if weight is None else 'ones' if weight is not w else 'random'}: "
+                      f"loss {e_loss:.2e} relative, dq {e_dq:.2e} of the max element")
+                assert e_loss <= 1e-5 and e_dq <= 1e-6
+                assert torch.all(dq32[zero] == 0) and torch.all(dq[zero] == 0)
+                assert torch.equal(dq, dq32.bfloat16().float() if dtype == _lib.VDQN_BF16 else dq32)
+                assert torch.equal(qc, inputs[0].cpu()[:, :15])
+                if weight is not None:
+                    e_err = (err.double() - exp_err).abs().max().item() / max(exp_err.abs().max().item(), 1e-30)
+                    print(f"  err {e_err:.2e} of the max element")
+                    assert e_err <= 1e-6
+            assert torch.equal(free[1], det[1]) and torch.equal(free[2], det[2])  # dq has no sum in it: only the loss may differ
+            if weight is not None:
+                assert torch.equal(free[3], det[3])
+            if weight is None:
+                plain = det, free
+            elif weight is not w:  # w = 1: the weighted entry is the plain one, bit for bit (the loss where its order is fixed)
+                assert torch.equal(plain[0][0], det[0])
+                for x, y in zip(plain, (det, free)):
+                    assert torch.equal(x[1], y[1]) and torch.equal(x[2], y[2])
 
 
 def _stepper(dtype, B, deterministic=True):

@@ -82,6 +82,7 @@ def main():
     a_ = torch.randint(0, 3, (B,), generator=g).to(dev)
     r_ = (torch.rand(B, 5, generator=g) < 0.3).float().to(dev)
     t_ = (torch.rand(B, 5, generator=g) < 0.2).float().to(dev)
+    w_ = (torch.rand(B, generator=g) * 0.9 + 0.1).to(dev)
     loss, pen = torch.zeros(1, device=dev), torch.zeros(1, device=dev)
     dq = torch.empty(B, 64, dtype=torch.bfloat16, device=dev)
     ta = _lib.TdArgs()
@@ -97,6 +98,7 @@ def main():
             _lib.profile_enable(True)
             for _ in range(50):
                 _lib.check(lib.vdqn_td_loss(C.byref(ta), st), "vdqn_td_loss")
+                _lib.check(lib.vdqn_td_loss_weighted(C.byref(ta), w_.data_ptr(), None, st), "vdqn_td_loss_weighted")
                 _lib.check(lib.vdqn_td_loss_cql(C.byref(ta), None, None, 1.0, pen.data_ptr(), st), "vdqn_td_loss_cql")
             prof = _lib.profile_collect()
             _lib.profile_enable(False)

@@ -109,7 +109,7 @@ __device__ __forceinline__ float mul_rounded(float a, float b) {
 }
 
 // adam_kernel (pointwise.hip) with gs = g * coef in place of g and p * decay in place of p; the three expressions are that kernel's.
-// A kernel of its own rather than a flag on adam_kernel, which keeps the ISA it has (the rule td_loss_w_kernel follows): coef = 1
+// A kernel of its own rather than a flag on adam_kernel, which keeps the ISA it has: coef = 1
 // and decay = 1 give the plain kernel's bits.
 __global__ __launch_bounds__(256) void adam_scaled_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                           float* __restrict__ v, long n, float step_size, float beta1, float beta2,

@@ -272,71 +272,44 @@ __global__ __launch_bounds__(256) void maxpool_bwd_rows_kernel(const T* __restri
 }
 
 // ---------------------------------------------------------------------------------------------------------
+// block sum shared by the loss kernels below
+// ---------------------------------------------------------------------------------------------------------
+// The block's sums of N values per thread, each in one fixed order, come in two steps.  wave_partials (every thread): a shuffle
+// tree per wave, then the waves' partials into red[j][wave] and a barrier.  add_partials (thread 0, inside the branch that uses
+// the sums): red[j][0 .. n_waves) added first to last.  n_waves is the launch's blockDim.x >> 6, 16 at the most; a kernel that is
+// only ever launched with 256 threads passes the literal 4, which unrolls to red[j][0] + red[j][1] + red[j][2] + red[j][3].
+// (Two calls rather than one that hands the sums back: a sum that leaves thread 0's branch reaches the atomic as a per-lane value,
+// and the compiler then adds the lanes' values up in a loop before the atomic instead of issuing it for the one lane.)
+template <int N>
+__device__ __forceinline__ void wave_partials(const float (&mine)[N], float (&red)[N][16]) {
+  float v[N];
+#pragma unroll
+  for (int j = 0; j < N; ++j) v[j] = mine[j];
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1)
+#pragma unroll
+    for (int j = 0; j < N; ++j) v[j] += __shfl_down(v[j], o, 64);
+  if ((threadIdx.x & 63) == 0)
+#pragma unroll
+    for (int j = 0; j < N; ++j) red[j][threadIdx.x >> 6] = v[j];
+  __syncthreads();
+}
+template <int N>
+__device__ __forceinline__ void add_partials(const float (&red)[N][16], int n_waves, float (&sum)[N]) {
+#pragma unroll
+  for (int j = 0; j < N; ++j) sum[j] = red[j][0];
+  for (int w = 1; w < n_waves; ++w)
+#pragma unroll
+    for (int j = 0; j < N; ++j) sum[j] += red[j][w];
+}
+
+// ---------------------------------------------------------------------------------------------------------
 // fused Double-DQN target + TD loss + dQ   (train_q_network.py:134-169,180)
 // one thread per (sample, padded column); loss reduced per block, one atomic per block
 // ---------------------------------------------------------------------------------------------------------
-template <typename T>
-__global__ __launch_bounds__(256) void td_loss_kernel(const vdqn_td_args a) {
-  const int total = a.batch * a.ldq;
-  float my_loss = 0.f;
-  // one element per thread; a deterministic launch is ONE block that walks all elements (fixed summation order)
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
-    const int b = i / a.ldq, col = i - b * a.ldq;
-    float g = 0.f;
-    if (col < a.n_cat * a.n_act) {
-      const int c = col / a.n_act, ac = col - c * a.n_act;
-      const int act = (int)a.act[b];
-      if (a.q_copy) a.q_copy[(size_t)b * (a.n_cat * a.n_act) + col] = a.q_before[(size_t)b * a.ldq + col];
-      if (ac == act) {
-        const float qb = a.q_before[(size_t)b * a.ldq + col];
-        const float* qo = a.q_after_online + (size_t)b * a.ldq + c * a.n_act;
-        int best = 0;
-        float bv = qo[0];
-        for (int k = 1; k < a.n_act; ++k) {
-          const float v = qo[k];
-          if (v > bv) {  // strict: first maximum wins (torch.argmax)
-            bv = v;
-            best = k;
-          }
-        }
-        float qa = a.q_after_target[(size_t)b * a.ldq + c * a.n_act + best];
-        qa = qa * (1.0f - a.term[b * a.n_cat + c]);
-        const float r = a.rew[b * a.n_cat + c];
-        float y = a.linear ? r + (qa - 0.1f) : r + a.gamma * qa;
-        if (a.clip_rect) y = fminf(fmaxf(y, 0.f), 1.f);
-        const float d = qb - y;
-        const float vm = a.use_valid ? a.valid[b * a.n_cat + c] : 1.0f;
-        if (a.loss_kind == 1) {  // Huber, beta = 1 (torch.nn.functional.smooth_l1_loss)
-          const float ad = fabsf(d);
-          my_loss += (ad < 1.0f ? 0.5f * d * d : ad - 0.5f) * vm;
-          g = fminf(fmaxf(d, -1.0f), 1.0f) * vm * a.inv_count;
-        } else {
-          my_loss += 0.5f * d * d * vm;
-          g = d * vm * a.inv_count;
-        }
-      }
-    }
-    if (a.dq) ((T*)a.dq)[i] = from_f32<T>(g);
-    if (a.dq_f32) a.dq_f32[i] = g;
-  }
-  // block reduction of the loss
-  __shared__ float red[4];
-  float v = my_loss;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const float s = red[0] + red[1] + red[2] + red[3];
-    if (s != 0.f) atomicAdd(a.loss, s * a.inv_count);
-  }
-}
-
-// d = Q(s)[b, col] - y for the taken action's column `col` of category c: the Double-DQN target of td_loss_kernel (first
-// arg-max of the online Q(s'), the target network's value there, terminal mask, LINEAR / gamma, rect clip), stated once for the
-// weighted kernel, whose loss terms and per-sample error both take d from here.  (td_loss_kernel keeps its own inline copy: moving
-// it into this helper changes that kernel's register allocation.  tests/test_gpu_replay.py pins the two against each other bit
-// for bit over every target option.)
+// d = Q(s)[b, col] - y for the taken action's column `col` of category c: the Double-DQN target (first arg-max of the online
+// Q(s'), the target network's value there, terminal mask, LINEAR / gamma, rect clip).  The only statement of the target: the loss
+// terms of every mode and the per-sample error take d from here.
 __device__ __forceinline__ float td_error_of(const vdqn_td_args& a, int b, int c, int col) {
   const float qb = a.q_before[(size_t)b * a.ldq + col];
   const float* qo = a.q_after_online + (size_t)b * a.ldq + c * a.n_act;
@@ -357,91 +330,41 @@ __device__ __forceinline__ float td_error_of(const vdqn_td_args& a, int b, int c
   return qb - y;
 }
 
-// The weighted twin of td_loss_kernel (prioritized replay, vdqn_td_loss_weighted): sample b's loss terms and dQ row are scaled by
-// w[b] — before vm, so w = 1 leaves every rounding of td_loss_kernel as it is — and the thread of column 0 writes
-// err[b] = sum_c |d_bc| * valid_bc / n_cat (the raw TD error, whatever the loss kind).  A kernel of its own rather than a template
-// flag on td_loss_kernel: adding a template parameter to that kernel alone already moves its register allocation, and its float
-// and bf16 instances must keep the ISA they have.
-struct td_w_args : vdqn_td_args {
-  const float* w;  // [batch]
+// One kernel for the three entries, MODE chosen at compile time (a run-time flag would put the other modes' loads and registers
+// into every instance).  For sample b and category c, with d = td_error_of, l(d) / dl(d) the half squared error and d, or Huber
+// with beta 1 and its clamp (loss kinds 0 / 1), vm_bc = valid or 1, and a* = act[b]:
+//   TD_PLAIN (vdqn_td_loss)             loss += l * vm                dq[b, c*A+a*] = dl * vm * inv_count
+//   TD_WEIGHTED (vdqn_td_loss_weighted) loss += (l * w_b) * vm        dq[b, c*A+a*] = (dl * w_b) * vm * inv_count
+//     w_b is applied before vm, so w = 1 leaves every rounding of TD_PLAIN as it is.  The thread of column 0 writes
+//     err[b] = sum_c |d_bc| * vm_bc / n_cat (the raw TD error, whatever the loss kind).
+//   TD_CQL (vdqn_td_loss_cql): the discrete conservative Q-learning penalty (Kumar et al., NeurIPS 2020) for training from logged
+//     data only, on top of the loss of train_q_network.py:167,180.  With q = q_before[b, c*A .. c*A+A) in f32:
+//       m      = max_a q_a          sum = sum_a expf(q_a - m)  (a = 0 .. A-1, in that order)          p_a = expf(q_a - m) / sum
+//       pen_bc = logf(sum) + (m - q_{a*})    == logsumexp_a q_a - q_{a*}; the max is subtracted before anything is exponentiated, and
+//                m - q_{a*} is taken before the logarithm is added, so a row such as [1e4, -1e4, 0] loses nothing to the size of m
+//       s_bc   = w_b * vm_bc                                  (w_b = 1 without weights)
+//       loss    += s_bc * (l(d_bc) + alpha * pen_bc)          penalty += s_bc * pen_bc           (not scaled by alpha)
+//       dq[b, c*A+a] = (([a == a*] ? dl(d_bc) : 0) + alpha * (p_a - [a == a*])) * s_bc * inv_count
+//     so dq is dense over the actions of every category, where the other two modes write one column per category.  Each thread of
+//     a category recomputes that category's m and sum from A loads (A is 3 here; the row is in cache), and the thread of the taken
+//     action adds the loss terms.  err[b] stays the raw mean |d| (priorities follow the TD error, not the penalty).
+// The block's sums are multiplied by inv_count and added to a.loss (a.penalty) with one atomic each; padding columns of dq are 0.
+// Launch shapes: 256 threads and one element per thread.  A deterministic launch is ONE block that walks all elements (thread t
+// takes t, t + blockDim.x, ..; the block sum's fixed order): 256 threads for TD_PLAIN and TD_WEIGHTED, 1024 for TD_CQL — a quarter of
+// the serial passes.  __launch_bounds__(1024) is there for that launch alone, and it budgets the TD_CQL instances' 256-thread
+// launches too: 128 VGPRs per thread.  They take 38; should they grow, they have to stay under that.
+enum { TD_PLAIN = 0, TD_WEIGHTED = 1, TD_CQL = 2 };
+struct td_kernel_args : vdqn_td_args {
+  const float* w;  // [batch]; TD_CQL: or NULL (= 1)
   float* err;      // [batch] or NULL
+  float* penalty;  // TD_CQL: f32 scalar or NULL
+  float alpha;     // TD_CQL
 };
-template <typename T>
-__global__ __launch_bounds__(256) void td_loss_w_kernel(const td_w_args a) {
+template <typename T, int MODE>
+__global__ __launch_bounds__(MODE == TD_CQL ? 1024 : 256) void td_loss_kernel(const td_kernel_args a) {
   const int total = a.batch * a.ldq;
-  float my_loss = 0.f;
-  // one element per thread; a deterministic launch is ONE block that walks all elements (fixed summation order)
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
-    const int b = i / a.ldq, col = i - b * a.ldq;
-    float g = 0.f;
-    if (col < a.n_cat * a.n_act) {
-      const int c = col / a.n_act, ac = col - c * a.n_act;
-      const int act = (int)a.act[b];
-      if (a.q_copy) a.q_copy[(size_t)b * (a.n_cat * a.n_act) + col] = a.q_before[(size_t)b * a.ldq + col];
-      if (ac == act) {
-        const float d = td_error_of(a, b, c, col);
-        const float vm = a.use_valid ? a.valid[b * a.n_cat + c] : 1.0f;
-        const float wb = a.w[b];
-        if (a.loss_kind == 1) {  // Huber, beta = 1 (torch.nn.functional.smooth_l1_loss)
-          const float ad = fabsf(d);
-          my_loss += ((ad < 1.0f ? 0.5f * d * d : ad - 0.5f) * wb) * vm;
-          g = (fminf(fmaxf(d, -1.0f), 1.0f) * wb) * vm * a.inv_count;
-        } else {
-          my_loss += (0.5f * d * d * wb) * vm;
-          g = (d * wb) * vm * a.inv_count;
-        }
-      }
-    }
-    if (col == 0 && a.err) {
-      float e = 0.f;
-      for (int c = 0; c < a.n_cat; ++c) e += fabsf(td_error_of(a, b, c, c * a.n_act + (int)a.act[b])) * (a.use_valid ? a.valid[b * a.n_cat + c] : 1.0f);
-      a.err[b] = e / (float)a.n_cat;
-    }
-    if (a.dq) ((T*)a.dq)[i] = from_f32<T>(g);
-    if (a.dq_f32) a.dq_f32[i] = g;
-  }
-  // block reduction of the loss
-  __shared__ float red[4];
-  float v = my_loss;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const float s = red[0] + red[1] + red[2] + red[3];
-    if (s != 0.f) atomicAdd(a.loss, s * a.inv_count);
-  }
-}
-
-// The TD loss with the discrete conservative Q-learning penalty (Kumar et al., NeurIPS 2020; vdqn_td_loss_cql), for training from
-// logged data only (train_q_network.py:167,180 is the loss it extends).  For sample b and category c, with q = q_before[b, c*A ..
-// c*A+A) in f32 and a* = act[b]:
-//   m      = max_a q_a          sum = sum_a expf(q_a - m)  (a = 0 .. A-1, in that order)          p_a = expf(q_a - m) / sum
-//   pen_bc = logf(sum) + (m - q_{a*})    == logsumexp_a q_a - q_{a*}; the max is subtracted before anything is exponentiated, and
-//            m - q_{a*} is taken before the logarithm is added, so a row such as [1e4, -1e4, 0] loses nothing to the size of m
-//   d, l(d), dl(d)  exactly as td_loss_w_kernel (td_error_of; loss kinds 0 / 1)
-//   s_bc   = w_b * vm_bc                                  (w_b = 1 without weights; vm_bc = valid or 1)
-//   loss    += inv_count * sum_bc s_bc * (l(d_bc) + alpha * pen_bc)
-//   penalty += inv_count * sum_bc s_bc * pen_bc           (not scaled by alpha)
-//   dq[b, c*A+a] = (([a == a*] ? dl(d_bc) : 0) + alpha * (p_a - [a == a*])) * s_bc * inv_count;  padding columns 0
-// so dq is dense over the actions of every category, where the two kernels above write one column per category.  err[b] stays
-// the raw mean |d| (priorities follow the TD error, not the penalty).  One thread per (sample, padded column), as above: each
-// thread of a category recomputes that category's m and sum from A loads (A is 3 here; the row is in cache), and the thread of
-// the taken action adds the loss terms.  A third kernel rather than a flag, for the reason td_loss_w_kernel gives.
-// Blocks are 256 threads, or ONE block of 1024 for a deterministic launch: the same fixed order (thread t takes elements t,
-// t + 1024, ..; a shuffle tree per wave; the waves' partial sums added first to last by thread 0) with a quarter of the serial
-// passes of a 256-thread block.  __launch_bounds__(1024) is there for that launch alone, and it budgets the 256-thread launches
-// too: 128 VGPRs per thread.  The kernel takes 38; should it grow, it has to stay under that.
-struct td_cql_args : vdqn_td_args {
-  const float* w;  // [batch] or NULL (= 1)
-  float* err;      // [batch] or NULL
-  float* penalty;  // f32 scalar or NULL
-  float alpha;
-};
-template <typename T>
-__global__ __launch_bounds__(1024) void td_loss_cql_kernel(const td_cql_args a) {
-  const int total = a.batch * a.ldq;
-  float my_loss = 0.f, my_pen = 0.f;
+  constexpr int N_SUMS = MODE == TD_CQL ? 2 : 1;
+  float sums[N_SUMS] = {};  // this thread's loss terms (TD_CQL: and penalty terms)
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
     const int b = i / a.ldq, col = i - b * a.ldq;
     float g = 0.f;
@@ -450,13 +373,15 @@ __global__ __launch_bounds__(1024) void td_loss_cql_kernel(const td_cql_args a) 
       const int act = (int)a.act[b];
       const float* q = a.q_before + (size_t)b * a.ldq + c * a.n_act;
       if (a.q_copy) a.q_copy[(size_t)b * (a.n_cat * a.n_act) + col] = q[ac];
-      float m = q[0];
-      for (int k = 1; k < a.n_act; ++k) m = fmaxf(m, q[k]);
-      float sum = 0.f;
-      for (int k = 0; k < a.n_act; ++k) sum += expf(q[k] - m);
-      const float p = expf(q[ac] - m) / sum;
-      const float vm = a.use_valid ? a.valid[b * a.n_cat + c] : 1.0f;
-      const float s = (a.w ? a.w[b] : 1.0f) * vm;
+      float m = 0.f, sum = 0.f, p = 0.f, s = 0.f;  // TD_CQL only
+      if constexpr (MODE == TD_CQL) {
+        m = q[0];
+        for (int k = 1; k < a.n_act; ++k) m = fmaxf(m, q[k]);
+        for (int k = 0; k < a.n_act; ++k) sum += expf(q[k] - m);
+        p = expf(q[ac] - m) / sum;
+        s = (a.w ? a.w[b] : 1.0f) * (a.use_valid ? a.valid[b * a.n_cat + c] : 1.0f);
+        g = a.alpha * p;
+      }
       if (ac == act) {
         const float d = td_error_of(a, b, c, col);
         float l, dl;
@@ -468,44 +393,41 @@ __global__ __launch_bounds__(1024) void td_loss_cql_kernel(const td_cql_args a) 
           l = 0.5f * d * d;
           dl = d;
         }
-        const float pen = logf(sum) + (m - q[ac]);
-        my_loss += s * (l + a.alpha * pen);
-        my_pen += s * pen;
-        g = dl + a.alpha * (p - 1.0f);
-      } else {
-        g = a.alpha * p;
+        if constexpr (MODE == TD_CQL) {
+          const float pen = logf(sum) + (m - q[ac]);
+          sums[0] += s * (l + a.alpha * pen);
+          sums[1] += s * pen;
+          g = dl + a.alpha * (p - 1.0f);
+        } else {
+          const float vm = a.use_valid ? a.valid[b * a.n_cat + c] : 1.0f;
+          if constexpr (MODE == TD_WEIGHTED) {
+            l *= a.w[b];
+            dl *= a.w[b];
+          }
+          sums[0] += l * vm;
+          g = dl * vm * a.inv_count;
+        }
       }
-      g = g * s * a.inv_count;
+      if constexpr (MODE == TD_CQL) g = g * s * a.inv_count;
     }
-    if (col == 0 && a.err) {
-      float e = 0.f;
-      for (int c = 0; c < a.n_cat; ++c) e += fabsf(td_error_of(a, b, c, c * a.n_act + (int)a.act[b])) * (a.use_valid ? a.valid[b * a.n_cat + c] : 1.0f);
-      a.err[b] = e / (float)a.n_cat;
+    if constexpr (MODE != TD_PLAIN) {
+      if (col == 0 && a.err) {
+        float e = 0.f;
+        for (int c = 0; c < a.n_cat; ++c) e += fabsf(td_error_of(a, b, c, c * a.n_act + (int)a.act[b])) * (a.use_valid ? a.valid[b * a.n_cat + c] : 1.0f);
+        a.err[b] = e / (float)a.n_cat;
+      }
     }
     if (a.dq) ((T*)a.dq)[i] = from_f32<T>(g);
     if (a.dq_f32) a.dq_f32[i] = g;
   }
-  // block reduction of the loss and the penalty: 4 waves, or 16 in the one block of a deterministic launch
-  __shared__ float red[2][16];
-  float v = my_loss, u = my_pen;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    v += __shfl_down(v, o, 64);
-    u += __shfl_down(u, o, 64);
-  }
-  if ((threadIdx.x & 63) == 0) {
-    red[0][threadIdx.x >> 6] = v;
-    red[1][threadIdx.x >> 6] = u;
-  }
-  __syncthreads();
+  __shared__ float red[N_SUMS][16];
+  wave_partials(sums, red);
   if (threadIdx.x == 0) {
-    float sl = 0.f, sp = 0.f;
-    for (int w = 0; w < (int)(blockDim.x >> 6); ++w) {
-      sl += red[0][w];
-      sp += red[1][w];
+    add_partials(red, MODE == TD_CQL ? (int)(blockDim.x >> 6) : 4, sums);
+    if (sums[0] != 0.f) atomicAdd(a.loss, sums[0] * a.inv_count);
+    if constexpr (MODE == TD_CQL) {
+      if (a.penalty && sums[1] != 0.f) atomicAdd(a.penalty, sums[1] * a.inv_count);
     }
-    if (sl != 0.f) atomicAdd(a.loss, sl * a.inv_count);
-    if (a.penalty && sp != 0.f) atomicAdd(a.penalty, sp * a.inv_count);
   }
 }
 
@@ -541,13 +463,13 @@ __global__ __launch_bounds__(256) void gt_loss_kernel(const float* __restrict__ 
     if (dq) dq[i] = from_f32<T>(g);
     if (dq_f32) dq_f32[i] = g;
   }
-  __shared__ float red[4];
-  float v = my_loss;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  if (threadIdx.x == 0) atomicAdd(loss, (red[0] + red[1] + red[2] + red[3]) * inv_count);
+  __shared__ float red[1][16];
+  float sum[1] = {my_loss};
+  wave_partials(sum, red);
+  if (threadIdx.x == 0) {
+    add_partials(red, 4, sum);
+    atomicAdd(loss, sum[0] * inv_count);
+  }
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -729,60 +651,44 @@ extern "C" int vdqn_axpy(float* y, const float* x, float alpha, int64_t n, void*
   return VDQN_OK;
 }
 
-extern "C" int vdqn_td_loss(const vdqn_td_args* a, void* stream) {
-  VDQN_CHECK(a && a->q_before && a->q_after_online && a->q_after_target && a->act && a->rew && a->term && a->loss, "vdqn_td_loss: null arg");
-  VDQN_CHECK(!a->use_valid || a->valid, "vdqn_td_loss: use_valid without valid mask");
-  VDQN_CHECK(a->batch > 0 && a->n_cat > 0 && a->n_act > 0 && a->ldq >= a->n_cat * a->n_act, "vdqn_td_loss: bad dims");
-  VDQN_CHECK(a->dtype == VDQN_F32 || a->dtype == VDQN_BF16, "vdqn_td_loss: bad dtype");
-  VDQN_CHECK(a->loss_kind == 0 || a->loss_kind == 1, "vdqn_td_loss: loss_kind %d (0 = half squared error, 1 = Huber)", a->loss_kind);
+// The three TD-loss entries: every check (each fails by the entry's name before any HIP call), then the one launch.
+template <int MODE>
+static int td_loss_launch(const char* entry, const char* prof_name, const vdqn_td_args* a, const float* weight, float* err_out, float cql_alpha,
+                          float* penalty, void* stream) {
+  VDQN_CHECK(a && a->q_before && a->q_after_online && a->q_after_target && a->act && a->rew && a->term && a->loss && (MODE != TD_WEIGHTED || weight),
+             "%s: null arg", entry);
+  VDQN_CHECK(!a->use_valid || a->valid, "%s: use_valid without valid mask", entry);
+  VDQN_CHECK(a->batch > 0 && a->n_cat > 0 && a->n_act > 0 && a->ldq >= a->n_cat * a->n_act, "%s: bad dims", entry);
+  if (MODE == TD_CQL) VDQN_CHECK(a->n_act >= 2, "%s: n_act is 1: with one action logsumexp_a Q - Q(a) is identically zero; use vdqn_td_loss", entry);
+  VDQN_CHECK(a->dtype == VDQN_F32 || a->dtype == VDQN_BF16, "%s: bad dtype", entry);
+  VDQN_CHECK(a->loss_kind == 0 || a->loss_kind == 1, "%s: loss_kind %d (0 = half squared error, 1 = Huber)", entry, a->loss_kind);
+  if (MODE == TD_CQL)
+    VDQN_CHECK(isfinite(cql_alpha) && cql_alpha > 0.f, "%s: cql_alpha %g must be finite and > 0 (without the penalty: vdqn_td_loss)", entry, (double)cql_alpha);
+  const int threads = MODE == TD_CQL && a->deterministic ? 1024 : 256;
   const int g = a->deterministic ? 1 : (a->batch * a->ldq + 255) / 256;
-  ProfScope ps_("td_loss", 0.0, (double)a->batch * a->ldq * 16.0, (hipStream_t)stream);
-  if (a->dtype == VDQN_BF16) hipLaunchKernelGGL((td_loss_kernel<bf16raw>), dim3(g), dim3(256), 0, (hipStream_t)stream, *a);
-  else hipLaunchKernelGGL((td_loss_kernel<float>), dim3(g), dim3(256), 0, (hipStream_t)stream, *a);
-  VDQN_LAUNCH_CHECK();
-  return VDQN_OK;
-}
-
-extern "C" int vdqn_td_loss_weighted(const vdqn_td_args* a, const float* weight, float* err_out, void* stream) {
-  VDQN_CHECK(a && a->q_before && a->q_after_online && a->q_after_target && a->act && a->rew && a->term && a->loss && weight,
-             "vdqn_td_loss_weighted: null arg");
-  VDQN_CHECK(!a->use_valid || a->valid, "vdqn_td_loss_weighted: use_valid without valid mask");
-  VDQN_CHECK(a->batch > 0 && a->n_cat > 0 && a->n_act > 0 && a->ldq >= a->n_cat * a->n_act, "vdqn_td_loss_weighted: bad dims");
-  VDQN_CHECK(a->dtype == VDQN_F32 || a->dtype == VDQN_BF16, "vdqn_td_loss_weighted: bad dtype");
-  VDQN_CHECK(a->loss_kind == 0 || a->loss_kind == 1, "vdqn_td_loss_weighted: loss_kind %d (0 = half squared error, 1 = Huber)", a->loss_kind);
-  const int g = a->deterministic ? 1 : (a->batch * a->ldq + 255) / 256;
-  ProfScope ps_("td_loss_w", 0.0, (double)a->batch * a->ldq * 16.0 + (double)a->batch * 8.0, (hipStream_t)stream);
-  td_w_args k;
-  static_cast<vdqn_td_args&>(k) = *a;
-  k.w = weight;
-  k.err = err_out;
-  if (a->dtype == VDQN_BF16) hipLaunchKernelGGL((td_loss_w_kernel<bf16raw>), dim3(g), dim3(256), 0, (hipStream_t)stream, k);
-  else hipLaunchKernelGGL((td_loss_w_kernel<float>), dim3(g), dim3(256), 0, (hipStream_t)stream, k);
-  VDQN_LAUNCH_CHECK();
-  return VDQN_OK;
-}
-
-extern "C" int vdqn_td_loss_cql(const vdqn_td_args* a, const float* weight, float* err_out, float cql_alpha, float* penalty, void* stream) {
-  VDQN_CHECK(a && a->q_before && a->q_after_online && a->q_after_target && a->act && a->rew && a->term && a->loss, "vdqn_td_loss_cql: null arg");
-  VDQN_CHECK(!a->use_valid || a->valid, "vdqn_td_loss_cql: use_valid without valid mask");
-  VDQN_CHECK(a->batch > 0 && a->n_cat > 0 && a->n_act > 0 && a->ldq >= a->n_cat * a->n_act, "vdqn_td_loss_cql: bad dims");
-  VDQN_CHECK(a->n_act >= 2, "vdqn_td_loss_cql: n_act is 1: with one action logsumexp_a Q - Q(a) is identically zero; use vdqn_td_loss");
-  VDQN_CHECK(a->dtype == VDQN_F32 || a->dtype == VDQN_BF16, "vdqn_td_loss_cql: bad dtype");
-  VDQN_CHECK(a->loss_kind == 0 || a->loss_kind == 1, "vdqn_td_loss_cql: loss_kind %d (0 = half squared error, 1 = Huber)", a->loss_kind);
-  VDQN_CHECK(isfinite(cql_alpha) && cql_alpha > 0.f, "vdqn_td_loss_cql: cql_alpha %g must be finite and > 0 (without the penalty: vdqn_td_loss)", (double)cql_alpha);
-  const int threads = a->deterministic ? 1024 : 256;
-  const int g = a->deterministic ? 1 : (a->batch * a->ldq + 255) / 256;
-  ProfScope ps_("td_loss_cql", 0.0, (double)a->batch * a->ldq * 16.0 + (double)a->batch * 8.0, (hipStream_t)stream);
-  td_cql_args k;
+  ProfScope ps_(prof_name, 0.0, (double)a->batch * a->ldq * 16.0 + (MODE == TD_PLAIN ? 0.0 : (double)a->batch * 8.0), (hipStream_t)stream);
+  td_kernel_args k;
   static_cast<vdqn_td_args&>(k) = *a;
   k.w = weight;
   k.err = err_out;
   k.penalty = penalty;
   k.alpha = cql_alpha;
-  if (a->dtype == VDQN_BF16) hipLaunchKernelGGL((td_loss_cql_kernel<bf16raw>), dim3(g), dim3(threads), 0, (hipStream_t)stream, k);
-  else hipLaunchKernelGGL((td_loss_cql_kernel<float>), dim3(g), dim3(threads), 0, (hipStream_t)stream, k);
+  if (a->dtype == VDQN_BF16) hipLaunchKernelGGL((td_loss_kernel<bf16raw, MODE>), dim3(g), dim3(threads), 0, (hipStream_t)stream, k);
+  else hipLaunchKernelGGL((td_loss_kernel<float, MODE>), dim3(g), dim3(threads), 0, (hipStream_t)stream, k);
   VDQN_LAUNCH_CHECK();
   return VDQN_OK;
+}
+
+extern "C" int vdqn_td_loss(const vdqn_td_args* a, void* stream) {
+  return td_loss_launch<TD_PLAIN>("vdqn_td_loss", "td_loss", a, nullptr, nullptr, 0.f, nullptr, stream);
+}
+
+extern "C" int vdqn_td_loss_weighted(const vdqn_td_args* a, const float* weight, float* err_out, void* stream) {
+  return td_loss_launch<TD_WEIGHTED>("vdqn_td_loss_weighted", "td_loss_w", a, weight, err_out, 0.f, nullptr, stream);
+}
+
+extern "C" int vdqn_td_loss_cql(const vdqn_td_args* a, const float* weight, float* err_out, float cql_alpha, float* penalty, void* stream) {
+  return td_loss_launch<TD_CQL>("vdqn_td_loss_cql", "td_loss_cql", a, weight, err_out, cql_alpha, penalty, stream);
 }
 
 extern "C" int vdqn_gt_loss(const float* q_before, const int64_t* act, const float* gt, float* loss, void* dq, float* dq_f32, int32_t batch,

@@ -168,40 +168,12 @@ def stem_wgrad_pool(g_pool: torch.Tensor, idx: torch.Tensor, t_in: torch.Tensor,
 LOSS_KINDS = {"l2": 0, "huber": 1}  # vdqn_td_args.loss_kind
 
 
-def td_loss(q_before, q_after_online, q_after_target, act, rew, term, valid=None, *, n_cat=5, n_act=3, gamma=0.99,
-            inv_count=None, clip_rect=True, linear=False, out_dtype=torch.float32, loss_kind="l2"):
-    """q_*: f32 [B, ldq] (ldq >= n_cat*n_act).  Returns (loss[1], dq[B, ldq] out_dtype, dq_f32)."""
-    lib = _lib.load()
+def _td_args(q_before, q_after_online, q_after_target, act, rew, term, valid, n_cat, n_act, gamma, inv_count, clip_rect, linear, out_dtype,
+             loss_kind, deterministic=False):
+    """-> (TdArgs, loss[1], dq[B, ldq] out_dtype, dq_f32): the argument struct of the three TD-loss entries and the outputs it points to."""
     B, ldq = q_before.shape
     dev = q_before.device
     loss = torch.zeros(1, dtype=torch.float32, device=dev)
-    dq = torch.empty((B, ldq), dtype=out_dtype, device=dev)
-    dq32 = torch.empty((B, ldq), dtype=torch.float32, device=dev)
-    a = _lib.TdArgs()
-    a.q_before, a.q_after_online, a.q_after_target = _ptr(q_before), _ptr(q_after_online), _ptr(q_after_target)
-    a.act, a.rew, a.term, a.valid = _ptr(act), _ptr(rew), _ptr(term), _ptr(valid)
-    a.loss, a.dq, a.dq_f32 = _ptr(loss), _ptr(dq), _ptr(dq32)
-    a.batch, a.n_cat, a.n_act, a.ldq = B, n_cat, n_act, ldq
-    a.gamma = gamma
-    a.inv_count = (1.0 / (B * n_cat)) if inv_count is None else inv_count
-    a.clip_rect, a.linear, a.use_valid, a.dtype = int(clip_rect), int(linear), int(valid is not None), dtype_code(dq)
-    a.loss_kind = LOSS_KINDS[loss_kind]
-    _lib.check(lib.vdqn_td_loss(C.byref(a), _stream()), "vdqn_td_loss")
-    return loss, dq, dq32
-
-
-def td_loss_cql(q_before, q_after_online, q_after_target, act, rew, term, valid=None, *, cql_alpha, weights=None, with_err=False,
-                n_cat=5, n_act=3, gamma=0.99, inv_count=None, clip_rect=True, linear=False, out_dtype=torch.float32, loss_kind="l2",
-                deterministic=False):
-    """td_loss with the conservative Q-learning penalty (vdqn_td_loss_cql): cql_alpha * (logsumexp_a Q(s, .) - Q(s, act)) per sample
-    and category, dq dense over the actions.  weights: optional f32 [B].  Returns (loss[1], dq[B, ldq] out_dtype, dq_f32,
-    penalty[1], err[B] or None)."""
-    lib = _lib.load()
-    B, ldq = q_before.shape
-    dev = q_before.device
-    loss = torch.zeros(1, dtype=torch.float32, device=dev)
-    penalty = torch.zeros(1, dtype=torch.float32, device=dev)
-    err = torch.empty(B, dtype=torch.float32, device=dev) if with_err else None
     dq = torch.empty((B, ldq), dtype=out_dtype, device=dev)
     dq32 = torch.empty((B, ldq), dtype=torch.float32, device=dev)
     a = _lib.TdArgs()
@@ -214,6 +186,30 @@ def td_loss_cql(q_before, q_after_online, q_after_target, act, rew, term, valid=
     a.clip_rect, a.linear, a.use_valid, a.dtype = int(clip_rect), int(linear), int(valid is not None), dtype_code(dq)
     a.loss_kind = LOSS_KINDS[loss_kind]
     a.deterministic = int(deterministic)
+    return a, loss, dq, dq32
+
+
+def td_loss(q_before, q_after_online, q_after_target, act, rew, term, valid=None, *, n_cat=5, n_act=3, gamma=0.99,
+            inv_count=None, clip_rect=True, linear=False, out_dtype=torch.float32, loss_kind="l2"):
+    """q_*: f32 [B, ldq] (ldq >= n_cat*n_act).  Returns (loss[1], dq[B, ldq] out_dtype, dq_f32)."""
+    lib = _lib.load()
+    a, loss, dq, dq32 = _td_args(q_before, q_after_online, q_after_target, act, rew, term, valid, n_cat, n_act, gamma, inv_count, clip_rect,
+                                 linear, out_dtype, loss_kind)
+    _lib.check(lib.vdqn_td_loss(C.byref(a), _stream()), "vdqn_td_loss")
+    return loss, dq, dq32
+
+
+def td_loss_cql(q_before, q_after_online, q_after_target, act, rew, term, valid=None, *, cql_alpha, weights=None, with_err=False,
+                n_cat=5, n_act=3, gamma=0.99, inv_count=None, clip_rect=True, linear=False, out_dtype=torch.float32, loss_kind="l2",
+                deterministic=False):
+    """td_loss with the conservative Q-learning penalty (vdqn_td_loss_cql): cql_alpha * (logsumexp_a Q(s, .) - Q(s, act)) per sample
+    and category, dq dense over the actions.  weights: optional f32 [B].  Returns (loss[1], dq[B, ldq] out_dtype, dq_f32,
+    penalty[1], err[B] or None)."""
+    lib = _lib.load()
+    a, loss, dq, dq32 = _td_args(q_before, q_after_online, q_after_target, act, rew, term, valid, n_cat, n_act, gamma, inv_count, clip_rect,
+                                 linear, out_dtype, loss_kind, deterministic)
+    penalty = torch.zeros(1, dtype=torch.float32, device=loss.device)
+    err = torch.empty(q_before.shape[0], dtype=torch.float32, device=loss.device) if with_err else None
     _lib.check(lib.vdqn_td_loss_cql(C.byref(a), _ptr(weights), _ptr(err), float(cql_alpha), _ptr(penalty), _stream()), "vdqn_td_loss_cql")
     return loss, dq, dq32, penalty, err
 

@@ -187,6 +187,38 @@ class DevicePrefetcher:
         return dev_batch
 
 
+class LateScalar:
+    """A device f32 scalar read on the host one update late: push() queues a copy into one of two pinned slots and an event behind
+    it, waits for nothing, and hands back what the push before it queued — complete long ago, the GPU is busy with this update."""
+
+    def __init__(self):
+        self.host = torch.zeros(2, dtype=torch.float32).pin_memory()
+        self.pending = None  # (slot, event, update number) of the copy not read yet
+
+    def push(self, src, number, stream=None, wait=None):
+        """Queue the copy of update `number`'s value (on `stream`, behind wait(), when given: neither touches the compute stream).
+        -> take() of the push before."""
+        slot = number & 1
+        ev = torch.cuda.Event()
+        with torch.cuda.stream(stream):  # (None: the current stream)
+            if wait is not None:
+                wait()
+            self.host[slot:slot + 1].copy_(src, non_blocking=True)
+            ev.record()
+        before = self.take()
+        self.pending = (slot, ev, number)
+        return before
+
+    def take(self):
+        """-> (update number, value) of the pending copy once it has landed, None when there is none."""
+        if self.pending is None:
+            return None
+        slot, ev, number = self.pending
+        self.pending = None
+        ev.synchronize()
+        return number, float(self.host[slot])
+
+
 def run_train(config, resume_from=-1, max_steps=None, rank=0, world_size=1, log=print):
     """train_q_network.py:84-250."""
     aug_pad, aug_flip = getattr(config, "AUG_SHIFT_PAD", 0), getattr(config, "AUG_FLIP", False)
@@ -385,32 +417,20 @@ def run_train(config, resume_from=-1, max_steps=None, rank=0, world_size=1, log=
         iterator = store.prioritized_batches(replay, sample_number)
 
     running_loss = None
-    host_loss = torch.zeros(2, dtype=torch.float32).pin_memory()
-    pending = None  # (slot, event) of the previous step's loss copy
-    # GRAD_CLIP_NORM: the gradient norm is read back the same way (pinned, two slots, one update late) for the `grad_norm/train` scalar
-    host_norm = torch.zeros(2, dtype=torch.float32).pin_memory() if clip_norm > 0 else None
-    pending_norm, grad_norm = None, None
+    late_loss = LateScalar()
+    # GRAD_CLIP_NORM: the gradient norm is read back the same way for the `grad_norm/train` scalar
+    late_norm, grad_norm = (LateScalar() if clip_norm > 0 else None), None
     # CQL_ALPHA: and the penalty, for the `cql_penalty/train` scalar.  This rank's share of the global mean (the kernel divides by the
     # global batch) times the world size is the mean over its own samples: what rank 0 logs, with no collective
-    host_pen = torch.zeros(2, dtype=torch.float32).pin_memory() if cql_alpha > 0 else None
-    pending_pen, cql_pen = None, None
+    late_pen, cql_pen = (LateScalar() if cql_alpha > 0 else None), None
     loss_stream = None  # N > 1: where the all-reduced loss is waited for and copied to the host
     num_steps = config.NUM_STEPS if max_steps is None else min(config.NUM_STEPS, sample_number + max_steps)
 
-    def consume(p):
+    def average(taken):
         nonlocal running_loss
-        slot, ev = p
-        ev.synchronize()
-        v = float(host_loss[slot])
-        running_loss = v if running_loss is None else running_loss * 0.99 + v * 0.01  # :228-231
-
-    def consume_norm(p):
-        p[1].synchronize()
-        return float(host_norm[p[0]])
-
-    def consume_pen(p):
-        p[1].synchronize()
-        return float(host_pen[p[0]]) * world_size
+        if taken is not None:
+            v = taken[1]
+            running_loss = v if running_loss is None else running_loss * 0.99 + v * 0.01  # :228-231
 
     try:  # (the streaming input path owns a thread, pinned buffers and a prefetch stream: released on every exit)
         while sample_number < num_steps:
@@ -438,41 +458,21 @@ def run_train(config, resume_from=-1, max_steps=None, rank=0, world_size=1, log=
             # copied to the host on the read-back stream only — the compute stream, i.e. the next update's first kernel, never
             # waits for it — so the average that is printed, logged and returned is still the reference's: an EMA of the true
             # global batch-mean loss, one update late like the single-process read-back
-            slot = sample_number & 1
-            ev = torch.cuda.Event()
             reduced = comm.take_loss() if comm is not None else None
             if reduced is not None:
                 buf, work = reduced
                 if loss_stream is None:
                     loss_stream = torch.cuda.Stream(device=model.engine.device)
-                with torch.cuda.stream(loss_stream):
-                    work.wait()
-                    host_loss[slot:slot + 1].copy_(buf, non_blocking=True)
-                    ev.record(loss_stream)
+                average(late_loss.push(buf, sample_number, stream=loss_stream, wait=work.wait))
             else:
-                host_loss[slot:slot + 1].copy_(loss, non_blocking=True)
-                ev.record()
-            if pending is not None:
-                consume(pending)
-            pending = (slot, ev)
-            if host_norm is not None:
-                host_norm[slot:slot + 1].copy_(stepper.clip_out[:1], non_blocking=True)
-                ev_n = torch.cuda.Event()
-                ev_n.record()
-                if pending_norm is not None:  # the previous update's: complete long ago, the GPU is busy with this one
-                    grad_norm = (sample_number - 1, consume_norm(pending_norm))
-                pending_norm = (slot, ev_n)
-            if host_pen is not None:
-                host_pen[slot:slot + 1].copy_(stepper.cql_penalty, non_blocking=True)
-                ev_p = torch.cuda.Event()
-                ev_p.record()
-                if pending_pen is not None:
-                    cql_pen = (sample_number - 1, consume_pen(pending_pen))
-                pending_pen = (slot, ev_p)
+                average(late_loss.push(loss, sample_number))
+            if late_norm is not None:
+                grad_norm = late_norm.push(stepper.clip_out[:1], sample_number) or grad_norm  # (update number, norm): one late
+            if late_pen is not None:
+                cql_pen = late_pen.push(stepper.cql_penalty, sample_number) or cql_pen
             log_now = sample_number % 100 == 0 and rank == 0 and hasattr(config, "writer")
             if log_now:  # the reference logs the average INCLUDING this update's loss (:228-238): take it in before writing
-                consume(pending)
-                pending = None
+                average(late_loss.take())
             if rank == 0 and running_loss is not None:
                 print(f"\rbatch:{sample_number}/{config.NUM_STEPS} avg_loss: {running_loss}", end="")
             if log_now and running_loss is not None:
@@ -480,15 +480,14 @@ def run_train(config, resume_from=-1, max_steps=None, rank=0, world_size=1, log=
             if log_now and grad_norm is not None:  # the norm BEFORE clipping, as clip_grad_norm_ returns it; non-finite values show here
                 config.writer.add_scalar("grad_norm/train", grad_norm[1], grad_norm[0])  # (the update it was measured at: one late)
             if log_now and cql_pen is not None:  # the unscaled penalty of the update one back; avg_q_loss/train is the full objective
-                config.writer.add_scalar("cql_penalty/train", cql_pen[1], cql_pen[0])
+                config.writer.add_scalar("cql_penalty/train", cql_pen[1] * world_size, cql_pen[0])
             if log_now and replay is not None:
                 config.writer.add_scalar("per/beta", replay.beta(sample_number), sample_number)  # (host arithmetic: nothing read back)
             if sample_number % config.CHECKPOINT_INTERVAL == 0 and rank == 0:  # :241-247
                 torch.cuda.synchronize()
                 save_checkpoint(f"{config.folder}/models/sample{sample_number}.torch", sample_number, model, stepper,
                                 replay_state=(replay.state_dict() if replay is not None else None))
-        if pending is not None:
-            consume(pending)
+        average(late_loss.take())
         torch.cuda.synchronize()
     finally:
         if stream is not None:
