@@ -276,9 +276,29 @@ int vdqn_grad_sumsq(const float* g, int64_t n, void* workspace, int32_t slot, vo
 int vdqn_clip_finalize(const void* workspace, int32_t n_ranges, double max_norm, float* out, void* stream);
 /* torch.optim.AdamW step on gradients scaled by a device-side coefficient (the multiply clip_grad_norm_ does in place):
  *   gs = g * coef[0] (coef == NULL: 1);  p = p * (1 - lr * weight_decay);  then vdqn_adam's update with gs for g.
- * With coef[0] == 1 and weight_decay == 0 it writes vdqn_adam's bits.  g itself is left as it is. */
+ * With coef[0] == 1 and weight_decay == 0 it writes vdqn_adam's bits — in the scalar tail (the n % 4 last elements) because the
+ * exp_avg multiply-add is written out there the way vdqn_adam's tail has it (optim.hip tail_moment).  g itself is left as it is. */
 int vdqn_adam_scaled(float* p, const float* g, float* m, float* v, int64_t n, int32_t step, double lr, double beta1,
                      double beta2, double eps, double weight_decay, const float* coef, void* stream);
+
+/* Soft (Polyak) target update over one flat f32 range, target <- target + tau (p - target): what a DQN loop does after every
+ * optimiser step in place of the hard copy every TARGET_UPDATE_INTERVAL updates.  The arithmetic is torch.lerp's two-branch rule
+ * with every product rounded to f32 on its own (nothing contracted into a fused multiply-add), per element:
+ *   d = p - t                                     (rounded)
+ *   tau <  0.5:  t' = t + tau_f * d               tau_f = (float)tau; the product is rounded, then the sum
+ *   tau >= 0.5:  t' = p - d * omt_f               omt_f = (float)(1.0 - tau), the difference formed in double
+ * so tau = 1 writes p's bits, p == t leaves t's bits, and three lines of numpy float32 reproduce it bit for bit
+ * (tests/polyak_oracle.py lerp_f32).  n >= 1, both pointers 16-byte aligned (float4 body, scalar tail), the two ranges disjoint,
+ * tau finite in (0, 1]; anything else fails by name before a launch. */
+int vdqn_polyak(float* target, const float* p, int64_t n, double tau, void* stream);
+/* vdqn_adam_scaled and vdqn_polyak in one launch: p, m, v are updated by vdqn_adam_scaled's expressions (coef == NULL and
+ * weight_decay == 0: vdqn_adam's bits), then the new p, still in registers, is lerped into target[0, n) by the rule above — one
+ * more read and one more write of `target` per element, where a second launch would stream p a third time.  Arguments as
+ * vdqn_adam_scaled's; target 16-byte aligned like the others, its range disjoint from theirs (refused by name otherwise); tau finite
+ * in (0, 1]. */
+int vdqn_adam_polyak(float* p, const float* g, float* m, float* v, int64_t n, int32_t step, double lr, double beta1,
+                     double beta2, double eps, double weight_decay, const float* coef /* NULL = 1 */,
+                     float* target, double tau, void* stream);
 
 /* torch.nn.BatchNorm2d in train mode over an NHWC conv output y[n_img][hw][c] (ARCHITECTURE='basic':
  * archs/HabitatDQNMultiAction.py:32-34,37-40 keeps the ResNet in train mode).  Images are sample-major, frame-minor;

@@ -147,6 +147,9 @@ _SIGS = {
     "vdqn_adam_scaled": (C.c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i32, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, c_vp, c_vp]),
     "vdqn_td_loss_cql": (C.c_int, [C.POINTER(TdArgs), c_vp, c_vp, c_f32, c_vp, c_vp]),
     "vdqn_net_td_forward_cql": (C.c_int, [c_vp, C.POINTER(StepArgs), c_f32, c_vp, c_vp]),
+    "vdqn_polyak": (C.c_int, [c_vp, c_vp, c_i64, C.c_double, c_vp]),
+    "vdqn_adam_polyak": (C.c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i32, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, c_vp,
+                                   c_vp, C.c_double, c_vp]),
 }
 COMM_UID_BYTES = 128
 EXPORTS = tuple(_SIGS)

@@ -36,7 +36,12 @@ the warm-up the rate goes from LEARNING_RATE to LEARNING_RATE * LR_FINAL_FRACTIO
 (NUM_STEPS - W), 0, 1); cosine is f + (1 - f) * (1 + cos(pi * progress)) / 2), LR_FINAL_FRACTION (0.0), CQL_ALPHA (0.0 = off; > 0:
 conservative Q-learning for training from logged data, Kumar et al. 2020 — CQL_ALPHA * (logsumexp_a Q(s, .) - Q(s, a_data)), averaged
 like the TD loss, is added to it inside the loss launch on the GPU, which pulls down the values of actions the data never shows;
-1.0 is the usual discrete setting; the TD branch with more than one action column only).
+1.0 is the usual discrete setting; the TD branch with more than one action column only), TARGET_TAU (0.0 = off, the reference's hard
+target copy every TARGET_UPDATE_INTERVAL updates; in (0, 1]: soft / Polyak target updates — after every optimiser step the target
+weights move as target <- target + TARGET_TAU * (online - target), inside the Adam launch on the GPU, in an f32 copy of all
+parameters from which the target network's weights are folded in front of every update; TARGET_UPDATE_INTERVAL is then unused;
+BatchNorm running statistics are copied from the online network, not averaged; 0.005 is the usual setting; the checkpoint gains
+`target_state_dict`; the TD branch only).
 """
 from __future__ import annotations
 
@@ -172,6 +177,7 @@ def get_cfg_defaults() -> CfgNode:
     c.LR_SCHEDULE = "constant"    # 'constant' | 'linear' | 'cosine': from LEARNING_RATE to LEARNING_RATE * LR_FINAL_FRACTION at NUM_STEPS
     c.LR_FINAL_FRACTION = 0.0
     c.CQL_ALPHA = 0.0             # > 0: conservative Q-learning penalty CQL_ALPHA * (logsumexp_a Q(s, .) - Q(s, a_data)) in the loss launch; 0 = off
+    c.TARGET_TAU = 0.0            # in (0, 1]: soft target updates target <- target + TARGET_TAU * (online - target) after every optimiser step; 0 = hard copies
     return c
 
 

@@ -287,13 +287,20 @@ class TDStepper:
     """Device state of the training loop: target-network weights, Adam moments, workspaces, and one TD update.
 
     ``step()`` follows train_q_network.py:213-227: target sync check (before the update), forward x3 (the two
-    online passes run as one 2B batch), Double-DQN target + loss, backward, Adam."""
+    online passes run as one 2B batch), Double-DQN target + loss, backward, Adam.
+
+    target_tau > 0 replaces the hard target copy by the soft update target <- target + tau (online - target) after every optimiser
+    step: `target_params` (f32, all of `net.params`) is updated inside the Adam launches and folded into `packed_target` in front of
+    every update; target_update_interval is then unused.  BatchNorm running statistics are copied from the online network, not
+    averaged: the fold uses the online `bnstats` as they stand (constant in extra_capacity; in 'basic', those of the previous
+    update)."""
 
     def __init__(self, net: NetEngine, batch: int, lr: float, gamma: float, clip_rect: bool, linear: bool = False,
                  remove_before_reward: bool = False, train_on_ground_truth: bool = False, value_learning: bool = False,
                  target_update_interval: int = 8000, betas=(0.9, 0.999), eps: float = 1e-8, world_size: int = 1,
                  allreduce=None, loss_kind: str = "l2", allreduce_loss=None, allreduce_wait=None, allreduce_errors=None,
-                 grad_clip_norm: float = 0.0, weight_decay: float = 0.0, lr_fn=None, cql_alpha: float = 0.0):
+                 grad_clip_norm: float = 0.0, weight_decay: float = 0.0, lr_fn=None, cql_alpha: float = 0.0,
+                 target_tau: float = 0.0):
         net._need_gpu()
         self.net, self.B = net, batch
         self.lib = net.lib
@@ -328,6 +335,20 @@ class TDStepper:
         if cql_alpha > 0 and net.action_dim < 2:
             raise _lib.VdqnError("TDStepper: cql_alpha needs action_dim >= 2 (with one action the penalty is identically zero)")
         self.cql_alpha = cql_alpha
+        # target_tau > 0 (soft / Polyak target updates): `target_params`, an f32 copy of the whole flat `net.params` (the trainable
+        # prefix and the frozen resnet.fc tail), follows the online weights as target <- target + tau (params - target) inside every
+        # Adam launch (vdqn_adam_polyak), and `packed_target` is folded from it in front of every update; target_update_interval is
+        # not consulted.  The averaged weights live in f32 there, never in `packed_target`: a bf16 packed weight cannot hold an
+        # increment of half a percent.  BatchNorm running statistics are copied, not averaged (as stable-baselines3's polyak_update
+        # treats buffers): the fold takes the online `bnstats` as they stand — in extra_capacity they never change, in 'basic' they
+        # are those the previous update left.  0: none of this exists — no allocation, no launch, the same bits.
+        target_tau = float(target_tau)
+        if not (0.0 <= target_tau <= 1.0):  # (a NaN fails both comparisons)
+            raise _lib.VdqnError(f"TDStepper: target_tau must be a finite number in [0, 1] (0 = hard target copies), not {target_tau}")
+        if target_tau > 0 and train_on_ground_truth:
+            raise _lib.VdqnError("TDStepper: target_tau applies to the TD branch only (train_on_ground_truth has no target network)")
+        self.target_tau = target_tau
+        self.target_params = None
         self.tui = target_update_interval
         self.world_size = world_size
         self.allreduce = allreduce  # callable(tensor_slice, stage) or None
@@ -364,6 +385,8 @@ class TDStepper:
             if self.grad_clip_norm > 0:
                 self.clip_ws = torch.zeros(self.lib.vdqn_clip_workspace_bytes(3) // 8, dtype=torch.float64, device=dev)
                 self.clip_out = torch.zeros(2, dtype=torch.float32, device=dev)
+            if self.target_tau > 0:
+                self.target_params = torch.empty_like(net.params)
         self.adam_step = 0
         self.sample_number = 0
         self._grad_stream = None  # torch view of the engine's side stream (vdqn_net_grad_stream)
@@ -377,8 +400,15 @@ class TDStepper:
 
     def sync_target(self):
         """target_net.load_state_dict(model.state_dict()) (train_q_network.py:121,208,216): the target network
-        only ever runs forward, so its state is the packed (BN-folded) copy of the current online weights."""
+        only ever runs forward, so its state is the packed (BN-folded) copy of the current online weights.
+
+        With target_tau > 0 the copy goes into `target_params` (all of `net.params`, the frozen tail included), and the packed copy
+        is made from there with the online BatchNorm statistics."""
         with torch.cuda.device(self.net.device):
+            if self.target_params is not None:
+                self.target_params.copy_(self.net.params)
+                self.net.pack_weights(self.packed_target, with_dgrad=False, params=self.target_params)
+                return
             self.net.pack_weights(self.packed_target, with_dgrad=False)
 
     def _args(self, before, after, src_kind, act, rew, term, valid, gt, weights=None, td_error=None, augment=None) -> _lib.StepArgs:
@@ -554,6 +584,16 @@ class TDStepper:
     def _adam_range(self, b: int, e: int, step: int):
         """Adam (train_q_network.py:227) over the flat element range [b, e) on the current stream."""
         n = self.net
+        if self.target_params is not None:
+            # the soft target update rides in the Adam launch, wherever that is queued (optimizer_step, the early launches on the
+            # gradient stream, the per-bucket ones on `_post_stream`): there is no window in which `params` has moved and
+            # `target_params` has not, and whatever orders one array's writes orders the other's
+            coef = self.clip_out.data_ptr() + 4 if self.grad_clip_norm > 0 else None
+            _lib.check(self.lib.vdqn_adam_polyak(n.params.data_ptr() + 4 * b, self.grads.data_ptr() + 4 * b, self.exp_avg.data_ptr() + 4 * b,
+                                                 self.exp_avg_sq.data_ptr() + 4 * b, e - b, step, self.lr, self.betas[0], self.betas[1],
+                                                 self.eps, self.weight_decay, coef, self.target_params.data_ptr() + 4 * b, self.target_tau,
+                                                 _stream()), "vdqn_adam_polyak")
+            return
         if self.grad_clip_norm > 0 or self.weight_decay != 0:
             coef = self.clip_out.data_ptr() + 4 if self.grad_clip_norm > 0 else None
             _lib.check(self.lib.vdqn_adam_scaled(n.params.data_ptr() + 4 * b, self.grads.data_ptr() + 4 * b, self.exp_avg.data_ptr() + 4 * b,
@@ -625,7 +665,16 @@ class TDStepper:
                 if t is not None and (t.dtype != torch.float32 or t.numel() != self.B or not t.is_contiguous() or not t.is_cuda):
                     raise _lib.VdqnError(f"TDStepper.step: {name} must be a contiguous f32 [{self.B}] device tensor")
         self.sample_number += 1
-        if self.sample_number % self.tui == 0:
+        if self.target_params is not None:
+            # Soft target: fold `packed_target` from the averaged weights for every update, on the caller's stream, immediately in
+            # front of the online fold at the top of vdqn_net_td_forward.  No event of its own is needed: the Adam launches write
+            # `params` and `target_params` together, so whatever already orders their writes of `params` before that online fold
+            # (stage 2's join of the gradient stream, optimizer_step's wait for `_post_stream`) orders their writes of
+            # `target_params` before this one; the previous update's target pass was joined into this stream before its loss
+            # launch, so it has finished reading `packed_target`; and nothing else reads `target_params`.
+            with torch.cuda.device(self.net.device):
+                self.net.pack_weights(self.packed_target, with_dgrad=False, params=self.target_params)
+        elif self.sample_number % self.tui == 0:
             self.sync_target()
         if self.lr_fn is not None:
             self.lr = float(self.lr_fn(self.sample_number))

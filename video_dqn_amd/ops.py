@@ -260,6 +260,23 @@ def adam_scaled(p, g, m, v, step, lr, beta1=0.9, beta2=0.999, eps=1e-8, weight_d
                                     _stream()), "vdqn_adam_scaled")
 
 
+def polyak_update(target: torch.Tensor, online: torch.Tensor, tau: float) -> None:
+    """Soft target update in place: target <- target + tau * (online - target) over two contiguous f32 device tensors of one size
+    (vdqn_polyak: torch.lerp's two-branch rule, every product rounded on its own; tau in (0, 1], tau = 1 copies)."""
+    if target.numel() != online.numel():
+        raise _lib.VdqnError(f"polyak_update: target has {target.numel()} elements, online {online.numel()}")
+    _lib.check(_lib.load().vdqn_polyak(_ptr(target), _ptr(online), target.numel(), float(tau), _stream()), "vdqn_polyak")
+
+
+def adam_polyak(p, g, m, v, target, tau, step, lr, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.0, coef: Optional[torch.Tensor] = None):
+    """adam_scaled and polyak_update(target, p, tau) in one launch: the new p is lerped into `target` from registers."""
+    if target.numel() != p.numel():
+        raise _lib.VdqnError(f"adam_polyak: target has {target.numel()} elements, p {p.numel()}")
+    lib = _lib.load()
+    _lib.check(lib.vdqn_adam_polyak(_ptr(p), _ptr(g), _ptr(m), _ptr(v), p.numel(), step, lr, beta1, beta2, eps, weight_decay, _ptr(coef),
+                                    _ptr(target), float(tau), _stream()), "vdqn_adam_polyak")
+
+
 def bn_train_fwd(y: torch.Tensor, gamma, beta, running_mean=None, running_var=None, *, resid=None, relu=False,
                  num_frames=1, imgs_per_half=None, momentum=0.1, eps=1e-5, deterministic=False):
     """Train-mode BatchNorm2d over NHWC y [n, h, w, c] (statistic groups: see include/vdqn.h).

@@ -81,14 +81,43 @@ def load_optimizer_state_dict(stepper: TDStepper, sd: dict) -> None:
     stepper.lr, stepper.betas, stepper.eps = g["lr"], tuple(g["betas"]), g["eps"]
 
 
-def save_checkpoint(path, sample_number, model, stepper, replay_state=None):
+def target_state_dict(stepper: TDStepper, model) -> "OrderedDict[str, torch.Tensor]":
+    """TARGET_TAU > 0: the Polyak-averaged target weights as a state_dict with the model's own keys, names and shapes — every
+    parameter from `stepper.target_params` through the engine's slot table, every BatchNorm buffer as the online network holds it
+    (statistics are copied, not averaged) — so the reference's class loads it as the smoothed network."""
+    net = stepper.net
+    out = OrderedDict()
+    for name, value in model.state_dict().items():
+        s = net.slots.get(name)
+        if s is not None and s.kind in (0, 1):
+            out[name] = stepper.target_params[s.offset:s.offset + s.numel].view(s.shape).clone()
+        else:
+            out[name] = value.clone()
+    return out
+
+
+def load_target_state_dict(stepper: TDStepper, sd) -> None:
+    """The parameters of a `target_state_dict` into `stepper.target_params`, then `packed_target` folded from them again."""
+    net = stepper.net
+    with torch.no_grad():
+        for s in net.slots.values():
+            if s.kind in (0, 1):
+                stepper.target_params[s.offset:s.offset + s.numel].copy_(sd[s.name].to(torch.float32).reshape(-1))
+    with torch.cuda.device(net.device):
+        net.pack_weights(stepper.packed_target, with_dgrad=False, params=stepper.target_params)
+
+
+def save_checkpoint(path, sample_number, model, stepper, replay_state=None, target_state_dict=None):
     """replay_state (PRIORITIZED_REPLAY): {'priorities': f32 CPU tensor [N]}, stored under its own key next to the reference's
-    three, which stay as they are (load_model_number and the reference class read the file as before)."""
+    three, which stay as they are (load_model_number and the reference class read the file as before).  target_state_dict
+    (TARGET_TAU > 0): the averaged target weights in the model's names and shapes, likewise under a key of its own."""
     ckpt = {"sample_number": sample_number,
             "model_state_dict": model.state_dict(),
             "optimizer_state_dict": optimizer_state_dict(stepper)}
     if replay_state is not None:
         ckpt["replay_state"] = replay_state
+    if target_state_dict is not None:
+        ckpt["target_state_dict"] = target_state_dict
     torch.save(ckpt, path)
 
 
@@ -137,6 +166,17 @@ def check_cql(config) -> None:
             if getattr(config, key, False):
                 raise ValueError(f"CQL_ALPHA needs more than one action: {key} builds a network with one action column, "
                                  "where logsumexp_a Q(s, .) - Q(s, a) is identically zero")
+
+
+def check_target(config) -> None:
+    """TARGET_TAU: raise ValueError naming the key (before any device work) for a value that is not a finite number in [0, 1] and,
+    when it is on, for the ground-truth branch, which has no target network."""
+    import math
+    tau = getattr(config, "TARGET_TAU", 0.0)
+    if isinstance(tau, bool) or not isinstance(tau, (int, float)) or not math.isfinite(tau) or tau < 0 or tau > 1:
+        raise ValueError(f"TARGET_TAU must be a finite number in [0, 1] (0 = hard copies every TARGET_UPDATE_INTERVAL), not {tau!r}")
+    if tau > 0 and getattr(config, "TRAIN_ON_GROUND_TRUTH", False):
+        raise ValueError("TARGET_TAU needs the TD branch: TRAIN_ON_GROUND_TRUTH regresses on given targets and has no target network")
 
 
 def _to_device_batch(batch, device, num_classes=5):
@@ -226,7 +266,9 @@ def run_train(config, resume_from=-1, max_steps=None, rank=0, world_size=1, log=
     check_augment(aug_pad, aug_flip, aug_actions)
     check_optim(config)
     check_cql(config)
+    check_target(config)
     cql_alpha = float(getattr(config, "CQL_ALPHA", 0.0))
+    target_tau = float(getattr(config, "TARGET_TAU", 0.0))
     clip_norm, weight_decay = float(getattr(config, "GRAD_CLIP_NORM", 0.0)), float(getattr(config, "WEIGHT_DECAY", 0.0))
     lr_fn = None
     if schedule_active(getattr(config, "LR_WARMUP_STEPS", 0), getattr(config, "LR_SCHEDULE", "constant")):
@@ -349,7 +391,11 @@ def run_train(config, resume_from=-1, max_steps=None, rank=0, world_size=1, log=
                         allreduce=(comm.launch if comm else None), loss_kind=getattr(config, "LOSS_KIND", "l2"),
                         allreduce_loss=(comm.launch_loss if comm else None), allreduce_wait=(comm.wait_last if comm else None),
                         allreduce_errors=((lambda: comm.launch_errors(replay.err_all)) if comm and replay else None),
-                        grad_clip_norm=clip_norm, weight_decay=weight_decay, lr_fn=lr_fn, cql_alpha=cql_alpha)
+                        grad_clip_norm=clip_norm, weight_decay=weight_decay, lr_fn=lr_fn, cql_alpha=cql_alpha,
+                        target_tau=target_tau)
+    if target_tau > 0:
+        log(f"soft target updates: target <- target + {target_tau:g} * (online - target) inside every Adam launch, the target weights "
+            "folded from the average in front of every update; TARGET_UPDATE_INTERVAL is unused")
     if cql_alpha > 0:
         log(f"conservative Q-learning: {cql_alpha:g} * (logsumexp_a Q(s, .) - Q(s, a_data)) added to the TD loss in the loss launch")
     if clip_norm > 0 or weight_decay > 0 or lr_fn is not None:
@@ -379,12 +425,14 @@ def run_train(config, resume_from=-1, max_steps=None, rank=0, world_size=1, log=
         iterator = DevicePrefetcher(loopLoader(loader, on_reset=(sampler.set_epoch if sampler else None)), model.engine.device)
     os.makedirs(f"{config.folder}/models", exist_ok=True)
     sample_number = resume_from + 1
+    resumed_target = None  # TARGET_TAU: the checkpoint's averaged target weights, loaded behind the :208 sync below
     if resume_from > -1:  # :192-198
         model_loc = f"{config.folder}/models/sample{resume_from}.torch"
         snapshot = torch.load(model_loc, map_location=config.device)
         log(f"Loading model from: {model_loc}")
         model.load_state_dict(snapshot["model_state_dict"])
         load_optimizer_state_dict(stepper, snapshot["optimizer_state_dict"])
+        resumed_target = snapshot.get("target_state_dict")
         if replay is not None:
             if "replay_state" in snapshot:
                 replay.load_state_dict(snapshot["replay_state"])
@@ -403,13 +451,22 @@ def run_train(config, resume_from=-1, max_steps=None, rank=0, world_size=1, log=
             "models.resnet18(pretrained=True) (archs/HabitatDQNMultiAction.py:11); set PRETRAINED_WEIGHTS in config.yml "
             "(a torchvision resnet18 state_dict file) to train on ImageNet features as the reference does")
     if world_size > 1:  # replicas must start identical: rank 0's parameters, statistics and optimiser state everywhere
+        # (TARGET_TAU: the target too; from then on every rank applies the same reduced gradient inside the same launch, so the
+        # targets stay identical with no collective of their own — a resumed target comes from the one file every rank reads)
         eng = model.engine
-        broadcast_replica_state([eng.params, eng.bnstats, eng.num_batches_tracked, stepper.exp_avg, stepper.exp_avg_sq])
+        broadcast_replica_state([eng.params, eng.bnstats, eng.num_batches_tracked, stepper.exp_avg, stepper.exp_avg_sq] +
+                                ([stepper.target_params] if target_tau > 0 else []))
         steps = torch.tensor([stepper.adam_step], dtype=torch.int64, device=eng.device)
         torch.distributed.broadcast(steps, src=0)
         stepper.adam_step = int(steps.item())
         eng.mark_dirty()
     stepper.sync_target()  # :208
+    if target_tau > 0 and resume_from > -1:  # the averaged target of the interrupted run, in place of the copy :208 has just made
+        if resumed_target is not None:
+            load_target_state_dict(stepper, resumed_target)
+            log("soft target updates: target weights restored from the checkpoint")
+        else:
+            log("soft target updates: the checkpoint has no target_state_dict, the target starts from the online weights")
     stepper.sample_number = sample_number
     stepper.replay = replay  # the run's PrioritizedSampler (PRIORITIZED_REPLAY), None otherwise: returned with the stepper
     stepper.augmenter = augmenter  # the run's Augmenter (AUG_SHIFT_PAD / AUG_FLIP), None otherwise
@@ -486,7 +543,8 @@ def run_train(config, resume_from=-1, max_steps=None, rank=0, world_size=1, log=
             if sample_number % config.CHECKPOINT_INTERVAL == 0 and rank == 0:  # :241-247
                 torch.cuda.synchronize()
                 save_checkpoint(f"{config.folder}/models/sample{sample_number}.torch", sample_number, model, stepper,
-                                replay_state=(replay.state_dict() if replay is not None else None))
+                                replay_state=(replay.state_dict() if replay is not None else None),
+                                target_state_dict=(target_state_dict(stepper, model) if target_tau > 0 else None))
         average(late_loss.take())
         torch.cuda.synchronize()
     finally:
