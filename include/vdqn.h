@@ -252,9 +252,14 @@ int vdqn_softmax_ce(const float* logits, const int64_t* labels, float* loss, voi
 int vdqn_mask_scale(const void* x, const void* mask, void* out, int64_t n, float scale, int32_t dtype, void* stream);
 int vdqn_axpy(float* y, const float* x, float alpha, int64_t n, void* stream);
 
-/* torch.optim.Adam step (train_q_network.py:124,227) over one flat f32 range:
- *   m = b1 m + (1-b1) g; v = b2 v + (1-b2) g^2; p -= (lr / (1-b1^t)) * m / (sqrt(v)/sqrt(1-b2^t) + eps)
- * Hyper-parameters are doubles like torch's python scalars (1-b2 is formed in double before rounding to f32). */
+/* torch.optim.Adam step (train_q_network.py:124,227) over one flat f32 range.  vdqn_adam, vdqn_adam_scaled and vdqn_adam_polyak
+ * (below) are three instances of one kernel and share one element update, in which every fma rounds once and every other
+ * product, sum and quotient rounds on its own, in the float4 body and in the scalar tail (the n % 4 last elements) alike:
+ *   m = fma(1-b1, g, b1 * m);   v = fma((1-b2) * g, g, b2 * v);
+ *   p = fma(-(lr / (1-b1^t)), m / fma(sqrtf(v), 1 / sqrt(1-b2^t), eps), p)
+ * so an element's result does not depend on its position in the range or on the entry.  Hyper-parameters are doubles like
+ * torch's python scalars (1-b2 is formed in double before rounding to f32).  All three check alike and fail by their own name
+ * before any launch: no null pointer, n >= 1, step >= 1, p / g / m / v (and target) 16-byte aligned. */
 int vdqn_adam(float* p, const float* g, float* m, float* v, int64_t n, int32_t step, double lr, double beta1,
               double beta2, double eps, void* stream);
 
@@ -275,9 +280,9 @@ int vdqn_grad_sumsq(const float* g, int64_t n, void* workspace, int32_t slot, vo
  * is not special-cased (a NaN norm gives a NaN coef, as torch's does). */
 int vdqn_clip_finalize(const void* workspace, int32_t n_ranges, double max_norm, float* out, void* stream);
 /* torch.optim.AdamW step on gradients scaled by a device-side coefficient (the multiply clip_grad_norm_ does in place):
- *   gs = g * coef[0] (coef == NULL: 1);  p = p * (1 - lr * weight_decay);  then vdqn_adam's update with gs for g.
- * With coef[0] == 1 and weight_decay == 0 it writes vdqn_adam's bits — in the scalar tail (the n % 4 last elements) because the
- * exp_avg multiply-add is written out there the way vdqn_adam's tail has it (optim.hip tail_moment).  g itself is left as it is. */
+ *   gs = g * coef[0] (coef == NULL: 1);  p = p * (1 - lr * weight_decay);  then vdqn_adam's update with gs for g,
+ * both products rounded on their own: with coef[0] == 1 and weight_decay == 0 it writes vdqn_adam's bits.  g itself is left as it
+ * is.  weight_decay finite and >= 0; coef 4-byte aligned (checked here as in vdqn_adam_polyak). */
 int vdqn_adam_scaled(float* p, const float* g, float* m, float* v, int64_t n, int32_t step, double lr, double beta1,
                      double beta2, double eps, double weight_decay, const float* coef, void* stream);
 
@@ -291,7 +296,7 @@ int vdqn_adam_scaled(float* p, const float* g, float* m, float* v, int64_t n, in
  * (tests/polyak_oracle.py lerp_f32).  n >= 1, both pointers 16-byte aligned (float4 body, scalar tail), the two ranges disjoint,
  * tau finite in (0, 1]; anything else fails by name before a launch. */
 int vdqn_polyak(float* target, const float* p, int64_t n, double tau, void* stream);
-/* vdqn_adam_scaled and vdqn_polyak in one launch: p, m, v are updated by vdqn_adam_scaled's expressions (coef == NULL and
+/* vdqn_adam_scaled and vdqn_polyak in one launch: p, m, v are updated by vdqn_adam_scaled's element update (coef == NULL and
  * weight_decay == 0: vdqn_adam's bits), then the new p, still in registers, is lerped into target[0, n) by the rule above — one
  * more read and one more write of `target` per element, where a second launch would stream p a third time.  Arguments as
  * vdqn_adam_scaled's; target 16-byte aligned like the others, its range disjoint from theirs (refused by name otherwise); tau finite

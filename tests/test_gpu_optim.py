@@ -181,6 +181,66 @@ def test_adam_scaled_at_unit_factors_is_adam_bit_for_bit(coef_kind):
     assert not torch.equal(a[0].cpu(), p0)
 
 
+_PRISTINE = {}
+
+
+def _pristine(n):
+    """_adam_state(n) of tests/test_gpu_polyak.py (nonzero moments) on the device, made once per n and never written."""
+    from test_gpu_polyak import _adam_state
+    if n not in _PRISTINE:
+        _PRISTINE[n] = [torch.from_numpy(x).to(DEV) for x in _adam_state(n, 5 * n + 2)]
+    return _PRISTINE[n]
+
+
+def _two_steps(entry, n, length, tau):
+    """Fresh guarded copies of the n-element state, two steps of `entry` over their first `length` elements -> [(buffer, view)] * 5."""
+    from test_gpu_polyak import POISON
+    from video_dqn_amd import ops
+    state = []
+    for x in _pristine(n):
+        buf = torch.full((n + 8,), POISON, dtype=torch.float32, device=DEV)
+        assert buf.data_ptr() % 16 == 0
+        buf[4:4 + n] = x
+        state.append((buf, buf[4:4 + n]))
+    p, g, m, v, t = (view[:length] for _, view in state)
+    kw = dict(weight_decay=0.1, coef=torch.full((1,), 0.37, dtype=torch.float32, device=DEV))
+    for step in (1, 2):
+        if entry == "adam":
+            ops.adam(p, g, m, v, step, 1e-3)
+        elif entry == "adam_scaled":
+            ops.adam_scaled(p, g, m, v, step, 1e-3, **kw)
+        else:
+            ops.adam_polyak(p, g, m, v, t, tau, step, 1e-3, **kw)
+    return state
+
+
+@pytest.mark.parametrize("n", [8, 260, 4096 * 256 * 4 + 8])
+@pytest.mark.parametrize("entry", ["adam", "adam_scaled", "adam_polyak"])
+def test_adam_element_does_not_depend_on_its_position_in_the_range(entry, n):
+    """Two steps over [0, n) against the same two steps over [0, n - 1), [0, n - 2) and [0, n - 3): n is a multiple of 4, so the last
+    elements of the shorter ranges sit in the float4 loop of one launch and in the scalar tail loop of the other (at the largest n every
+    thread of the capped grid walks its float4 loop twice).  Every element both launches cover agrees bit for bit in p, exp_avg,
+    exp_avg_sq and the target; what lies behind the shorter range, and the guards, are untouched.  One element function with every
+    rounding written out serves both loops (csrc/optim.hip adam_element): two loops that the compiler may contract differently
+    (exp_avg_sq as one fma in one, as two rounded products in the other) fail this in exp_avg_sq."""
+    from test_gpu_polyak import _guards_intact
+    names = ("p", "g", "exp_avg", "exp_avg_sq", "target")
+    touched = (True, False, True, True, entry == "adam_polyak")
+    for tau in ((0.005, 0.5) if entry == "adam_polyak" else (None,)):
+        full = _two_steps(entry, n, n, tau)
+        for name, (buf, view), x, moved in zip(names, full, _pristine(n), touched):
+            assert _guards_intact(buf), (name, tau)
+            assert torch.equal(view.view(torch.int32), x.view(torch.int32)) != moved, (name, tau)
+        for cut in (1, 2, 3):
+            part = _two_steps(entry, n, n - cut, tau)
+            for name, (_, a), (buf, b), x in zip(names, full, part, _pristine(n)):
+                assert torch.equal(a[:n - cut].view(torch.int32), b[:n - cut].view(torch.int32)), (name, cut, tau)
+                assert torch.equal(b[n - cut:].view(torch.int32), x[n - cut:].view(torch.int32)), (name, cut, tau)
+                assert _guards_intact(buf), (name, cut, tau)
+            del part
+        del full
+
+
 # ---- 3. updates through the engine ---------------------------------------------------------------------------------------------------
 BASE_LR, WD, WARMUP = 1e-3, 0.1, 4  # (the reference's rate: an lr-sized step stays well above the f32 spacing of the weights)
 

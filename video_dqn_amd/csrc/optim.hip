@@ -101,62 +101,6 @@ __global__ __launch_bounds__(256) void clip_finalize_kernel(const double* __rest
   }
 }
 
-// The two multiplies AdamW and the clipping add in front of Adam's arithmetic, each rounded on its own: never contracted into the
-// adds that follow, so a unit factor leaves every bit of the plain update as it is.
-__device__ __forceinline__ float mul_rounded(float a, float b) {
-#pragma clang fp contract(off)
-  return a * b;
-}
-
-// m = beta1 * m + omb1 * g of the scalar tail loops below, with the one fused multiply-add written out as adam_kernel's tail has it:
-// fma(beta1, m, round(omb1 * g)).  Left to the compiler, the tail here contracted the other product (fma(omb1, g, round(beta1 * m))),
-// and the up to three tail elements of a range then missed the plain kernel's bits at unit factors.
-// What this pins is this file's side only.  adam_kernel (pointwise.hip) still leaves both of its loops to the compiler, and the float4
-// bodies of adam_scaled_kernel and adam_polyak_kernel match its body because the compiler contracts the same expression the same
-// way in all three: a toolchain that decides otherwise breaks the "vdqn_adam's bits" equality again, and tests/test_gpu_polyak.py
-// (every size with a tail, moments that are not zero) is what notices.  Writing the fma out in adam_kernel too would settle it, at
-// the price of that kernel's ISA.
-__device__ __forceinline__ float tail_moment(float beta1, float m, float omb1, float g) {
-  return __builtin_fmaf(beta1, m, mul_rounded(omb1, g));
-}
-
-// adam_kernel (pointwise.hip) with gs = g * coef in place of g and p * decay in place of p; the three expressions are that kernel's.
-// A kernel of its own rather than a flag on adam_kernel, which keeps the ISA it has: coef = 1
-// and decay = 1 give the plain kernel's bits.
-__global__ __launch_bounds__(256) void adam_scaled_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                          float* __restrict__ v, long n, float step_size, float beta1, float beta2,
-                                                          float omb1, float omb2, float inv_sqrt_bc2, float eps, float decay,
-                                                          const float* __restrict__ coef_ptr) {
-  const float coef = coef_ptr ? coef_ptr[0] : 1.0f;
-  const long n4 = n >> 2;
-  const long stride = (long)gridDim.x * blockDim.x;
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
-    float4 pp = reinterpret_cast<float4*>(p)[i];
-    float4 gg = reinterpret_cast<const float4*>(g)[i];
-    float4 mm = reinterpret_cast<float4*>(m)[i];
-    float4 vv = reinterpret_cast<float4*>(v)[i];
-#define VDQN_ADAM1(c)                                              \
-  gg.c = mul_rounded(gg.c, coef);                        \
-  pp.c = mul_rounded(pp.c, decay);                       \
-  mm.c = beta1 * mm.c + omb1 * gg.c;                     \
-  vv.c = beta2 * vv.c + omb2 * gg.c * gg.c;              \
-  pp.c = pp.c - step_size * (mm.c / (sqrtf(vv.c) * inv_sqrt_bc2 + eps));
-    VDQN_ADAM1(x) VDQN_ADAM1(y) VDQN_ADAM1(z) VDQN_ADAM1(w)
-#undef VDQN_ADAM1
-    reinterpret_cast<float4*>(p)[i] = pp;
-    reinterpret_cast<float4*>(m)[i] = mm;
-    reinterpret_cast<float4*>(v)[i] = vv;
-  }
-  for (long i = (n4 << 2) + (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-    const float gg = mul_rounded(g[i], coef);
-    const float mm = tail_moment(beta1, m[i], omb1, gg);
-    const float vv = beta2 * v[i] + omb2 * gg * gg;
-    m[i] = mm;
-    v[i] = vv;
-    p[i] = mul_rounded(p[i], decay) - step_size * (mm / (sqrtf(vv) * inv_sqrt_bc2 + eps));
-  }
-}
-
 // Soft (Polyak) target update of one element, theta- <- theta- + tau (theta - theta-), as torch.lerp's two-branch rule with every
 // product rounded on its own (include/vdqn.h writes it out; tests/polyak_oracle.py restates it in numpy float32):
 //   d = p - t;   tau < 0.5: t + tau_f * d;   otherwise: p - d * omt_f      (tau_f = (float)tau, omt_f = (float)(1.0 - tau))
@@ -167,6 +111,12 @@ __device__ __forceinline__ float lerp_rounded(float t, float p, float tau_f, flo
   const float a = tau_f * d;
   const float b = d * omt_f;
   return lo ? t + a : p - b;
+}
+
+// 256 threads, one float4 per thread and pass, 4096 blocks at the most (n / 4 + 1: a range shorter than 4 still gets its tail's block)
+inline int flat_grid(int64_t n) {
+  const int64_t b = ((n / 4 + 1) + 255) / 256;
+  return (int)(b > 4096 ? 4096 : b);
 }
 
 __global__ __launch_bounds__(256) void polyak_kernel(float* __restrict__ t, const float* __restrict__ p, long n, float tau_f, float omt_f,
@@ -185,46 +135,75 @@ __global__ __launch_bounds__(256) void polyak_kernel(float* __restrict__ t, cons
   for (long i = (n4 << 2) + (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) t[i] = lerp_rounded(t[i], p[i], tau_f, omt_f, lo);
 }
 
-// adam_scaled_kernel, then the new p — still in registers — lerped into the target copy: one more read and one more write of `t`
-// per element instead of a second launch that streams p again.  The p, m, v expressions are adam_scaled_kernel's, token for token.
-__global__ __launch_bounds__(256) void adam_polyak_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                          float* __restrict__ v, long n, float step_size, float beta1, float beta2,
-                                                          float omb1, float omb2, float inv_sqrt_bc2, float eps, float decay,
-                                                          const float* __restrict__ coef_ptr, float* __restrict__ t, float tau_f,
-                                                          float omt_f, int lo) {
-  const float coef = coef_ptr ? coef_ptr[0] : 1.0f;
+// The Adam update of one element (torch.optim.Adam / AdamW; train_q_network.py:124,227), the only statement of it.  Contraction is
+// off and every fused multiply-add is written out, so each fma below rounds once and every other product, sum and quotient rounds
+// on its own, whichever loop, instance or compiler evaluates it:
+//   SCALED:  g = g * coef;   p = p * decay                                  (coef = coef_ptr[0] or 1, decay = 1 - lr * weight_decay)
+//   m = fma(omb1, g, beta1 * m)                v = fma(omb2 * g, g, beta2 * v)                          (omb = 1 - beta)
+//   p = fma(-step_size, m / fma(sqrtf(v), inv_sqrt_bc2, eps), p)            (step_size = lr / bc1, inv_sqrt_bc2 = 1 / sqrt(bc2))
+//   POLYAK:  t = lerp_rounded(t, p)            (the new p, still in registers: one more read and write of t, no second launch)
+// A unit coef and decay multiply exactly, so the SCALED instances then write the plain one's bits.
+struct adam_consts {
+  float step_size, beta1, beta2, omb1, omb2, inv_sqrt_bc2, eps, decay, tau_f, omt_f;
+  int lo;
+};
+template <bool SCALED, bool POLYAK>
+__device__ __forceinline__ void adam_element(float& p, float g, float& m, float& v, float& t, float coef, const adam_consts& k) {
+#pragma clang fp contract(off)
+  if constexpr (SCALED) {
+    g = g * coef;
+    p = p * k.decay;
+  }
+  m = __builtin_fmaf(k.omb1, g, k.beta1 * m);
+  v = __builtin_fmaf(k.omb2 * g, g, k.beta2 * v);
+  p = __builtin_fmaf(-k.step_size, m / __builtin_fmaf(sqrtf(v), k.inv_sqrt_bc2, k.eps), p);
+  if constexpr (POLYAK) t = lerp_rounded(t, p, k.tau_f, k.omt_f, k.lo);
+}
+
+// Three instances: plain (vdqn_adam), SCALED (vdqn_adam_scaled), SCALED + POLYAK (vdqn_adam_polyak).  Compile-time flags: a run-time
+// one would put the target's loads and registers into every instance.  `t` and `coef_ptr` are read only by the instances that use them.
+template <bool SCALED, bool POLYAK>
+__global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                   float* __restrict__ v, float* __restrict__ t, const float* __restrict__ coef_ptr, long n,
+                                                   const adam_consts k) {
+  float coef = 1.0f;
+  if constexpr (SCALED) coef = coef_ptr ? coef_ptr[0] : 1.0f;
   const long n4 = n >> 2;
   const long stride = (long)gridDim.x * blockDim.x;
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
     float4 pp = reinterpret_cast<float4*>(p)[i];
-    float4 gg = reinterpret_cast<const float4*>(g)[i];
+    const float4 gg = reinterpret_cast<const float4*>(g)[i];
     float4 mm = reinterpret_cast<float4*>(m)[i];
     float4 vv = reinterpret_cast<float4*>(v)[i];
-    float4 tt = reinterpret_cast<float4*>(t)[i];
-#define VDQN_ADAM1(c)                                              \
-  gg.c = mul_rounded(gg.c, coef);                        \
-  pp.c = mul_rounded(pp.c, decay);                       \
-  mm.c = beta1 * mm.c + omb1 * gg.c;                     \
-  vv.c = beta2 * vv.c + omb2 * gg.c * gg.c;              \
-  pp.c = pp.c - step_size * (mm.c / (sqrtf(vv.c) * inv_sqrt_bc2 + eps)); \
-  tt.c = lerp_rounded(tt.c, pp.c, tau_f, omt_f, lo);
-    VDQN_ADAM1(x) VDQN_ADAM1(y) VDQN_ADAM1(z) VDQN_ADAM1(w)
-#undef VDQN_ADAM1
+    float4 tt = {};
+    if constexpr (POLYAK) tt = reinterpret_cast<float4*>(t)[i];
+    adam_element<SCALED, POLYAK>(pp.x, gg.x, mm.x, vv.x, tt.x, coef, k);
+    adam_element<SCALED, POLYAK>(pp.y, gg.y, mm.y, vv.y, tt.y, coef, k);
+    adam_element<SCALED, POLYAK>(pp.z, gg.z, mm.z, vv.z, tt.z, coef, k);
+    adam_element<SCALED, POLYAK>(pp.w, gg.w, mm.w, vv.w, tt.w, coef, k);
     reinterpret_cast<float4*>(p)[i] = pp;
     reinterpret_cast<float4*>(m)[i] = mm;
     reinterpret_cast<float4*>(v)[i] = vv;
-    reinterpret_cast<float4*>(t)[i] = tt;
+    if constexpr (POLYAK) reinterpret_cast<float4*>(t)[i] = tt;
   }
   for (long i = (n4 << 2) + (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-    const float gg = mul_rounded(g[i], coef);
-    const float mm = tail_moment(beta1, m[i], omb1, gg);
-    const float vv = beta2 * v[i] + omb2 * gg * gg;
+    float pp = p[i], mm = m[i], vv = v[i], tt = 0.f;
+    if constexpr (POLYAK) tt = t[i];
+    adam_element<SCALED, POLYAK>(pp, g[i], mm, vv, tt, coef, k);
+    p[i] = pp;
     m[i] = mm;
     v[i] = vv;
-    const float pp = mul_rounded(p[i], decay) - step_size * (mm / (sqrtf(vv) * inv_sqrt_bc2 + eps));
-    p[i] = pp;
-    t[i] = lerp_rounded(t[i], pp, tau_f, omt_f, lo);
+    if constexpr (POLYAK) t[i] = tt;
   }
+}
+
+// tau in (0, 1] and finite, written so that a NaN fails
+inline bool tau_ok(double tau) { return isfinite(tau) && tau > 0.0 && tau <= 1.0; }
+
+// [a, a + n) and [b, b + n) floats share no element (the kernels declare both __restrict__)
+inline bool disjoint(const float* a, const float* b, int64_t n) {
+  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b, bytes = (uintptr_t)n * sizeof(float);
+  return x + bytes <= y || y + bytes <= x;
 }
 
 }  // namespace
@@ -258,75 +237,67 @@ extern "C" int vdqn_clip_finalize(const void* workspace, int32_t n_ranges, doubl
   return VDQN_OK;
 }
 
-extern "C" int vdqn_adam_scaled(float* p, const float* g, float* m, float* v, int64_t n, int32_t step, double lr, double beta1, double beta2,
-                                double eps, double weight_decay, const float* coef, void* stream) {
-  VDQN_CHECK(p && g && m && v && n > 0 && step >= 1, "vdqn_adam_scaled: bad args");
-  VDQN_CHECK((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0, "vdqn_adam_scaled: pointers must be 16-byte aligned");
-  VDQN_CHECK(weight_decay >= 0.0 && isfinite(weight_decay), "vdqn_adam_scaled: weight_decay must be finite and >= 0");
-  const double bc1 = 1.0 - pow(beta1, (double)step);
-  const double bc2 = 1.0 - pow(beta2, (double)step);
-  const float step_size = (float)(lr / bc1);
-  const float inv_sqrt_bc2 = (float)(1.0 / sqrt(bc2));
-  const float decay = (float)(1.0 - lr * weight_decay);
-  int64_t grid = ((n / 4 + 1) + 255) / 256;  // vdqn_adam's grid
-  if (grid > 4096) grid = 4096;
-  ProfScope ps_("adam_scaled", 0.0, (double)n * 28.0, (hipStream_t)stream);
-  hipLaunchKernelGGL(adam_scaled_kernel, dim3((int)grid), dim3(256), 0, (hipStream_t)stream, p, g, m, v, (long)n, step_size, (float)beta1,
-                     (float)beta2, (float)(1.0 - beta1), (float)(1.0 - beta2), inv_sqrt_bc2, (float)eps, decay, coef);
-  VDQN_LAUNCH_CHECK();
-  return VDQN_OK;
-}
-
-namespace {
-
-// tau in (0, 1] and finite, written so that a NaN fails
-inline bool tau_ok(double tau) { return isfinite(tau) && tau > 0.0 && tau <= 1.0; }
-
-// [a, a + n) and [b, b + n) floats share no element (the kernels declare both __restrict__)
-inline bool disjoint(const float* a, const float* b, int64_t n) {
-  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b, bytes = (uintptr_t)n * sizeof(float);
-  return x + bytes <= y || y + bytes <= x;
-}
-
-}  // namespace
-
 extern "C" int vdqn_polyak(float* target, const float* p, int64_t n, double tau, void* stream) {
   VDQN_CHECK(target && p, "vdqn_polyak: null pointer");
   VDQN_CHECK(n >= 1, "vdqn_polyak: n must be >= 1");
   VDQN_CHECK((((uintptr_t)target | (uintptr_t)p) & 15) == 0, "vdqn_polyak: pointers must be 16-byte aligned");
   VDQN_CHECK(tau_ok(tau), "vdqn_polyak: tau must be finite and in (0, 1]");
   VDQN_CHECK(disjoint(target, p, n), "vdqn_polyak: target and p must not overlap");
-  int64_t grid = ((n / 4 + 1) + 255) / 256;
-  if (grid > 4096) grid = 4096;
   ProfScope ps_("polyak", 0.0, (double)n * 12.0, (hipStream_t)stream);
-  hipLaunchKernelGGL(polyak_kernel, dim3((int)grid), dim3(256), 0, (hipStream_t)stream, target, p, (long)n, (float)tau, (float)(1.0 - tau),
+  hipLaunchKernelGGL(polyak_kernel, dim3(flat_grid(n)), dim3(256), 0, (hipStream_t)stream, target, p, (long)n, (float)tau, (float)(1.0 - tau),
                      (int)(tau < 0.5));
   VDQN_LAUNCH_CHECK();
   return VDQN_OK;
 }
 
-extern "C" int vdqn_adam_polyak(float* p, const float* g, float* m, float* v, int64_t n, int32_t step, double lr, double beta1, double beta2,
-                                double eps, double weight_decay, const float* coef, float* target, double tau, void* stream) {
-  VDQN_CHECK(p && g && m && v && target, "vdqn_adam_polyak: null pointer");
-  VDQN_CHECK(n >= 1 && step >= 1, "vdqn_adam_polyak: n and step must be >= 1");
-  VDQN_CHECK((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v | (uintptr_t)target) & 15) == 0,
-             "vdqn_adam_polyak: pointers must be 16-byte aligned");
-  VDQN_CHECK((((uintptr_t)coef) & 3) == 0, "vdqn_adam_polyak: coef must be 4-byte aligned");
-  VDQN_CHECK(weight_decay >= 0.0 && isfinite(weight_decay), "vdqn_adam_polyak: weight_decay must be finite and >= 0");
-  VDQN_CHECK(tau_ok(tau), "vdqn_adam_polyak: tau must be finite and in (0, 1]");
-  VDQN_CHECK(disjoint(target, p, n) && disjoint(target, g, n) && disjoint(target, m, n) && disjoint(target, v, n),
-             "vdqn_adam_polyak: target must not overlap p, g, m or v");
+// The three Adam entries: every check (each fails by the entry's name before any HIP call), the host constants, then the one launch.
+// Plain entries pass weight_decay 0 and coef NULL; only the POLYAK entry has a target and a tau.
+template <bool SCALED, bool POLYAK>
+static int adam_launch(const char* entry, const char* prof_name, float* p, const float* g, float* m, float* v, int64_t n, int32_t step, double lr,
+                       double beta1, double beta2, double eps, double weight_decay, const float* coef, float* target, double tau, void* stream) {
+  VDQN_CHECK(p && g && m && v && (!POLYAK || target), "%s: null pointer", entry);
+  VDQN_CHECK(n >= 1 && step >= 1, "%s: n and step must be >= 1", entry);
+  VDQN_CHECK((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v | (uintptr_t)target) & 15) == 0, "%s: pointers must be 16-byte aligned", entry);
+  VDQN_CHECK((((uintptr_t)coef) & 3) == 0, "%s: coef must be 4-byte aligned", entry);
+  VDQN_CHECK(weight_decay >= 0.0 && isfinite(weight_decay), "%s: weight_decay must be finite and >= 0", entry);
+  if (POLYAK) {
+    VDQN_CHECK(tau_ok(tau), "%s: tau must be finite and in (0, 1]", entry);
+    VDQN_CHECK(disjoint(target, p, n) && disjoint(target, g, n) && disjoint(target, m, n) && disjoint(target, v, n),
+               "%s: target must not overlap p, g, m or v", entry);
+  }
   const double bc1 = 1.0 - pow(beta1, (double)step);
   const double bc2 = 1.0 - pow(beta2, (double)step);
-  const float step_size = (float)(lr / bc1);
-  const float inv_sqrt_bc2 = (float)(1.0 / sqrt(bc2));
-  const float decay = (float)(1.0 - lr * weight_decay);
-  int64_t grid = ((n / 4 + 1) + 255) / 256;  // vdqn_adam's grid
-  if (grid > 4096) grid = 4096;
-  ProfScope ps_("adam_polyak", 0.0, (double)n * 36.0, (hipStream_t)stream);
-  hipLaunchKernelGGL(adam_polyak_kernel, dim3((int)grid), dim3(256), 0, (hipStream_t)stream, p, g, m, v, (long)n, step_size, (float)beta1,
-                     (float)beta2, (float)(1.0 - beta1), (float)(1.0 - beta2), inv_sqrt_bc2, (float)eps, decay, coef, target, (float)tau,
-                     (float)(1.0 - tau), (int)(tau < 0.5));
+  adam_consts k;
+  k.step_size = (float)(lr / bc1);
+  k.beta1 = (float)beta1;
+  k.beta2 = (float)beta2;
+  k.omb1 = (float)(1.0 - beta1);
+  k.omb2 = (float)(1.0 - beta2);
+  k.inv_sqrt_bc2 = (float)(1.0 / sqrt(bc2));
+  k.eps = (float)eps;
+  k.decay = (float)(1.0 - lr * weight_decay);
+  k.tau_f = (float)tau;
+  k.omt_f = (float)(1.0 - tau);
+  k.lo = (int)(tau < 0.5);
+  ProfScope ps_(prof_name, 0.0, (double)n * (POLYAK ? 36.0 : 28.0), (hipStream_t)stream);
+  hipLaunchKernelGGL((adam_kernel<SCALED, POLYAK>), dim3(flat_grid(n)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, target, coef, (long)n, k);
   VDQN_LAUNCH_CHECK();
   return VDQN_OK;
+}
+
+extern "C" int vdqn_adam(float* p, const float* g, float* m, float* v, int64_t n, int32_t step, double lr, double beta1, double beta2, double eps,
+                         void* stream) {
+  return adam_launch<false, false>("vdqn_adam", "adam", p, g, m, v, n, step, lr, beta1, beta2, eps, 0.0, nullptr, nullptr, 1.0, stream);
+}
+
+extern "C" int vdqn_adam_scaled(float* p, const float* g, float* m, float* v, int64_t n, int32_t step, double lr, double beta1, double beta2,
+                                double eps, double weight_decay, const float* coef, void* stream) {
+  return adam_launch<true, false>("vdqn_adam_scaled", "adam_scaled", p, g, m, v, n, step, lr, beta1, beta2, eps, weight_decay, coef, nullptr, 1.0,
+                                  stream);
+}
+
+extern "C" int vdqn_adam_polyak(float* p, const float* g, float* m, float* v, int64_t n, int32_t step, double lr, double beta1, double beta2,
+                                double eps, double weight_decay, const float* coef, float* target, double tau, void* stream) {
+  return adam_launch<true, true>("vdqn_adam_polyak", "adam_polyak", p, g, m, v, n, step, lr, beta1, beta2, eps, weight_decay, coef, target, tau,
+                                 stream);
 }

@@ -1,5 +1,5 @@
 // HBM-bound kernels of the hot path: input packing (normalise + space-to-depth), 3x3/2 max-pool forward and
-// backward, the fused Double-DQN target / TD-loss / dQ kernel, and the flat fused Adam.
+// backward, and the fused Double-DQN target / TD-loss / dQ kernel.  (The optimiser, Adam included, is optim.hip.)
 // All accesses are 16-byte vectors over the contiguous NHWC channel axis.
 #include <math.h>
 
@@ -472,39 +472,6 @@ __global__ __launch_bounds__(256) void gt_loss_kernel(const float* __restrict__ 
   }
 }
 
-// ---------------------------------------------------------------------------------------------------------
-// Adam over a flat f32 range (torch.optim.Adam defaults; train_q_network.py:124,227)
-// ---------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                   float* __restrict__ v, long n, float step_size, float beta1, float beta2,
-                                                   float omb1, float omb2, float inv_sqrt_bc2, float eps) {
-  const long n4 = n >> 2;
-  const long stride = (long)gridDim.x * blockDim.x;
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
-    float4 pp = reinterpret_cast<float4*>(p)[i];
-    const float4 gg = reinterpret_cast<const float4*>(g)[i];
-    float4 mm = reinterpret_cast<float4*>(m)[i];
-    float4 vv = reinterpret_cast<float4*>(v)[i];
-#define VDQN_ADAM1(c)                                              \
-  mm.c = beta1 * mm.c + omb1 * gg.c;                     \
-  vv.c = beta2 * vv.c + omb2 * gg.c * gg.c;              \
-  pp.c = pp.c - step_size * (mm.c / (sqrtf(vv.c) * inv_sqrt_bc2 + eps));
-    VDQN_ADAM1(x) VDQN_ADAM1(y) VDQN_ADAM1(z) VDQN_ADAM1(w)
-#undef VDQN_ADAM1
-    reinterpret_cast<float4*>(p)[i] = pp;
-    reinterpret_cast<float4*>(m)[i] = mm;
-    reinterpret_cast<float4*>(v)[i] = vv;
-  }
-  for (long i = (n4 << 2) + (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-    const float gg = g[i];
-    const float mm = beta1 * m[i] + omb1 * gg;
-    const float vv = beta2 * v[i] + omb2 * gg * gg;
-    m[i] = mm;
-    v[i] = vv;
-    p[i] = p[i] - step_size * (mm / (sqrtf(vv) * inv_sqrt_bc2 + eps));
-  }
-}
-
 inline int grid_for(long total, int cap = 8192) {
   long b = (total + 255) / 256;
   if (b > cap) b = cap;
@@ -700,22 +667,6 @@ extern "C" int vdqn_gt_loss(const float* q_before, const int64_t* act, const flo
   ProfScope ps_("gt_loss", 0.0, (double)batch * ldq * 8.0, (hipStream_t)stream);
   if (dtype == VDQN_BF16) hipLaunchKernelGGL((gt_loss_kernel<bf16raw>), dim3(g), dim3(256), 0, (hipStream_t)stream, q_before, act, gt, loss, (bf16raw*)dq, dq_f32, batch, n_cat, n_act, ldq, inv_count, value_learning);
   else hipLaunchKernelGGL((gt_loss_kernel<float>), dim3(g), dim3(256), 0, (hipStream_t)stream, q_before, act, gt, loss, (float*)dq, dq_f32, batch, n_cat, n_act, ldq, inv_count, value_learning);
-  VDQN_LAUNCH_CHECK();
-  return VDQN_OK;
-}
-
-extern "C" int vdqn_adam(float* p, const float* g, float* m, float* v, int64_t n, int32_t step, double lr, double beta1, double beta2, double eps,
-                         void* stream) {
-  VDQN_CHECK(p && g && m && v && n > 0 && step >= 1, "vdqn_adam: bad args");
-  VDQN_CHECK((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0, "vdqn_adam: pointers must be 16-byte aligned");
-  const double bc1 = 1.0 - pow(beta1, (double)step);
-  const double bc2 = 1.0 - pow(beta2, (double)step);
-  const float step_size = (float)(lr / bc1);
-  const float inv_sqrt_bc2 = (float)(1.0 / sqrt(bc2));
-  const int grid = grid_for(n / 4 + 1, 4096);
-  ProfScope ps_("adam", 0.0, (double)n * 28.0, (hipStream_t)stream);
-  hipLaunchKernelGGL(adam_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, p, g, m, v, (long)n, step_size, (float)beta1, (float)beta2,
-                     (float)(1.0 - beta1), (float)(1.0 - beta2), inv_sqrt_bc2, (float)eps);
   VDQN_LAUNCH_CHECK();
   return VDQN_OK;
 }

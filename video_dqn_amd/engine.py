@@ -583,26 +583,19 @@ class TDStepper:
 
     def _adam_range(self, b: int, e: int, step: int):
         """Adam (train_q_network.py:227) over the flat element range [b, e) on the current stream."""
-        n = self.net
+        common = [t.data_ptr() + 4 * b for t in (self.net.params, self.grads, self.exp_avg, self.exp_avg_sq)]
+        common += [e - b, step, self.lr, self.betas[0], self.betas[1], self.eps]
+        scaled = [self.weight_decay, self.clip_out.data_ptr() + 4 if self.grad_clip_norm > 0 else None]
         if self.target_params is not None:
             # the soft target update rides in the Adam launch, wherever that is queued (optimizer_step, the early launches on the
             # gradient stream, the per-bucket ones on `_post_stream`): there is no window in which `params` has moved and
             # `target_params` has not, and whatever orders one array's writes orders the other's
-            coef = self.clip_out.data_ptr() + 4 if self.grad_clip_norm > 0 else None
-            _lib.check(self.lib.vdqn_adam_polyak(n.params.data_ptr() + 4 * b, self.grads.data_ptr() + 4 * b, self.exp_avg.data_ptr() + 4 * b,
-                                                 self.exp_avg_sq.data_ptr() + 4 * b, e - b, step, self.lr, self.betas[0], self.betas[1],
-                                                 self.eps, self.weight_decay, coef, self.target_params.data_ptr() + 4 * b, self.target_tau,
-                                                 _stream()), "vdqn_adam_polyak")
-            return
-        if self.grad_clip_norm > 0 or self.weight_decay != 0:
-            coef = self.clip_out.data_ptr() + 4 if self.grad_clip_norm > 0 else None
-            _lib.check(self.lib.vdqn_adam_scaled(n.params.data_ptr() + 4 * b, self.grads.data_ptr() + 4 * b, self.exp_avg.data_ptr() + 4 * b,
-                                                 self.exp_avg_sq.data_ptr() + 4 * b, e - b, step, self.lr, self.betas[0], self.betas[1],
-                                                 self.eps, self.weight_decay, coef, _stream()), "vdqn_adam_scaled")
-            return
-        _lib.check(self.lib.vdqn_adam(n.params.data_ptr() + 4 * b, self.grads.data_ptr() + 4 * b, self.exp_avg.data_ptr() + 4 * b,
-                                      self.exp_avg_sq.data_ptr() + 4 * b, e - b, step, self.lr, self.betas[0], self.betas[1],
-                                      self.eps, _stream()), "vdqn_adam")
+            entry, args = "vdqn_adam_polyak", common + scaled + [self.target_params.data_ptr() + 4 * b, self.target_tau]
+        elif self.grad_clip_norm > 0 or self.weight_decay != 0:
+            entry, args = "vdqn_adam_scaled", common + scaled
+        else:
+            entry, args = "vdqn_adam", common
+        _lib.check(getattr(self.lib, entry)(*args, _stream()), entry)
 
     def optimizer_step(self):
         n = self.net

@@ -226,9 +226,13 @@ def gt_loss(q_before, act, gt, *, n_cat=5, n_act=3, inv_count=None, value_learni
     return loss, dq32
 
 
+def _adam(entry, p, g, m, v, step, lr, beta1, beta2, eps, *more):
+    """One of the three Adam entries (csrc/optim.hip) over the flat tensors p, g, m, v; `more` = what the entry takes behind eps."""
+    _lib.check(getattr(_lib.load(), entry)(_ptr(p), _ptr(g), _ptr(m), _ptr(v), p.numel(), step, lr, beta1, beta2, eps, *more, _stream()), entry)
+
+
 def adam(p, g, m, v, step, lr, beta1=0.9, beta2=0.999, eps=1e-8):
-    lib = _lib.load()
-    _lib.check(lib.vdqn_adam(_ptr(p), _ptr(g), _ptr(m), _ptr(v), p.numel(), step, lr, beta1, beta2, eps, _stream()), "vdqn_adam")
+    _adam("vdqn_adam", p, g, m, v, step, lr, beta1, beta2, eps)
 
 
 def clip_workspace(device, n_ranges: int = 1) -> torch.Tensor:
@@ -255,9 +259,7 @@ def clip_finalize(workspace: torch.Tensor, n_ranges: int, max_norm: float, out: 
 
 def adam_scaled(p, g, m, v, step, lr, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.0, coef: Optional[torch.Tensor] = None):
     """torch.optim.AdamW on g * coef[0] (coef: f32 device tensor, e.g. clip_finalize(..)[1:]; None = 1)."""
-    lib = _lib.load()
-    _lib.check(lib.vdqn_adam_scaled(_ptr(p), _ptr(g), _ptr(m), _ptr(v), p.numel(), step, lr, beta1, beta2, eps, weight_decay, _ptr(coef),
-                                    _stream()), "vdqn_adam_scaled")
+    _adam("vdqn_adam_scaled", p, g, m, v, step, lr, beta1, beta2, eps, weight_decay, _ptr(coef))
 
 
 def polyak_update(target: torch.Tensor, online: torch.Tensor, tau: float) -> None:
@@ -272,9 +274,7 @@ def adam_polyak(p, g, m, v, target, tau, step, lr, beta1=0.9, beta2=0.999, eps=1
     """adam_scaled and polyak_update(target, p, tau) in one launch: the new p is lerped into `target` from registers."""
     if target.numel() != p.numel():
         raise _lib.VdqnError(f"adam_polyak: target has {target.numel()} elements, p {p.numel()}")
-    lib = _lib.load()
-    _lib.check(lib.vdqn_adam_polyak(_ptr(p), _ptr(g), _ptr(m), _ptr(v), p.numel(), step, lr, beta1, beta2, eps, weight_decay, _ptr(coef),
-                                    _ptr(target), float(tau), _stream()), "vdqn_adam_polyak")
+    _adam("vdqn_adam_polyak", p, g, m, v, step, lr, beta1, beta2, eps, weight_decay, _ptr(coef), _ptr(target), float(tau))
 
 
 def bn_train_fwd(y: torch.Tensor, gamma, beta, running_mean=None, running_var=None, *, resid=None, relu=False,
