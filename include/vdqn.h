@@ -207,6 +207,22 @@ int vdqn_td_loss_weighted(const vdqn_td_args* a, const float* weight, float* err
  * `deterministic` sums loss and penalty in one block in a fixed order. */
 int vdqn_td_loss_cql(const vdqn_td_args* a, const float* weight /* NULL = 1 */, float* err_out /* NULL ok */, float cql_alpha,
                      float* penalty /* pre-zeroed f32 scalar, NULL ok */, void* stream);
+/* Held-out validation metrics of the same loss, forward only: the `eval_losses` list the reference reserves and never fills
+ * (train_q_network.py:183-186) and its `# checkpoint and eval` (:240).  One launch adds eight sums per category into
+ * acc (device f64 [n_cat][8], 8-byte aligned, ACCUMULATED into: the caller zeroes it once per validation pass).  With d, y and l(d)
+ * exactly vdqn_td_loss's f32 arithmetic, pen = vdqn_td_loss_cql's logsumexp_a q_before[b,c,:] - q_before[b,c,act[b]] (exactly 0 when
+ * n_act == 1) and vm = use_valid ? valid[b,c] : 1, every term is formed in f32, multiplied by vm last, converted to f64 and summed
+ * over b:
+ *   acc[c][0] += sum vm                 acc[c][1] += sum l(d) vm             acc[c][2] += sum |d| vm
+ *   acc[c][3] += sum Q(s,c,act[b]) vm   acc[c][4] += sum max_a Q(s,c,a) vm   acc[c][5] += sum y vm
+ *   acc[c][6] += sum pen vm             acc[c][7] += sum [argmax_a Q(s,c,.) == act[b]] vm   (first maximum)
+ * One block per category, no atomics, a fixed summation order that depends on batch, n_cat and n_act alone (written out in
+ * video_dqn_amd/csrc/eval.hip): two runs agree bit for bit, and each table entry takes one f64 addition of the launch's sum.
+ * Reads q_before, q_after_online, q_after_target, act, rew, term, valid (when use_valid), batch, n_cat, n_act, ldq, gamma,
+ * clip_rect, linear, use_valid, loss_kind; ignores loss, dq, dq_f32, inv_count, dtype, deterministic, q_copy (NULL / 0 allowed).  Non-finite
+ * Q values are not special-cased; a row whose action is outside [0, n_act) adds nothing.  Fails by name before any launch for a
+ * null required pointer, batch / n_cat / n_act < 1, n_cat * n_act > ldq, loss_kind outside {0, 1}, acc not 8-byte aligned. */
+int vdqn_td_eval(const vdqn_td_args* a, double* acc, void* stream);
 
 /* Ground-truth branch (train_q_network.py:170-178): l = 0.5 (Qb*mask - gt)^2, mask = !isnan(gt) when
  * value_learning, else l = 0.5 (Qb - gt)^2.  gt is f32 [batch][n_cat] (NaN allowed). */
@@ -483,6 +499,18 @@ int vdqn_net_td_forward(vdqn_net* net, const vdqn_step_args* a, void* stream);
  * == 0 is vdqn_net_td_forward: the same launches and bits.  Fails by name for a negative or non-finite cql_alpha, and with
  * cql_alpha > 0 for train_on_ground_truth and for action_dim == 1.  Either architecture, every compute mode. */
 int vdqn_net_td_forward_cql(vdqn_net* net, const vdqn_step_args* a, float cql_alpha, float* cql_penalty, void* stream);
+/* One held-out batch of a validation pass (the reference's unfilled `eval_losses`, train_q_network.py:183-186, and `# checkpoint
+ * and eval`, :240): the online network over [before; after] (2 * batch samples), the target network over after on the side stream,
+ * then vdqn_td_eval on the two f32 Q tensors (ldq 64) into acc (device f64 [num_classes][8], accumulated into).  Forward only, both
+ * passes through the eval-mode path of either architecture ('basic' runs on its running statistics), no arg-max bytes, no backward
+ * workspace; nothing of the training state is written and no host synchronisation happens.
+ * Reads packed_online AS IT STANDS (the caller folds it once per validation pass with vdqn_net_pack_weights, flag word 0),
+ * packed_target, before, after, src_kind, batch, act, rew, term, valid, gamma, clip_rect, linear, use_valid, loss_kind, acts_online,
+ * acts_target; reads neither params, bnstats, bwd, grads, loss nor q_before.  1 <= batch and 2 * batch <= max_batch: the activation
+ * layouts are those of 2 * batch and batch samples, which fit the workspaces of any larger batch, so a short last batch needs no
+ * workspace of its own.  Refuses by name train_on_ground_truth, sample_weight, sample_err, aug_params, packed_frames and
+ * acts_samples != 0. */
+int vdqn_net_td_eval(vdqn_net* net, const vdqn_step_args* a, double* acc, void* stream);
 /* Stage s of the backward pass (0: head + layer4, 1: layer3, 2: layer2, layer1, stem).  With the overlap on, the stage's weight
  * gradients and the kernel that writes its range of `grads` run on the engine's side stream: after the call returns that range is
  * complete on vdqn_net_grad_stream(net), NOT on `stream`, which goes straight on to the next stage's data gradients.  The call

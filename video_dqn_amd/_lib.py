@@ -150,6 +150,8 @@ _SIGS = {
     "vdqn_polyak": (C.c_int, [c_vp, c_vp, c_i64, C.c_double, c_vp]),
     "vdqn_adam_polyak": (C.c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i32, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, c_vp,
                                    c_vp, C.c_double, c_vp]),
+    "vdqn_td_eval": (C.c_int, [C.POINTER(TdArgs), c_vp, c_vp]),
+    "vdqn_net_td_eval": (C.c_int, [c_vp, C.POINTER(StepArgs), c_vp, c_vp]),
 }
 COMM_UID_BYTES = 128
 EXPORTS = tuple(_SIGS)

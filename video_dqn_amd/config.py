@@ -41,7 +41,14 @@ target copy every TARGET_UPDATE_INTERVAL updates; in (0, 1]: soft / Polyak targe
 weights move as target <- target + TARGET_TAU * (online - target), inside the Adam launch on the GPU, in an f32 copy of all
 parameters from which the target network's weights are folded in front of every update; TARGET_UPDATE_INTERVAL is then unused;
 BatchNorm running statistics are copied from the online network, not averaged; 0.005 is the usual setting; the checkpoint gains
-`target_state_dict`; the TD branch only).
+`target_state_dict`; the TD branch only), VAL_DATASET ('' = off: the held-out set of the validation pass the reference reserves
+and never fills, train_q_network.py:183-186,240 — a path as DATASET takes it, or 'synthetic', a SyntheticTupleDataset of 1024 tuples
+seeded with SEED + 1), VAL_INTERVAL (0 = off; > 0: after every update t with t % VAL_INTERVAL == 0, in front of that update's
+checkpoint, rank 0 walks the validation set in index order in batches of BATCH_SIZE, the last short one included, without
+augmentation or importance weights — forward passes only, the metric sums kept on the GPU and read back once per pass — and logs
+avg_q_loss/val, td_abs_error/val, q_data/val, q_max/val, td_target/val, cql_penalty/val, action_agreement/val and the per-category
+avg_q_loss_cat<c>/val; the TD branch only; needs VAL_DATASET), VAL_BATCHES (0 = the whole validation set; > 0: its first
+VAL_BATCHES batches).
 """
 from __future__ import annotations
 
@@ -178,6 +185,9 @@ def get_cfg_defaults() -> CfgNode:
     c.LR_FINAL_FRACTION = 0.0
     c.CQL_ALPHA = 0.0             # > 0: conservative Q-learning penalty CQL_ALPHA * (logsumexp_a Q(s, .) - Q(s, a_data)) in the loss launch; 0 = off
     c.TARGET_TAU = 0.0            # in (0, 1]: soft target updates target <- target + TARGET_TAU * (online - target) after every optimiser step; 0 = hard copies
+    c.VAL_DATASET = ""            # held-out validation set: a path as DATASET takes it, or 'synthetic' (seeded with SEED + 1); '' = off
+    c.VAL_INTERVAL = 0            # > 0: a validation pass on rank 0 after every update t with t % VAL_INTERVAL == 0; 0 = off
+    c.VAL_BATCHES = 0             # > 0: only the first VAL_BATCHES batches of the validation set; 0 = the whole set
     return c
 
 

@@ -1435,6 +1435,53 @@ extern "C" int vdqn_net_td_forward_cql(vdqn_net* net, const vdqn_step_args* a, f
   return td_forward_impl(net, a, cql_alpha, cql_penalty, stream);
 }
 
+// One held-out batch of a validation pass (train_q_network.py:183-186 `eval_losses`, :240 `# checkpoint and eval`): the frames
+// packed as td_forward_impl packs them, the target pass over s' on the side stream beside the online pass over [s; s'] — both
+// through forward_impl, i.e. eval-mode BatchNorm in either architecture, with grad_samples = 0 (no arg-max bytes) — then the
+// metrics launch on the two qf tensors.  `packed_online` is read as the caller folded it; nothing but the two activation
+// workspaces and `acc` is written.  The layouts are those of 2 * batch and batch samples: prefixes of the workspaces of any larger batch.
+extern "C" int vdqn_net_td_eval(vdqn_net* net, const vdqn_step_args* a, double* acc, void* stream) {
+  VDQN_CHECK(net && a && acc, "vdqn_net_td_eval: null arg");
+  VDQN_CHECK(!a->train_on_ground_truth, "vdqn_net_td_eval: train_on_ground_truth: the ground-truth branch has no target network and no TD error to validate");
+  VDQN_CHECK(!a->sample_weight, "vdqn_net_td_eval: sample_weight is given: validation metrics are unweighted");
+  VDQN_CHECK(!a->sample_err, "vdqn_net_td_eval: sample_err is given: the metrics launch writes no per-sample errors");
+  VDQN_CHECK(!a->aug_params, "vdqn_net_td_eval: aug_params are given: validation frames are not augmented");
+  VDQN_CHECK(!a->packed_frames, "vdqn_net_td_eval: packed_frames are given: the validation pass packs its own frames");
+  VDQN_CHECK(a->acts_samples == 0, "vdqn_net_td_eval: acts_samples %d must be 0", a->acts_samples);
+  VDQN_CHECK(a->packed_online && a->packed_target && a->before && a->after && a->act && a->rew && a->term && a->acts_online && a->acts_target,
+             "vdqn_net_td_eval: null buffer");
+  VDQN_CHECK(!a->use_valid || a->valid, "vdqn_net_td_eval: use_valid without valid mask");
+  const int B = a->batch;
+  VDQN_CHECK(B >= 1 && 2 * (int64_t)B <= net->cfg.max_batch, "vdqn_net_td_eval: batch %d needs max_batch >= 2 * batch (max_batch %d)", B, net->cfg.max_batch);
+  VDQN_CHECK(a->loss_kind == 0 || a->loss_kind == 1, "vdqn_net_td_eval: loss_kind %d (0 = half squared error, 1 = Huber)", a->loss_kind);
+  VDQN_CHECK((((uintptr_t)acc) & 7) == 0, "vdqn_net_td_eval: acc must be 8-byte aligned");
+  hipStream_t st = (hipStream_t)stream;
+  const int F = net->cfg.num_frames, dt = net->cfg.dtype;
+  const ActLayout A = act_layout(net, 2 * B), T = act_layout(net, B);
+  unsigned char* ao = (unsigned char*)a->acts_online;
+  unsigned char* at = (unsigned char*)a->acts_target;
+  const int64_t frame_bytes = (int64_t)115 * 115 * 16 * net->esz;
+  hipStream_t tst = fork_side(net, st);  // == st when the overlap is off; ordered behind the previous batch's metrics launch
+  RC(vdqn_pack_input(a->before, a->src_kind, ao + A.t_in, B * F, dt, tst));
+  RC(vdqn_pack_input(a->after, a->src_kind, ao + A.t_in + (int64_t)B * F * frame_bytes, B * F, dt, tst));
+  if (tst != st) join_side(net, st);  // packed input ready for the online pass
+  RC(forward_impl(net, (const unsigned char*)a->packed_target, ao + A.t_in + (int64_t)B * F * frame_bytes, B, at, T, tst, false, 0));
+  RC(forward_impl(net, (const unsigned char*)a->packed_online, ao + A.t_in, 2 * B, ao, A, st, false, 0));
+  if (tst != st) join_side(net, st);
+  const float* qf_online = reinterpret_cast<const float*>(ao + A.qf);
+  vdqn_td_args t;
+  memset(&t, 0, sizeof(t));
+  t.q_before = qf_online;
+  t.q_after_online = qf_online + (size_t)B * 64;
+  t.q_after_target = reinterpret_cast<const float*>(at + T.qf);
+  t.act = a->act; t.rew = a->rew; t.term = a->term; t.valid = a->valid;
+  t.batch = B; t.n_cat = net->cfg.num_classes; t.n_act = net->cfg.action_dim; t.ldq = 64;
+  t.gamma = a->gamma;
+  t.clip_rect = a->clip_rect; t.linear = a->linear; t.use_valid = a->use_valid;
+  t.loss_kind = a->loss_kind;
+  return vdqn_td_eval(&t, acc, st);
+}
+
 namespace {
 
 // backward of BasicBlock b (gradient of its output, already ReLU-masked, is in g_o[b])

@@ -387,6 +387,8 @@ class TDStepper:
                 self.clip_out = torch.zeros(2, dtype=torch.float32, device=dev)
             if self.target_tau > 0:
                 self.target_params = torch.empty_like(net.params)
+        self.eval_acc = None   # f64 [num_classes][8] metric sums of the validation pass, allocated by the first eval_begin
+        self.val_history = []  # (update number, eval_result()) of every validation pass the trainer ran
         self.adam_step = 0
         self.sample_number = 0
         self._grad_stream = None  # torch view of the engine's side stream (vdqn_net_grad_stream)
@@ -620,6 +622,61 @@ class TDStepper:
                     self._adam_range(pos, b, self.adam_step)
                 pos = max(pos, e)
         n.mark_dirty()
+
+    # ---- held-out validation (vdqn_net_td_eval): forward-only TD metrics summed on the device ---------------------------------
+    EVAL_SLOTS = ("count", "loss", "td_abs_error", "q_data", "q_max", "td_target", "cql_penalty", "action_agreement")
+
+    def eval_begin(self):
+        """Start a validation pass (the reference's unfilled `eval_losses`, train_q_network.py:183-186,240) on the current stream,
+        behind `step()`: fold `packed_online` in eval mode — every training update refolds that buffer at its top, so it is free
+        between updates — refold `packed_target` from the averaged weights under target_tau > 0, exactly as `step()` does in front
+        of an update, and zero `eval_acc` (f64 [num_classes][8]).  What orders the next update's weight fold behind the Adam
+        launches (stage 2's join of the gradient stream, `optimizer_step`'s wait for `_post_stream`) orders this fold the same way:
+        it is queued on the stream they were joined into.  Nothing of the training state is written."""
+        if self.gtb:
+            raise _lib.VdqnError("TDStepper.eval_begin: validation covers the TD branch only (train_on_ground_truth has no target network)")
+        n = self.net
+        with torch.cuda.device(n.device):
+            n.pack_weights(self.packed_online, with_dgrad=False)
+            if self.target_params is not None:
+                n.pack_weights(self.packed_target, with_dgrad=False, params=self.target_params)
+            if self.eval_acc is None:
+                self.eval_acc = torch.zeros((n.num_classes, 8), dtype=torch.float64, device=n.device)
+            else:
+                self.eval_acc.zero_()
+
+    def eval_batch(self, before, after, src_kind, act, rew, term, valid=None):
+        """Queue one held-out batch of 1 .. B samples behind `eval_begin`: the online pass over [s; s'], the target pass over s' and
+        the metrics launch that adds this batch's sums into `eval_acc`.  No host synchronisation."""
+        if self.eval_acc is None:
+            raise _lib.VdqnError("TDStepper.eval_batch: call eval_begin first")
+        nb = int(act.shape[0])
+        if not 1 <= nb <= self.B:
+            raise _lib.VdqnError(f"TDStepper.eval_batch: a batch of {nb} samples (1 .. {self.B})")
+        if self.rbr and valid is None:
+            raise _lib.VdqnError("TDStepper.eval_batch: remove_before_reward needs the valid mask")
+        keep = (before, after, act, rew, term, valid)  # keep inputs alive until the launches are queued
+        with torch.cuda.device(self.net.device):
+            a = self._args(before, after, src_kind, act, rew, term, valid if valid is not None else self._ones, None)
+            a.batch = nb
+            _lib.check(self.lib.vdqn_net_td_eval(self.net.handle, C.byref(a), self.eval_acc.data_ptr(), _stream()), "vdqn_net_td_eval")
+        del keep
+
+    def eval_result(self) -> dict:
+        """Synchronise once and return the pass's means: {name: slot total / count} over all categories, {name + '_cat': [per
+        category]}, 'count' (the number of valid (sample, category) terms) and 'table' (the raw f64 [num_classes][8] sums, CPU)."""
+        if self.eval_acc is None:
+            raise _lib.VdqnError("TDStepper.eval_result: call eval_begin first")
+        table = self.eval_acc.cpu()  # (the one synchronisation of the pass)
+        total = table.sum(0)
+        nan = float("nan")
+        out = {"count": float(total[0]), "count_cat": [float(x) for x in table[:, 0]], "table": table}
+        for k, name in enumerate(self.EVAL_SLOTS):
+            if k == 0:
+                continue
+            out[name] = float(total[k] / total[0]) if total[0] > 0 else nan
+            out[name + "_cat"] = [float(table[c, k] / table[c, 0]) if table[c, 0] > 0 else nan for c in range(table.shape[0])]
+        return out
 
     def step(self, before, after, src_kind, act, rew, term, valid=None, gt=None, finish_allreduce=None, next_frames=None,
              weights=None, td_error=None, augment=None) -> torch.Tensor:

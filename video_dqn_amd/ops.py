@@ -214,6 +214,26 @@ def td_loss_cql(q_before, q_after_online, q_after_target, act, rew, term, valid=
     return loss, dq, dq32, penalty, err
 
 
+def td_eval(q_before, q_after_online, q_after_target, act, rew, term, valid=None, *, acc=None, n_cat=5, n_act=3, gamma=0.99,
+            clip_rect=True, linear=False, loss_kind="l2"):
+    """Held-out validation metrics of the TD loss (vdqn_td_eval): eight f64 sums per category — count, loss, |TD error|, Q(s, a_data),
+    max_a Q(s, a), the target y, the conservative penalty, agreement of the greedy action with the data — ADDED into acc (f64
+    [n_cat, 8] on the device; None: a fresh table of zeros).  q_*: f32 [B, ldq] (ldq >= n_cat * n_act).  Returns acc."""
+    lib = _lib.load()
+    B, ldq = q_before.shape
+    if acc is None:
+        acc = torch.zeros((n_cat, 8), dtype=torch.float64, device=q_before.device)
+    a = _lib.TdArgs()
+    a.q_before, a.q_after_online, a.q_after_target = _ptr(q_before), _ptr(q_after_online), _ptr(q_after_target)
+    a.act, a.rew, a.term, a.valid = _ptr(act), _ptr(rew), _ptr(term), _ptr(valid)
+    a.batch, a.n_cat, a.n_act, a.ldq = B, n_cat, n_act, ldq
+    a.gamma = gamma
+    a.clip_rect, a.linear, a.use_valid = int(clip_rect), int(linear), int(valid is not None)
+    a.loss_kind = LOSS_KINDS[loss_kind]
+    _lib.check(lib.vdqn_td_eval(C.byref(a), _ptr(acc), _stream()), "vdqn_td_eval")
+    return acc
+
+
 def gt_loss(q_before, act, gt, *, n_cat=5, n_act=3, inv_count=None, value_learning=False):
     lib = _lib.load()
     B, ldq = q_before.shape

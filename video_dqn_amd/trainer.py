@@ -179,6 +179,13 @@ def check_target(config) -> None:
         raise ValueError("TARGET_TAU needs the TD branch: TRAIN_ON_GROUND_TRUTH regresses on given targets and has no target network")
 
 
+def check_validation(config) -> None:
+    """VAL_DATASET / VAL_INTERVAL / VAL_BATCHES: raise ValueError naming the key (before any device work) for a negative or
+    non-integer value, for VAL_INTERVAL > 0 without VAL_DATASET, and for VAL_INTERVAL > 0 on the ground-truth branch."""
+    from .validate import check_config
+    check_config(config)
+
+
 def _to_device_batch(batch, device, num_classes=5):
     before, after, act, rew, term, gt, valid = batch
     nb = dict(non_blocking=True)
@@ -267,6 +274,7 @@ def run_train(config, resume_from=-1, max_steps=None, rank=0, world_size=1, log=
     check_optim(config)
     check_cql(config)
     check_target(config)
+    check_validation(config)
     cql_alpha = float(getattr(config, "CQL_ALPHA", 0.0))
     target_tau = float(getattr(config, "TARGET_TAU", 0.0))
     clip_norm, weight_decay = float(getattr(config, "GRAD_CLIP_NORM", 0.0)), float(getattr(config, "WEIGHT_DECAY", 0.0))
@@ -470,6 +478,12 @@ def run_train(config, resume_from=-1, max_steps=None, rank=0, world_size=1, log=
     stepper.sample_number = sample_number
     stepper.replay = replay  # the run's PrioritizedSampler (PRIORITIZED_REPLAY), None otherwise: returned with the stepper
     stepper.augmenter = augmenter  # the run's Augmenter (AUG_SHIFT_PAD / AUG_FLIP), None otherwise
+    # VAL_INTERVAL > 0: the held-out pass (video_dqn_amd/validate.py) on rank 0 alone; the other ranks wait in the next update's
+    # first collective.  Off: nothing is built, no launch differs
+    validator = None
+    if int(getattr(config, "VAL_INTERVAL", 0)) > 0 and rank == 0:
+        from .validate import Validator
+        validator = Validator(config, log=log)
     if replay is not None:
         iterator = store.prioritized_batches(replay, sample_number)
 
@@ -540,6 +554,8 @@ def run_train(config, resume_from=-1, max_steps=None, rank=0, world_size=1, log=
                 config.writer.add_scalar("cql_penalty/train", cql_pen[1] * world_size, cql_pen[0])
             if log_now and replay is not None:
                 config.writer.add_scalar("per/beta", replay.beta(sample_number), sample_number)  # (host arithmetic: nothing read back)
+            if validator is not None and validator.due(sample_number):  # :240 `# checkpoint and eval`: in front of the checkpoint
+                validator.run(stepper, sample_number, writer=getattr(config, "writer", None))
             if sample_number % config.CHECKPOINT_INTERVAL == 0 and rank == 0:  # :241-247
                 torch.cuda.synchronize()
                 save_checkpoint(f"{config.folder}/models/sample{sample_number}.torch", sample_number, model, stepper,
