@@ -207,6 +207,15 @@ int vdqn_td_loss_weighted(const vdqn_td_args* a, const float* weight, float* err
  * `deterministic` sums loss and penalty in one block in a fixed order. */
 int vdqn_td_loss_cql(const vdqn_td_args* a, const float* weight /* NULL = 1 */, float* err_out /* NULL ok */, float cql_alpha,
                      float* penalty /* pre-zeroed f32 scalar, NULL ok */, void* stream);
+/* The three entries above with a per-sample discount (n-step returns, vdqn_nstep_walk below): sample_gamma (f32 [batch], required)
+ * gives sample b's discount where they take a->gamma, which is not read.  cql_alpha > 0: vdqn_td_loss_cql's launch; else weight !=
+ * NULL: vdqn_td_loss_weighted's; else vdqn_td_loss's (err_out then has to be NULL, as penalty has to be when cql_alpha is 0).  The
+ * choice is made at compile time inside the one kernel template: the instances behind the three entries above keep their loads and
+ * bits, and with sample_gamma[b] == gamma for every b this entry writes exactly their bits; a dq row and err_out[b] depend on their
+ * own sample's discount alone.  Fails by name, before any launch, for everything those entries refuse and for linear != 0
+ * (y = r + (Qa - 0.1) has no discount), a NULL sample_gamma and a negative or non-finite cql_alpha. */
+int vdqn_td_loss_nstep(const vdqn_td_args* a, const float* weight /* NULL ok */, float* err_out /* NULL ok */, float cql_alpha /* 0 = none */,
+                       float* penalty /* NULL ok */, const float* sample_gamma, void* stream);
 /* Held-out validation metrics of the same loss, forward only: the `eval_losses` list the reference reserves and never fills
  * (train_q_network.py:183-186) and its `# checkpoint and eval` (:240).  One launch adds eight sums per category into
  * acc (device f64 [n_cat][8], 8-byte aligned, ACCUMULATED into: the caller zeroes it once per validation pass).  With d, y and l(d)
@@ -491,6 +500,12 @@ typedef struct vdqn_step_args {
   const int32_t* aug_params;  /* optional device int32 [batch][4], 16-byte aligned: vdqn_net_td_forward packs `before` and `after`
                                  with vdqn_pack_input_aug (the same params for both) where it calls vdqn_pack_input otherwise; it
                                  then fails for src_kind != 0 and for packed_frames.  NULL: the plain pack. */
+  const float* sample_gamma;  /* optional [batch] per-sample discount (n-step returns: `after`, rew, term are then those vdqn_nstep_walk
+                                 folded along each sample's chain): the loss launch is vdqn_td_loss_nstep with it, and `gamma` is not
+                                 read.  TD branch without `linear` only: vdqn_net_td_forward(_cql) fail by name otherwise, and
+                                 vdqn_net_td_eval refuses it (validation stays one-step).  NULL: the scalar `gamma`.  Added at the end of
+                                 the struct without a change of vdqn_abi_version(): a binding that predates it fails the
+                                 vdqn_abi_struct_size(6) comparison at load time. */
 } vdqn_step_args;
 int vdqn_net_td_forward(vdqn_net* net, const vdqn_step_args* a, void* stream);
 /* vdqn_net_td_forward with the conservative penalty (train_q_network.py:167,180): with cql_alpha > 0 the loss launch is
@@ -508,7 +523,8 @@ int vdqn_net_td_forward_cql(vdqn_net* net, const vdqn_step_args* a, float cql_al
  * packed_target, before, after, src_kind, batch, act, rew, term, valid, gamma, clip_rect, linear, use_valid, loss_kind, acts_online,
  * acts_target; reads neither params, bnstats, bwd, grads, loss nor q_before.  1 <= batch and 2 * batch <= max_batch: the activation
  * layouts are those of 2 * batch and batch samples, which fit the workspaces of any larger batch, so a short last batch needs no
- * workspace of its own.  Refuses by name train_on_ground_truth, sample_weight, sample_err, aug_params, packed_frames and
+ * workspace of its own.  Refuses by name train_on_ground_truth, sample_weight, sample_err, aug_params, packed_frames,
+ * sample_gamma (validation is one-step whatever the training target, so runs with different N_STEP are judged alike) and
  * acts_samples != 0. */
 int vdqn_net_td_eval(vdqn_net* net, const vdqn_step_args* a, double* acc, void* stream);
 /* Stage s of the backward pass (0: head + layer4, 1: layer3, 2: layer2, layer1, stem).  With the overlap on, the stage's weight
@@ -549,6 +565,24 @@ int vdqn_per_sample(const float* prio, int64_t n, int32_t global_batch, uint64_t
 /* prio[idx[j]] = (err[j] + 1e-6)^alpha for j < global_batch (f64 pow, stored as f32); an index that appears more than once takes
  * the value of its largest j.  Indices outside [0, n) are skipped. */
 int vdqn_per_update(float* prio, int64_t n, const int64_t* idx, const float* err, int32_t global_batch, double alpha, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * n-step returns (Sutton 1988; the multi-step target of Rainbow, Hessel et al., AAAI 2018) along a sampled row's chain in the logged
+ * data: the n-fold composition of the one-step backup of train_q_network.py:134-169, evaluated per category,
+ *   y = r(i0) + g (1 - t(i0)) [ r(i1) + g (1 - t(i1)) [ ... g (1 - t(i_{m-1})) Q_target(s^(m), argmax_a Q_online(s^(m), .)) ] ]
+ * folded into rew_n, term_n and disc so that y = rew_n + disc * (1 - term_n) * Q(s^(m)) is what vdqn_td_loss_nstep forms.  i_{k+1} =
+ * next_row[i_k] (int32 [n_rows]; a value outside [0, n_rows) means "no successor"), m <= n is the number of rows the chain provides,
+ * s^(m) the `after` frames of the last row walked.  No importance correction: with non-negative rewards the target is a lower bound
+ * of the optimal value.  The arithmetic, one thread per sample with every product and sum rounded on its own, is written out in
+ * video_dqn_amd/csrc/nstep.hip (tests/nstep_oracle.py restates it in numpy float32, bit for bit).
+ * ------------------------------------------------------------------------------------------------ */
+/* idx int64 [batch] (clamped to [0, n_rows)); rew / term f32 [n_rows][n_cat], n_cat 1..8; n 1..16; gamma finite.  Outputs: rew_n,
+ * term_n f32 [batch][n_cat], disc f32 [batch] (gamma^m), last_row int64 [batch], steps int32 [batch] (m).  No value of idx or
+ * next_row makes the kernel read outside its tables; cycles are legal (the walk ends at n rows).  Every check fails by name before
+ * any launch. */
+int vdqn_nstep_walk(const int64_t* idx, int32_t batch, const int32_t* next_row, const float* rew, const float* term, int64_t n_rows,
+                    int32_t n_cat, int32_t n, float gamma, float* rew_n, float* term_n, float* disc, int64_t* last_row, int32_t* steps,
+                    void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Random shift + left-right mirror augmentation of the training minibatch (DrQ / RAD style), fused into the input pack.  The

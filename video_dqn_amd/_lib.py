@@ -69,7 +69,7 @@ class StepArgs(C.Structure):
                 ("value_learning", c_i32),
                 ("acts_online", c_vp), ("acts_target", c_vp), ("bwd", c_vp), ("grads", c_vp), ("loss", c_vp),
                 ("q_before", c_vp), ("loss_kind", c_i32), ("packed_frames", c_vp), ("acts_samples", c_i32),
-                ("sample_weight", c_vp), ("sample_err", c_vp), ("aug_params", c_vp)]
+                ("sample_weight", c_vp), ("sample_err", c_vp), ("aug_params", c_vp), ("sample_gamma", c_vp)]
 
 
 ALLREDUCE_FN = C.CFUNCTYPE(None, c_vp, c_vp, c_i64, c_vp)  # vdqn_allreduce_fn(user, buf, count, stream)
@@ -152,6 +152,8 @@ _SIGS = {
                                    c_vp, C.c_double, c_vp]),
     "vdqn_td_eval": (C.c_int, [C.POINTER(TdArgs), c_vp, c_vp]),
     "vdqn_net_td_eval": (C.c_int, [c_vp, C.POINTER(StepArgs), c_vp, c_vp]),
+    "vdqn_td_loss_nstep": (C.c_int, [C.POINTER(TdArgs), c_vp, c_vp, c_f32, c_vp, c_vp, c_vp]),
+    "vdqn_nstep_walk": (C.c_int, [c_vp, c_i32, c_vp, c_vp, c_vp, c_i64, c_i32, c_i32, c_f32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
 }
 COMM_UID_BYTES = 128
 EXPORTS = tuple(_SIGS)

@@ -48,7 +48,13 @@ checkpoint, rank 0 walks the validation set in index order in batches of BATCH_S
 augmentation or importance weights — forward passes only, the metric sums kept on the GPU and read back once per pass — and logs
 avg_q_loss/val, td_abs_error/val, q_data/val, q_max/val, td_target/val, cql_penalty/val, action_agreement/val and the per-category
 avg_q_loss_cat<c>/val; the TD branch only; needs VAL_DATASET), VAL_BATCHES (0 = the whole validation set; > 0: its first
-VAL_BATCHES batches).
+VAL_BATCHES batches), N_STEP (1 = off, the reference's one-step target; 2 .. 16: n-step returns — the target of a sampled row is the
+N_STEP-fold composition of the one-step backup along the row's chain in the logged data, the row that follows row r being the row
+whose first `before` frame is r's first `after` frame, found in the shard index as it is; rewards, terminals and the discount
+gamma^m are folded by one launch on the GPU per update and s' is the `after` frame of the last of the m <= N_STEP rows the chain
+provides, so every sample still costs one s' forward; no importance correction: with non-negative rewards the target is a lower
+bound of the optimal value; the sampled rows are those of N_STEP 1 under the same seed; the TD branch without LINEAR on a
+decoded-frame shard dataset held in full in HBM on every rank; validation stays one-step).
 """
 from __future__ import annotations
 
@@ -188,6 +194,7 @@ def get_cfg_defaults() -> CfgNode:
     c.VAL_DATASET = ""            # held-out validation set: a path as DATASET takes it, or 'synthetic' (seeded with SEED + 1); '' = off
     c.VAL_INTERVAL = 0            # > 0: a validation pass on rank 0 after every update t with t % VAL_INTERVAL == 0; 0 = off
     c.VAL_BATCHES = 0             # > 0: only the first VAL_BATCHES batches of the validation set; 0 = the whole set
+    c.N_STEP = 1                  # 2 .. 16: n-step returns along each sampled row's chain in the logged data, folded on the GPU; 1 = off
     return c
 
 

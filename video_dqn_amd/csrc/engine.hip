@@ -1343,6 +1343,8 @@ static int td_forward_impl(vdqn_net* net, const vdqn_step_args* a, float cql_alp
   VDQN_CHECK(((uintptr_t)a->aug_params & 15) == 0, "vdqn_net_td_forward: aug_params must be 16-byte aligned");
   VDQN_CHECK(!a->aug_params || a->src_kind == 0, "vdqn_net_td_forward: aug_params take uint8 NHWC frames (src_kind 0), not src_kind %d", a->src_kind);
   VDQN_CHECK(!a->aug_params || !a->packed_frames, "vdqn_net_td_forward: aug_params are given, but packed_frames were packed without them");
+  VDQN_CHECK(!a->sample_gamma || !gtb, "vdqn_net_td_forward: sample_gamma is given, but the ground-truth branch bootstraps nothing (train_on_ground_truth)");
+  VDQN_CHECK(!a->sample_gamma || !a->linear, "vdqn_net_td_forward: sample_gamma is given with linear: y = r + (Qa - 0.1) has no discount and no n-step form");
   hipStream_t st = (hipStream_t)stream;
   const int F = net->cfg.num_frames, dt = net->cfg.dtype;
   const int ns_online = step_layout_samples(net, a);
@@ -1408,7 +1410,8 @@ static int td_forward_impl(vdqn_net* net, const vdqn_step_args* a, float cql_alp
     t.loss_kind = a->loss_kind;
     t.deterministic = net->cfg.deterministic;
     t.q_copy = a->q_before;  // (the compact copy of Q(s) rides in the loss launch: no 2-D copy between the loss and the first data gradient)
-    if (cql_alpha > 0.f) RC(vdqn_td_loss_cql(&t, a->sample_weight, a->sample_err, cql_alpha, cql_penalty, st));
+    if (a->sample_gamma) RC(vdqn_td_loss_nstep(&t, a->sample_weight, a->sample_err, cql_alpha, cql_alpha > 0.f ? cql_penalty : nullptr, a->sample_gamma, st));
+    else if (cql_alpha > 0.f) RC(vdqn_td_loss_cql(&t, a->sample_weight, a->sample_err, cql_alpha, cql_penalty, st));
     else if (a->sample_weight) RC(vdqn_td_loss_weighted(&t, a->sample_weight, a->sample_err, st));
     else RC(vdqn_td_loss(&t, st));
   } else {
@@ -1447,6 +1450,7 @@ extern "C" int vdqn_net_td_eval(vdqn_net* net, const vdqn_step_args* a, double* 
   VDQN_CHECK(!a->sample_err, "vdqn_net_td_eval: sample_err is given: the metrics launch writes no per-sample errors");
   VDQN_CHECK(!a->aug_params, "vdqn_net_td_eval: aug_params are given: validation frames are not augmented");
   VDQN_CHECK(!a->packed_frames, "vdqn_net_td_eval: packed_frames are given: the validation pass packs its own frames");
+  VDQN_CHECK(!a->sample_gamma, "vdqn_net_td_eval: sample_gamma is given: validation is one-step (the scalar gamma), whatever the training target");
   VDQN_CHECK(a->acts_samples == 0, "vdqn_net_td_eval: acts_samples %d must be 0", a->acts_samples);
   VDQN_CHECK(a->packed_online && a->packed_target && a->before && a->after && a->act && a->rew && a->term && a->acts_online && a->acts_target,
              "vdqn_net_td_eval: null buffer");

@@ -309,8 +309,9 @@ __device__ __forceinline__ void add_partials(const float (&red)[N][16], int n_wa
 // ---------------------------------------------------------------------------------------------------------
 // d = Q(s)[b, col] - y for the taken action's column `col` of category c: the Double-DQN target (first arg-max of the online
 // Q(s'), the target network's value there, terminal mask, LINEAR / gamma, rect clip).  The only statement of the target: the loss
-// terms of every mode and the per-sample error take d from here.
-__device__ __forceinline__ float td_error_of(const vdqn_td_args& a, int b, int c, int col) {
+// terms of every mode and the per-sample error take d from here.  `gamma` is the discount of sample b: a.gamma, or the sample's own
+// (n-step returns: gamma^m of the m rows its chain walked, csrc/nstep.hip) in the instances with a per-sample discount.
+__device__ __forceinline__ float td_error_of(const vdqn_td_args& a, int b, int c, int col, float gamma) {
   const float qb = a.q_before[(size_t)b * a.ldq + col];
   const float* qo = a.q_after_online + (size_t)b * a.ldq + c * a.n_act;
   int best = 0;
@@ -325,7 +326,7 @@ __device__ __forceinline__ float td_error_of(const vdqn_td_args& a, int b, int c
   float qa = a.q_after_target[(size_t)b * a.ldq + c * a.n_act + best];
   qa = qa * (1.0f - a.term[b * a.n_cat + c]);
   const float r = a.rew[b * a.n_cat + c];
-  float y = a.linear ? r + (qa - 0.1f) : r + a.gamma * qa;
+  float y = a.linear ? r + (qa - 0.1f) : r + gamma * qa;
   if (a.clip_rect) y = fminf(fmaxf(y, 0.f), 1.f);
   return qb - y;
 }
@@ -349,6 +350,9 @@ __device__ __forceinline__ float td_error_of(const vdqn_td_args& a, int b, int c
 //     a category recomputes that category's m and sum from A loads (A is 3 here; the row is in cache), and the thread of the taken
 //     action adds the loss terms.  err[b] stays the raw mean |d| (priorities follow the TD error, not the penalty).
 // The block's sums are multiplied by inv_count and added to a.loss (a.penalty) with one atomic each; padding columns of dq are 0.
+// SG (vdqn_td_loss_nstep), also chosen at compile time: the discount of sample b is a.sg[b] where the other instances take a.gamma —
+// one more load per taken-action thread, nothing else; with sg[b] == gamma for every b the instance writes the bits of its SG = false
+// twin, and a row depends on its own sample's discount only.
 // Launch shapes: 256 threads and one element per thread.  A deterministic launch is ONE block that walks all elements (thread t
 // takes t, t + blockDim.x, ..; the block sum's fixed order): 256 threads for TD_PLAIN and TD_WEIGHTED, 1024 for TD_CQL — a quarter of
 // the serial passes.  __launch_bounds__(1024) is there for that launch alone, and it budgets the TD_CQL instances' 256-thread
@@ -359,8 +363,9 @@ struct td_kernel_args : vdqn_td_args {
   float* err;      // [batch] or NULL
   float* penalty;  // TD_CQL: f32 scalar or NULL
   float alpha;     // TD_CQL
+  const float* sg;  // SG: [batch] per-sample discount
 };
-template <typename T, int MODE>
+template <typename T, int MODE, bool SG>
 __global__ __launch_bounds__(MODE == TD_CQL ? 1024 : 256) void td_loss_kernel(const td_kernel_args a) {
   const int total = a.batch * a.ldq;
   constexpr int N_SUMS = MODE == TD_CQL ? 2 : 1;
@@ -383,7 +388,7 @@ __global__ __launch_bounds__(MODE == TD_CQL ? 1024 : 256) void td_loss_kernel(co
         g = a.alpha * p;
       }
       if (ac == act) {
-        const float d = td_error_of(a, b, c, col);
+        const float d = td_error_of(a, b, c, col, SG ? a.sg[b] : a.gamma);
         float l, dl;
         if (a.loss_kind == 1) {  // Huber, beta = 1 (torch.nn.functional.smooth_l1_loss)
           const float ad = fabsf(d);
@@ -413,7 +418,7 @@ __global__ __launch_bounds__(MODE == TD_CQL ? 1024 : 256) void td_loss_kernel(co
     if constexpr (MODE != TD_PLAIN) {
       if (col == 0 && a.err) {
         float e = 0.f;
-        for (int c = 0; c < a.n_cat; ++c) e += fabsf(td_error_of(a, b, c, c * a.n_act + (int)a.act[b])) * (a.use_valid ? a.valid[b * a.n_cat + c] : 1.0f);
+        for (int c = 0; c < a.n_cat; ++c) e += fabsf(td_error_of(a, b, c, c * a.n_act + (int)a.act[b], SG ? a.sg[b] : a.gamma)) * (a.use_valid ? a.valid[b * a.n_cat + c] : 1.0f);
         a.err[b] = e / (float)a.n_cat;
       }
     }
@@ -618,10 +623,11 @@ extern "C" int vdqn_axpy(float* y, const float* x, float alpha, int64_t n, void*
   return VDQN_OK;
 }
 
-// The three TD-loss entries: every check (each fails by the entry's name before any HIP call), then the one launch.
+// The TD-loss entries: every check (each fails by the entry's name before any HIP call), then the one launch.  sample_gamma != NULL
+// (vdqn_td_loss_nstep only) selects the instances with a per-sample discount.
 template <int MODE>
 static int td_loss_launch(const char* entry, const char* prof_name, const vdqn_td_args* a, const float* weight, float* err_out, float cql_alpha,
-                          float* penalty, void* stream) {
+                          float* penalty, const float* sample_gamma, void* stream) {
   VDQN_CHECK(a && a->q_before && a->q_after_online && a->q_after_target && a->act && a->rew && a->term && a->loss && (MODE != TD_WEIGHTED || weight),
              "%s: null arg", entry);
   VDQN_CHECK(!a->use_valid || a->valid, "%s: use_valid without valid mask", entry);
@@ -629,6 +635,7 @@ static int td_loss_launch(const char* entry, const char* prof_name, const vdqn_t
   if (MODE == TD_CQL) VDQN_CHECK(a->n_act >= 2, "%s: n_act is 1: with one action logsumexp_a Q - Q(a) is identically zero; use vdqn_td_loss", entry);
   VDQN_CHECK(a->dtype == VDQN_F32 || a->dtype == VDQN_BF16, "%s: bad dtype", entry);
   VDQN_CHECK(a->loss_kind == 0 || a->loss_kind == 1, "%s: loss_kind %d (0 = half squared error, 1 = Huber)", entry, a->loss_kind);
+  VDQN_CHECK(!sample_gamma || !a->linear, "%s: linear with a per-sample discount: y = r + (Qa - 0.1) has no discount and no n-step form", entry);
   if (MODE == TD_CQL)
     VDQN_CHECK(isfinite(cql_alpha) && cql_alpha > 0.f, "%s: cql_alpha %g must be finite and > 0 (without the penalty: vdqn_td_loss)", entry, (double)cql_alpha);
   const int threads = MODE == TD_CQL && a->deterministic ? 1024 : 256;
@@ -640,22 +647,41 @@ static int td_loss_launch(const char* entry, const char* prof_name, const vdqn_t
   k.err = err_out;
   k.penalty = penalty;
   k.alpha = cql_alpha;
-  if (a->dtype == VDQN_BF16) hipLaunchKernelGGL((td_loss_kernel<bf16raw, MODE>), dim3(g), dim3(threads), 0, (hipStream_t)stream, k);
-  else hipLaunchKernelGGL((td_loss_kernel<float, MODE>), dim3(g), dim3(threads), 0, (hipStream_t)stream, k);
+  k.sg = sample_gamma;
+  if (sample_gamma) {
+    if (a->dtype == VDQN_BF16) hipLaunchKernelGGL((td_loss_kernel<bf16raw, MODE, true>), dim3(g), dim3(threads), 0, (hipStream_t)stream, k);
+    else hipLaunchKernelGGL((td_loss_kernel<float, MODE, true>), dim3(g), dim3(threads), 0, (hipStream_t)stream, k);
+  } else {
+    if (a->dtype == VDQN_BF16) hipLaunchKernelGGL((td_loss_kernel<bf16raw, MODE, false>), dim3(g), dim3(threads), 0, (hipStream_t)stream, k);
+    else hipLaunchKernelGGL((td_loss_kernel<float, MODE, false>), dim3(g), dim3(threads), 0, (hipStream_t)stream, k);
+  }
   VDQN_LAUNCH_CHECK();
   return VDQN_OK;
 }
 
 extern "C" int vdqn_td_loss(const vdqn_td_args* a, void* stream) {
-  return td_loss_launch<TD_PLAIN>("vdqn_td_loss", "td_loss", a, nullptr, nullptr, 0.f, nullptr, stream);
+  return td_loss_launch<TD_PLAIN>("vdqn_td_loss", "td_loss", a, nullptr, nullptr, 0.f, nullptr, nullptr, stream);
 }
 
 extern "C" int vdqn_td_loss_weighted(const vdqn_td_args* a, const float* weight, float* err_out, void* stream) {
-  return td_loss_launch<TD_WEIGHTED>("vdqn_td_loss_weighted", "td_loss_w", a, weight, err_out, 0.f, nullptr, stream);
+  return td_loss_launch<TD_WEIGHTED>("vdqn_td_loss_weighted", "td_loss_w", a, weight, err_out, 0.f, nullptr, nullptr, stream);
 }
 
 extern "C" int vdqn_td_loss_cql(const vdqn_td_args* a, const float* weight, float* err_out, float cql_alpha, float* penalty, void* stream) {
-  return td_loss_launch<TD_CQL>("vdqn_td_loss_cql", "td_loss_cql", a, weight, err_out, cql_alpha, penalty, stream);
+  return td_loss_launch<TD_CQL>("vdqn_td_loss_cql", "td_loss_cql", a, weight, err_out, cql_alpha, penalty, nullptr, stream);
+}
+
+// The three modes with a per-sample discount (n-step returns): cql_alpha > 0 is vdqn_td_loss_cql, else weight != NULL is
+// vdqn_td_loss_weighted, else vdqn_td_loss — each with sample_gamma[b] where it takes a->gamma, which is not read.
+extern "C" int vdqn_td_loss_nstep(const vdqn_td_args* a, const float* weight, float* err_out, float cql_alpha, float* penalty,
+                                  const float* sample_gamma, void* stream) {
+  VDQN_CHECK(sample_gamma, "vdqn_td_loss_nstep: sample_gamma is NULL (the scalar discount: vdqn_td_loss, vdqn_td_loss_weighted, vdqn_td_loss_cql)");
+  VDQN_CHECK(isfinite(cql_alpha) && cql_alpha >= 0.f, "vdqn_td_loss_nstep: cql_alpha %g must be finite and >= 0 (0 = no penalty)", (double)cql_alpha);
+  if (cql_alpha > 0.f) return td_loss_launch<TD_CQL>("vdqn_td_loss_nstep", "td_loss_cql", a, weight, err_out, cql_alpha, penalty, sample_gamma, stream);
+  VDQN_CHECK(!penalty, "vdqn_td_loss_nstep: penalty is given, but cql_alpha is 0");
+  VDQN_CHECK(weight || !err_out, "vdqn_td_loss_nstep: err_out without weight (the unweighted launch writes no per-sample errors)");
+  if (weight) return td_loss_launch<TD_WEIGHTED>("vdqn_td_loss_nstep", "td_loss_w", a, weight, err_out, 0.f, nullptr, sample_gamma, stream);
+  return td_loss_launch<TD_PLAIN>("vdqn_td_loss_nstep", "td_loss", a, nullptr, nullptr, 0.f, nullptr, sample_gamma, stream);
 }
 
 extern "C" int vdqn_gt_loss(const float* q_before, const int64_t* act, const float* gt, float* loss, void* dq, float* dq_f32, int32_t batch,

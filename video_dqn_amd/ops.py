@@ -190,8 +190,12 @@ def _td_args(q_before, q_after_online, q_after_target, act, rew, term, valid, n_
 
 
 def td_loss(q_before, q_after_online, q_after_target, act, rew, term, valid=None, *, n_cat=5, n_act=3, gamma=0.99,
-            inv_count=None, clip_rect=True, linear=False, out_dtype=torch.float32, loss_kind="l2"):
-    """q_*: f32 [B, ldq] (ldq >= n_cat*n_act).  Returns (loss[1], dq[B, ldq] out_dtype, dq_f32)."""
+            inv_count=None, clip_rect=True, linear=False, out_dtype=torch.float32, loss_kind="l2", discount=None):
+    """q_*: f32 [B, ldq] (ldq >= n_cat*n_act).  Returns (loss[1], dq[B, ldq] out_dtype, dq_f32).  discount (f32 [B], n-step returns):
+    the per-sample discount in place of gamma (td_loss_nstep)."""
+    if discount is not None:
+        return td_loss_nstep(q_before, q_after_online, q_after_target, act, rew, term, valid, discount=discount, n_cat=n_cat, n_act=n_act,
+                             inv_count=inv_count, clip_rect=clip_rect, out_dtype=out_dtype, loss_kind=loss_kind, linear=linear)[:3]
     lib = _lib.load()
     a, loss, dq, dq32 = _td_args(q_before, q_after_online, q_after_target, act, rew, term, valid, n_cat, n_act, gamma, inv_count, clip_rect,
                                  linear, out_dtype, loss_kind)
@@ -201,10 +205,14 @@ def td_loss(q_before, q_after_online, q_after_target, act, rew, term, valid=None
 
 def td_loss_cql(q_before, q_after_online, q_after_target, act, rew, term, valid=None, *, cql_alpha, weights=None, with_err=False,
                 n_cat=5, n_act=3, gamma=0.99, inv_count=None, clip_rect=True, linear=False, out_dtype=torch.float32, loss_kind="l2",
-                deterministic=False):
+                deterministic=False, discount=None):
     """td_loss with the conservative Q-learning penalty (vdqn_td_loss_cql): cql_alpha * (logsumexp_a Q(s, .) - Q(s, act)) per sample
     and category, dq dense over the actions.  weights: optional f32 [B].  Returns (loss[1], dq[B, ldq] out_dtype, dq_f32,
-    penalty[1], err[B] or None)."""
+    penalty[1], err[B] or None).  discount (f32 [B], n-step returns): the per-sample discount in place of gamma (td_loss_nstep)."""
+    if discount is not None:
+        return td_loss_nstep(q_before, q_after_online, q_after_target, act, rew, term, valid, discount=discount, weights=weights,
+                             with_err=with_err, cql_alpha=cql_alpha, n_cat=n_cat, n_act=n_act, inv_count=inv_count, clip_rect=clip_rect,
+                             out_dtype=out_dtype, loss_kind=loss_kind, deterministic=deterministic, linear=linear)
     lib = _lib.load()
     a, loss, dq, dq32 = _td_args(q_before, q_after_online, q_after_target, act, rew, term, valid, n_cat, n_act, gamma, inv_count, clip_rect,
                                  linear, out_dtype, loss_kind, deterministic)
@@ -212,6 +220,40 @@ def td_loss_cql(q_before, q_after_online, q_after_target, act, rew, term, valid=
     err = torch.empty(q_before.shape[0], dtype=torch.float32, device=loss.device) if with_err else None
     _lib.check(lib.vdqn_td_loss_cql(C.byref(a), _ptr(weights), _ptr(err), float(cql_alpha), _ptr(penalty), _stream()), "vdqn_td_loss_cql")
     return loss, dq, dq32, penalty, err
+
+
+def td_loss_nstep(q_before, q_after_online, q_after_target, act, rew, term, valid=None, *, discount, weights=None, with_err=False,
+                  cql_alpha=0.0, n_cat=5, n_act=3, inv_count=None, clip_rect=True, out_dtype=torch.float32, loss_kind="l2",
+                  deterministic=False, linear=False):
+    """The TD loss with a per-sample discount (vdqn_td_loss_nstep; n-step returns): discount f32 [B] on the device stands where
+    td_loss / td_loss_cql take the scalar gamma.  cql_alpha > 0: the CQL launch; else weights given: the weighted launch (with_err
+    needs them); else the plain one.  Returns (loss[1], dq[B, ldq] out_dtype, dq_f32, penalty[1] or None, err[B] or None)."""
+    lib = _lib.load()
+    if discount is None or discount.dtype != torch.float32 or discount.numel() != q_before.shape[0] or not discount.is_contiguous():
+        raise ValueError(f"td_loss_nstep: discount must be a contiguous f32 [{q_before.shape[0]}] device tensor")
+    a, loss, dq, dq32 = _td_args(q_before, q_after_online, q_after_target, act, rew, term, valid, n_cat, n_act, 0.0, inv_count, clip_rect,
+                                 linear, out_dtype, loss_kind, deterministic)
+    penalty = torch.zeros(1, dtype=torch.float32, device=loss.device) if cql_alpha > 0 else None
+    err = torch.empty(q_before.shape[0], dtype=torch.float32, device=loss.device) if with_err else None
+    _lib.check(lib.vdqn_td_loss_nstep(C.byref(a), _ptr(weights), _ptr(err), float(cql_alpha), _ptr(penalty), _ptr(discount), _stream()),
+               "vdqn_td_loss_nstep")
+    return loss, dq, dq32, penalty, err
+
+
+def nstep_walk(idx, next_row, rew, term, *, n, gamma):
+    """vdqn_nstep_walk: fold the chain of every sampled row (idx int64 [B]; next_row int32 [N]; rew / term f32 [N, n_cat], all on the
+    device) into (rew_n [B, n_cat], term_n [B, n_cat], disc [B], last_row [B] int64, steps [B] int32)."""
+    lib = _lib.load()
+    B, dev = idx.shape[0], rew.device
+    n_cat = rew.shape[1]
+    rew_n = torch.empty((B, n_cat), dtype=torch.float32, device=dev)
+    term_n = torch.empty((B, n_cat), dtype=torch.float32, device=dev)
+    disc = torch.empty(B, dtype=torch.float32, device=dev)
+    last_row = torch.empty(B, dtype=torch.int64, device=dev)
+    steps = torch.empty(B, dtype=torch.int32, device=dev)
+    _lib.check(lib.vdqn_nstep_walk(_ptr(idx), B, _ptr(next_row), _ptr(rew), _ptr(term), rew.shape[0], n_cat, int(n), float(gamma), _ptr(rew_n),
+                                   _ptr(term_n), _ptr(disc), _ptr(last_row), _ptr(steps), _stream()), "vdqn_nstep_walk")
+    return rew_n, term_n, disc, last_row, steps
 
 
 def td_eval(q_before, q_after_online, q_after_target, act, rew, term, valid=None, *, acc=None, n_cat=5, n_act=3, gamma=0.99,

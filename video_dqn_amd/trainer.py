@@ -179,6 +179,30 @@ def check_target(config) -> None:
         raise ValueError("TARGET_TAU needs the TD branch: TRAIN_ON_GROUND_TRUTH regresses on given targets and has no target network")
 
 
+def check_nstep(config, world_size: int = 1) -> None:
+    """N_STEP: raise ValueError naming the key (before any device work) for a value that is not an integer in 1 .. 16 and, when it is
+    above 1, for every configuration the chain walk does not cover: the ground-truth branch, LINEAR, generated tuples, a
+    feather+JPEG dataset and DEVICE_RESIDENT_DATA 'off' (a chain's last frame may be any frame: the walk needs the full store in
+    HBM; its size and fit are checked once the dataset is opened)."""
+    from .nstep import check_config
+    n = getattr(config, "N_STEP", 1)
+    check_config(n)
+    if int(n) == 1:
+        return
+    if getattr(config, "TRAIN_ON_GROUND_TRUTH", False):
+        raise ValueError("N_STEP > 1 needs the TD branch: TRAIN_ON_GROUND_TRUTH regresses Q(s, a) on given targets and bootstraps nothing")
+    if getattr(config, "LINEAR", False):
+        raise ValueError("N_STEP > 1 does not cover LINEAR: y = r + (Qa - 0.1) has no discount and no n-step form")
+    if getattr(config, "SYNTHETIC_DATA", False) or config.DATASET in ("none", "synthetic"):
+        raise ValueError("N_STEP > 1 needs a fixed dataset with a successor relation: SYNTHETIC_DATA generates unrelated tuples on the fly")
+    if not is_shard_dir(config.DATASET):
+        raise ValueError("N_STEP > 1 needs a decoded-frame shard dataset held in HBM, not a feather+JPEG dataset "
+                         "(build one with python -m video_dqn_amd.shards)")
+    if str(getattr(config, "DEVICE_RESIDENT_DATA", "auto")).lower() == "off":
+        raise ValueError("N_STEP > 1 ends a chain at any frame of the dataset: it needs the frames in HBM, "
+                         "and DEVICE_RESIDENT_DATA is 'off'")
+
+
 def check_validation(config) -> None:
     """VAL_DATASET / VAL_INTERVAL / VAL_BATCHES: raise ValueError naming the key (before any device work) for a negative or
     non-integer value, for VAL_INTERVAL > 0 without VAL_DATASET, and for VAL_INTERVAL > 0 on the ground-truth branch."""
@@ -275,6 +299,8 @@ def run_train(config, resume_from=-1, max_steps=None, rank=0, world_size=1, log=
     check_cql(config)
     check_target(config)
     check_validation(config)
+    check_nstep(config, world_size)
+    n_step = int(getattr(config, "N_STEP", 1))
     cql_alpha = float(getattr(config, "CQL_ALPHA", 0.0))
     target_tau = float(getattr(config, "TARGET_TAU", 0.0))
     clip_norm, weight_decay = float(getattr(config, "GRAD_CLIP_NORM", 0.0)), float(getattr(config, "WEIGHT_DECAY", 0.0))
@@ -309,19 +335,25 @@ def run_train(config, resume_from=-1, max_steps=None, rank=0, world_size=1, log=
             sharded = world_size > 1 and bool(getattr(config, "RANK_SHARDED_DATA", True))
             gather_threads = int(getattr(config, "HOST_GATHER_THREADS", 0))
             headroom = 32 << 30  # activations, workspaces, allocator slack
-            if per:
-                # prioritized replay may draw any sample at any update: the full store on every rank, whatever RANK_SHARDED_DATA says
-                from .replay import check_config
-                check_config(float(config.PER_ALPHA), float(config.PER_BETA), B * world_size, len(dataset))
+            if per or n_step > 1:
+                # prioritized replay may draw any sample at any update, and an n-step chain may end at any frame: the full store on
+                # every rank, whatever RANK_SHARDED_DATA says
+                key = "PRIORITIZED_REPLAY" if per else "N_STEP > 1"
+                if per:
+                    from .replay import check_config
+                    check_config(float(config.PER_ALPHA), float(config.PER_BETA), B * world_size, len(dataset))
                 need = sum(np.load(p_, mmap_mode="r").shape[0] for p_ in dataset._paths) * 224 * 224 * 3
                 free, _ = torch.cuda.mem_get_info(torch.device(config.device))
                 fits = need + headroom < free
                 if world_size > 1:
                     fits = agree_all(fits, device=config.device)
                 if not fits:
-                    raise ValueError(f"PRIORITIZED_REPLAY needs the dataset in HBM: its frames ({need / 2**30:.1f} GiB + {headroom >> 30} GiB "
+                    raise ValueError(f"{key} needs the dataset in HBM: its frames ({need / 2**30:.1f} GiB + {headroom >> 30} GiB "
                                      f"of headroom) do not fit in {free / 2**30:.1f} GiB of free HBM" + (" on every rank" if world_size > 1 else ""))
-                if sharded:
+                if sharded and n_step > 1:
+                    log("N_STEP: every rank holds the full dataset in HBM (RANK_SHARDED_DATA does not apply: "
+                        "a chain's last frame may be any frame)")
+                if sharded and per:
                     log("PRIORITIZED_REPLAY: every rank holds the full dataset in HBM (RANK_SHARDED_DATA does not apply: "
                         "any sample may be drawn at any update)")
                 resident = True
@@ -401,6 +433,17 @@ def run_train(config, resume_from=-1, max_steps=None, rank=0, world_size=1, log=
                         allreduce_errors=((lambda: comm.launch_errors(replay.err_all)) if comm and replay else None),
                         grad_clip_norm=clip_norm, weight_decay=weight_decay, lr_fn=lr_fn, cql_alpha=cql_alpha,
                         target_tau=target_tau)
+    walker = None
+    if n_step > 1:
+        # the successor table from index.npz as it is (host, once), held on the device beside store.rew / store.term; the shares of
+        # chain lengths are host arithmetic on that table: nothing is read back
+        from .nstep import NStepWalker, chain_shares, successors
+        next_row = successors(dataset.before[:, 0], dataset.after[:, 0])
+        walker = NStepWalker(next_row, store.rew, store.term, B, n_step, float(config.GAMMA), model.engine.device)
+        shares = chain_shares(next_row, n_step)
+        log(f"n-step returns: N_STEP {n_step}, one chain walk per update over {len(next_row)} rows; chains of " +
+            ", ".join(f"{k + 1} row{'s' if k else ''}: {100 * s:.1f} %" for k, s in enumerate(shares)) +
+            " (terminals ignored); validation stays one-step")
     if target_tau > 0:
         log(f"soft target updates: target <- target + {target_tau:g} * (online - target) inside every Adam launch, the target weights "
             "folded from the average in front of every update; TARGET_UPDATE_INTERVAL is unused")
@@ -426,7 +469,8 @@ def run_train(config, resume_from=-1, max_steps=None, rank=0, world_size=1, log=
         iterator = None  # store.prioritized_batches, from the update after the resume point (below)
     elif store is not None:  # minibatches are gathered on the device; no loader, no host copies
         from .shards import RankShardedFrameStore as _RS
-        iterator = store.batches(B, config.SEED) if isinstance(store, _RS) else store.batches(B, config.SEED, rank, world_size)
+        # (N_STEP > 1 always holds the full DeviceFrameStore: `walker` is None on the rank-sharded path)
+        iterator = store.batches(B, config.SEED) if isinstance(store, _RS) else store.batches(B, config.SEED, rank, world_size, walker=walker)
     elif stream is not None:
         iterator = stream.batches()
     else:
@@ -478,6 +522,7 @@ def run_train(config, resume_from=-1, max_steps=None, rank=0, world_size=1, log=
     stepper.sample_number = sample_number
     stepper.replay = replay  # the run's PrioritizedSampler (PRIORITIZED_REPLAY), None otherwise: returned with the stepper
     stepper.augmenter = augmenter  # the run's Augmenter (AUG_SHIFT_PAD / AUG_FLIP), None otherwise
+    stepper.nstep = walker  # the run's NStepWalker (N_STEP > 1), None otherwise
     # VAL_INTERVAL > 0: the held-out pass (video_dqn_amd/validate.py) on rank 0 alone; the other ranks wait in the next update's
     # first collective.  Off: nothing is built, no launch differs
     validator = None
@@ -485,7 +530,7 @@ def run_train(config, resume_from=-1, max_steps=None, rank=0, world_size=1, log=
         from .validate import Validator
         validator = Validator(config, log=log)
     if replay is not None:
-        iterator = store.prioritized_batches(replay, sample_number)
+        iterator = store.prioritized_batches(replay, sample_number, walker=walker)
 
     running_loss = None
     late_loss = LateScalar()
@@ -520,7 +565,8 @@ def run_train(config, resume_from=-1, max_steps=None, rank=0, world_size=1, log=
                                 gt if config.TRAIN_ON_GROUND_TRUTH else None,
                                 finish_allreduce=(comm.finish if comm else None),
                                 weights=(item[8] if replay is not None else None),
-                                td_error=(replay.err if replay is not None else None), augment=aug_params)
+                                td_error=(replay.err if replay is not None else None), augment=aug_params,
+                                discount=(item[-1] if walker is not None else None))  # (gather_nstep appends it)
             if replay is not None:
                 replay.update()  # behind the loss launch (and, with N ranks, the error exchange that finish_allreduce joined)
             # every rank's `loss` is its share of the global mean (the TD kernel divides by the global batch): their SUM is the
