@@ -500,6 +500,11 @@ typedef struct vdqn_step_args {
   const int32_t* aug_params;  /* optional device int32 [batch][4], 16-byte aligned: vdqn_net_td_forward packs `before` and `after`
                                  with vdqn_pack_input_aug (the same params for both) where it calls vdqn_pack_input otherwise; it
                                  then fails for src_kind != 0 and for packed_frames.  NULL: the plain pack. */
+  const int32_t* aug_color;   /* optional device int32 [batch][4] {f_b, f_c, f_s, 0}, 16-byte aligned, indexed like aug_params (which must
+                                 be given as well): vdqn_net_td_forward packs `before` and `after` with vdqn_pack_input_aug_color (the
+                                 same factors for both).  NULL: no colour jitter.  vdqn_net_td_eval refuses it.  Added beside aug_params without a change
+                                 of vdqn_abi_version(), as sample_gamma was: a binding that predates it fails the
+                                 vdqn_abi_struct_size(6) comparison at load time. */
   const float* sample_gamma;  /* optional [batch] per-sample discount (n-step returns: `after`, rew, term are then those vdqn_nstep_walk
                                  folded along each sample's chain): the loss launch is vdqn_td_loss_nstep with it, and `gamma` is not
                                  read.  TD branch without `linear` only: vdqn_net_td_forward(_cql) fail by name otherwise, and
@@ -523,7 +528,7 @@ int vdqn_net_td_forward_cql(vdqn_net* net, const vdqn_step_args* a, float cql_al
  * packed_target, before, after, src_kind, batch, act, rew, term, valid, gamma, clip_rect, linear, use_valid, loss_kind, acts_online,
  * acts_target; reads neither params, bnstats, bwd, grads, loss nor q_before.  1 <= batch and 2 * batch <= max_batch: the activation
  * layouts are those of 2 * batch and batch samples, which fit the workspaces of any larger batch, so a short last batch needs no
- * workspace of its own.  Refuses by name train_on_ground_truth, sample_weight, sample_err, aug_params, packed_frames,
+ * workspace of its own.  Refuses by name train_on_ground_truth, sample_weight, sample_err, aug_params, aug_color, packed_frames,
  * sample_gamma (validation is one-step whatever the training target, so runs with different N_STEP are judged alike) and
  * acts_samples != 0. */
 int vdqn_net_td_eval(vdqn_net* net, const vdqn_step_args* a, double* acc, void* stream);
@@ -607,6 +612,28 @@ int vdqn_aug_swap_actions(const int64_t* act, const int32_t* params, int32_t n, 
  * src, dst and params 16-byte aligned.  All-zero params give vdqn_pack_input's output. */
 int vdqn_pack_input_aug(const void* src, void* dst, int32_t n_img, int32_t frames_per_sample, const int32_t* params,
                         int32_t n_params, int32_t dtype, void* stream);
+
+/* Colour jitter (brightness, contrast, saturation as torchvision's ColorJitter draws them: one uniform factor in [1 - J, 1 + J] each),
+ * defined as a map from uint8 pixels to uint8 pixels in integer arithmetic, so the packed operand still equals vdqn_pack_input of
+ * host-augmented frames bit for bit (tests/aug_color_oracle.py).  One int32 {f_b, f_c, f_s, 0} per SAMPLE, Q8 (256 = factor 1.0),
+ * shared by its frames and by s and s'.  "/ 256" is floor division (an arithmetic shift).  One source pixel (R, G, B), in this order:
+ *   saturation:  g = (77 R + 150 G + 29 B + 128) / 256;   v = clamp(g + ((v - g) * f_s + 128) / 256, 0, 255)   for v in R, G, B
+ *   brightness:  v = min(255, (v * f_b + 128) / 256)
+ *   contrast:    v = clamp(128 + ((v - 128) * f_c + 128) / 256, 0, 255)          (pivot: mid-grey 128, no per-frame mean)
+ * then vdqn_pack_input's normalisation.  (256, 256, 256) is the identity on every byte.  Hue, white balance, blur and resized crops
+ * are not covered. */
+/* color[i] (int32 [n][4], 16-byte aligned) = the draw of sample first + i of a global batch of `global_batch` samples at update `step`:
+ *   h = splitmix64(splitmix64(seed ^ 0x415547434F4C5231 "AUGCOLR1") ^ (step * global_batch + first + i))
+ *   f_k = 256 - j_k + ((((h >> 16 k) & 0xFFFF) * (2 j_k + 1)) >> 16)     k = 0 brightness (jb), 1 contrast (jc), 2 saturation (js)
+ * uniform over the 2 j_k + 1 values of [256 - j_k, 256 + j_k]; word 3 is 0.  jb, jc, js are Q8 half-widths int(J * 256 + 0.5), 0 .. 256.
+ * A stream of its own: vdqn_aug_draw's values at the same seed and update do not depend on it.  Slices as vdqn_aug_draw. */
+int vdqn_aug_draw_color(uint64_t seed, uint64_t step, int32_t global_batch, int32_t first, int32_t n, int32_t jb, int32_t jc,
+                        int32_t js /* Q8 half-widths, 0 .. 256 */, int32_t* color, void* stream);
+/* vdqn_pack_input_aug with the colour transform applied to every source pixel it reads: frame i takes params[(i / frames_per_sample)
+ * % n_params] and color[(i / frames_per_sample) % n_params] (both int32 [n_params][4], 16-byte aligned).  Every factor is clamped to
+ * [0, 512] before use and word 3 is ignored: any int32 content is safe.  Factors (256, 256, 256) give vdqn_pack_input_aug's output. */
+int vdqn_pack_input_aug_color(const void* src, void* dst, int32_t n_img, int32_t frames_per_sample, const int32_t* params,
+                              const int32_t* color, int32_t n_params, int32_t dtype, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Data-parallel exchange: one process per GPU, the flat f32 gradient SUM-all-reduced over RCCL (xGMI)

@@ -9,6 +9,13 @@ frames bit for bit (video_dqn_amd/csrc/augment.hip has the arithmetic, tests/aug
 sample's action label has ``AUG_FLIP_ACTIONS`` exchanged (a left turn becomes a right turn).  Three small launches and no host
 round trip per update.
 
+Colour jitter (``AUG_BRIGHTNESS``, ``AUG_CONTRAST``, ``AUG_SATURATION``: the half-width J of a uniform factor range [1 - J, 1 + J],
+as torchvision's ``ColorJitter``) is the photometric half: one ``(f_b, f_c, f_s)`` in Q8 per update and per sample from a stream of
+its own, shared by the sample's frames and by s and s', applied as a map from uint8 pixels to uint8 pixels in integer arithmetic —
+saturation, then brightness, then contrast about mid-grey 128 — inside the same pack launch (``vdqn_pack_input_aug_color``), so the
+operand still equals ``vdqn_pack_input`` of host-augmented frames bit for bit (tests/aug_color_oracle.py).  One more small launch
+per update.
+
 Data parallelism keeps N ranks == one process on the big batch: every rank draws its slice of the one global draw.
 """
 from __future__ import annotations
@@ -18,10 +25,19 @@ import torch
 from . import _lib
 
 MAX_PAD = 32  # vdqn_aug_draw (include/vdqn.h)
+COLOR_KEYS = ("AUG_BRIGHTNESS", "AUG_CONTRAST", "AUG_SATURATION")  # the order of the factors in a colour row
 
 
-def check_config(pad, flip, flip_actions) -> None:
+def jq(j: float) -> int:
+    """The Q8 half-width vdqn_aug_draw_color takes: int(J * 256 + 0.5), 0 .. 256 for J in [0, 1]."""
+    return int(float(j) * 256 + 0.5)
+
+
+def check_config(pad, flip, flip_actions, brightness=0.0, contrast=0.0, saturation=0.0) -> None:
     """Raise ValueError, naming the config key, for values the augmentation does not take (host only: no device work)."""
+    for key, j in zip(COLOR_KEYS, (brightness, contrast, saturation)):
+        if isinstance(j, bool) or not isinstance(j, (int, float)) or not 0 <= j <= 1:  # (NaN fails both comparisons)
+            raise ValueError(f"{key} must be a number in [0, 1] (0 = off: the factor is drawn from [1 - {key}, 1 + {key}]), got {j!r}")
     if isinstance(pad, bool) or not isinstance(pad, int) or not 0 <= pad <= MAX_PAD:
         raise ValueError(f"AUG_SHIFT_PAD must be an integer in [0, {MAX_PAD}] (got {pad!r})")
     if not isinstance(flip, bool):
@@ -48,26 +64,50 @@ def aug_draw(seed: int, step: int, global_batch: int, first: int, n: int, pad: i
     return out
 
 
-def pack_input_aug(src: torch.Tensor, params: torch.Tensor, frames_per_sample: int, dtype: torch.dtype) -> torch.Tensor:
-    """uint8 NHWC [n][224][224][3] frames + int32 [*][4] params -> the augmented stem operand [n][115][115][16]."""
+def aug_draw_color(seed: int, step: int, global_batch: int, first: int, n: int, jb: int, jc: int, js: int, device="cuda",
+                   out: torch.Tensor = None) -> torch.Tensor:
+    """vdqn_aug_draw_color on the current stream -> int32 [n][4] {f_b, f_c, f_s, 0} (Q8, 256 = 1.0) of samples first .. first + n of
+    the global batch; jb, jc, js are the Q8 half-widths (`jq`)."""
+    dev = torch.device(device) if out is None else out.device
+    with torch.cuda.device(dev):
+        if out is None:
+            out = torch.empty((n, 4), dtype=torch.int32, device=dev)
+        _lib.check(_lib.load().vdqn_aug_draw_color(_u64(seed), _u64(step), global_batch, first, n, jb, jc, js, out.data_ptr(),
+                                                   torch.cuda.current_stream().cuda_stream), "vdqn_aug_draw_color")
+    return out
+
+
+def pack_input_aug(src: torch.Tensor, params: torch.Tensor, frames_per_sample: int, dtype: torch.dtype,
+                   color: torch.Tensor = None) -> torch.Tensor:
+    """uint8 NHWC [n][224][224][3] frames + int32 [*][4] params (+ int32 [*][4] colour factors, as many rows as params) -> the
+    augmented stem operand [n][115][115][16]."""
     if src.dtype != torch.uint8 or not src.is_contiguous() or params.dtype != torch.int32 or not params.is_contiguous():
         raise _lib.VdqnError("pack_input_aug: src must be contiguous uint8 NHWC frames and params contiguous int32 [*][4]")
+    if color is not None and (color.dtype != torch.int32 or not color.is_contiguous() or color.numel() != params.numel()
+                              or color.device != params.device):
+        raise _lib.VdqnError("pack_input_aug: color must be contiguous int32 [*][4] with as many rows as params, on their device")
     n_img = src.numel() // (224 * 224 * 3)
     with torch.cuda.device(src.device):
         dst = torch.empty((n_img, 115, 115, 16), dtype=dtype, device=src.device)
         code = _lib.VDQN_BF16 if dtype == torch.bfloat16 else _lib.VDQN_F32
-        _lib.check(_lib.load().vdqn_pack_input_aug(src.data_ptr(), dst.data_ptr(), n_img, frames_per_sample, params.data_ptr(),
-                                                   params.numel() // 4, code, torch.cuda.current_stream().cuda_stream), "vdqn_pack_input_aug")
+        st = torch.cuda.current_stream().cuda_stream
+        if color is not None:
+            _lib.check(_lib.load().vdqn_pack_input_aug_color(src.data_ptr(), dst.data_ptr(), n_img, frames_per_sample, params.data_ptr(),
+                                                             color.data_ptr(), params.numel() // 4, code, st), "vdqn_pack_input_aug_color")
+        else:
+            _lib.check(_lib.load().vdqn_pack_input_aug(src.data_ptr(), dst.data_ptr(), n_img, frames_per_sample, params.data_ptr(),
+                                                       params.numel() // 4, code, st), "vdqn_pack_input_aug")
     return dst
 
 
 class Augmenter:
     """The per-update draw of one rank: ``draw(step)`` -> this rank's int32 [B][4] on the device (valid until the next call),
-    ``actions(act)`` -> the action labels with ``flip_actions`` exchanged for the mirrored samples of that draw."""
+    ``actions(act)`` -> the action labels with ``flip_actions`` exchanged for the mirrored samples of that draw.  With a colour
+    half-width above 0, ``draw`` also fills ``color`` (int32 [B][4] {f_b, f_c, f_s, 0}; None when all three are 0)."""
 
     def __init__(self, batch: int, device, pad: int = 0, flip: bool = False, flip_actions=(1, 2), seed: int = 0, rank: int = 0,
-                 world_size: int = 1):
-        check_config(pad, flip, flip_actions)
+                 world_size: int = 1, brightness: float = 0.0, contrast: float = 0.0, saturation: float = 0.0):
+        check_config(pad, flip, flip_actions, brightness, contrast, saturation)
         self.lib = _lib.load()
         self.B, self.rank, self.world = int(batch), int(rank), int(world_size)
         self.G = self.B * self.world
@@ -76,10 +116,15 @@ class Augmenter:
         with torch.cuda.device(self.device):
             self.params = torch.zeros((self.B, 4), dtype=torch.int32, device=self.device)
             self._act = torch.zeros(self.B, dtype=torch.int64, device=self.device)
-        self.last_step = None  # the update number of the draw `params` holds
+            self.jq = (jq(brightness), jq(contrast), jq(saturation))
+            self.color = torch.empty((self.B, 4), dtype=torch.int32, device=self.device) if any(self.jq) else None
+        self.last_step = None  # the update number of the draw `params` (and `color`) hold
 
     def draw(self, step: int) -> torch.Tensor:
-        aug_draw(self.seed, step, self.G, self.rank * self.B, self.B, self.pad, self.flip, out=self.params)
+        if self.pad > 0 or self.flip or self.color is None:  # (colour alone: `params` stays the zeros vdqn_aug_draw gives for pad 0)
+            aug_draw(self.seed, step, self.G, self.rank * self.B, self.B, self.pad, self.flip, out=self.params)
+        if self.color is not None:
+            aug_draw_color(self.seed, step, self.G, self.rank * self.B, self.B, *self.jq, out=self.color)
         self.last_step = int(step)
         return self.params
 

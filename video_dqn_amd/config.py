@@ -27,7 +27,10 @@ shift augmentation — every update shows each sample padded by this many edge-r
 draw per sample shared by its frames and by s and s', fused into the input pack on the GPU), AUG_FLIP (False: mirror each sample
 left-right with probability 1/2, s and s' together), AUG_FLIP_ACTIONS ([1, 2]: the two action labels a mirror exchanges — turn left
 and turn right; from dataloaders/gibson.py:76 and habitat_test_env.py:242 under Habitat-API 0.1.3's STOP 0 / FORWARD 1 / LEFT 2 /
-RIGHT 3, unverified here, hence a key), GRAD_CLIP_NORM (0.0 = off; > 0: the whole gradient is rescaled so that its global L2 norm
+RIGHT 3, unverified here, hence a key), AUG_BRIGHTNESS, AUG_CONTRAST, AUG_SATURATION (0.0 = off, each in [0, 1]: colour jitter — the
+half-width J of a uniform factor range [1 - J, 1 + J] as torchvision's ColorJitter; one factor triple per update and sample, shared by
+its frames and by s and s', applied to the uint8 pixels in integer arithmetic, saturation then brightness then contrast about
+mid-grey 128, inside the same input pack on the GPU), GRAD_CLIP_NORM (0.0 = off; > 0: the whole gradient is rescaled so that its global L2 norm
 is at most this, torch.nn.utils.clip_grad_norm_: coef = min(1, max_norm / (norm + 1e-6)), norm and coefficient computed on the GPU
 and never read back for the update), WEIGHT_DECAY (0.0: decoupled, as torch.optim.AdamW: p <- p * (1 - lr * wd) in front of the
 Adam update, over every trainable element; resnet.fc, which never receives a gradient, stays untouched), LR_WARMUP_STEPS (0:
@@ -184,6 +187,9 @@ def get_cfg_defaults() -> CfgNode:
     c.AUG_SHIFT_PAD = 0           # random-shift augmentation: pad by this many replicated edge pixels, crop at a random offset (0 = off, <= 32)
     c.AUG_FLIP = False            # random left-right mirror of a sample (s and s' together), with its action label exchanged
     c.AUG_FLIP_ACTIONS = [1, 2]   # the two action labels a mirror exchanges (turn left, turn right)
+    c.AUG_BRIGHTNESS = 0.0        # colour jitter: brightness factor uniform in [1 - AUG_BRIGHTNESS, 1 + AUG_BRIGHTNESS] (0 = off, <= 1)
+    c.AUG_CONTRAST = 0.0          # contrast factor about mid-grey 128, uniform in [1 - AUG_CONTRAST, 1 + AUG_CONTRAST] (0 = off, <= 1)
+    c.AUG_SATURATION = 0.0        # saturation factor, uniform in [1 - AUG_SATURATION, 1 + AUG_SATURATION] (0 = off, <= 1)
     c.GRAD_CLIP_NORM = 0.0        # > 0: rescale the gradient to this global L2 norm at most (clip_grad_norm_, on the GPU); 0 = off
     c.WEIGHT_DECAY = 0.0          # decoupled weight decay (AdamW): p <- p * (1 - lr * WEIGHT_DECAY) in front of the Adam update
     c.LR_WARMUP_STEPS = 0         # the learning rate of update t is multiplied by min(1, t / LR_WARMUP_STEPS)

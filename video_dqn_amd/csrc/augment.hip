@@ -18,12 +18,34 @@
 // i.e. mirror the source, pad it by edge replication, crop at the drawn offset.  The packed operand's zero border (the
 // convolution's padding) stays zero.  The clamps hold for ANY int32 sx, sy and flip != 0 means 1: no parameter value makes the
 // kernel read outside the frame.
+//
+// Colour jitter (brightness, contrast, saturation), a map from uint8 pixels to uint8 pixels in integer arithmetic, so the operand is
+// still EXACTLY vdqn_pack_input of host-augmented frames (tests/aug_color_oracle.py restates it in numpy).  One int32 {f_b, f_c, f_s,
+// 0} per update and per SAMPLE, shared by its F frames and by s and s' (one camera, a fraction of a second apart).  Factors are Q8:
+// 256 = 1.0.  "/ 256" is floor division, i.e. an arithmetic shift.
+// Draw of sample j of the global batch G at update `step`, Jq_k = int(J_k * 256 + 0.5) in 0 .. 256 the Q8 half-width of factor k:
+//   key = splitmix64(seed ^ 0x415547434F4C5231)           "AUGCOLR1": a stream of its own, the shift / mirror draws do not move
+//   h   = splitmix64(key ^ (step * G + j))
+//   f_k = 256 - Jq_k + ((((h >> 16 k) & 0xFFFF) * (2 Jq_k + 1)) >> 16)     k = 0 brightness, 1 contrast, 2 saturation
+//   color[j] = int32 {f_b, f_c, f_s, 0}
+// Transform of one source pixel (R, G, B), in this order:
+//   saturation:  g = (77 R + 150 G + 29 B + 128) / 256                                  (BT.601 weights, sum 256)
+//                v = clamp(g + ((v - g) * f_s + 128) / 256, 0, 255)                     for v in R, G, B
+//   brightness:  v = min(255, (v * f_b + 128) / 256)
+//   contrast:    v = clamp(128 + ((v - 128) * f_c + 128) / 256, 0, 255)                 (pivot: mid-grey 128, no per-frame mean)
+// then the normalisation of pack_input.  Saturation goes first because it is the only stage that mixes channels: what follows it,
+// brightness then contrast, is a byte -> byte map bc(t) that folds into the per-block normalisation table, lut[c][t] = norm_c(bc(t)),
+// so only saturation costs per-pixel work.  The shift / mirror remap only picks the source pixel: the two compose in either order.
+// The kernel clamps every factor to [0, 512] first: no int32 value overflows a product or indexes outside a table; word 3 is ignored.
 #include "common.h"
 
 namespace {
 
 constexpr uint64_t kAugStream = 0x4155474D454E5431ull;
+constexpr uint64_t kColorStream = 0x415547434F4C5231ull;
 constexpr int kMaxPad = 32;
+constexpr int kMaxJq = 256;      // Q8 half-width of a colour factor: J in [0, 1]
+constexpr int kMaxFactor = 512;  // 256 + kMaxJq
 
 __host__ __device__ inline uint64_t splitmix64(uint64_t x) {
   uint64_t z = x + 0x9E3779B97F4A7C15ull;
@@ -45,6 +67,19 @@ __global__ __launch_bounds__(256) void aug_draw_kernel(uint64_t seed, uint64_t s
   params[i] = make_int4(sx, sy, flip_on ? (int)((h >> 32) & 1) : 0, 0);
 }
 
+// ---- aug_draw_color: one thread per sample -----------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void aug_draw_color_kernel(uint64_t seed, uint64_t step, int G, int first, int n, int jb, int jc, int js,
+                                                             int4* __restrict__ color) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const uint64_t key = splitmix64(seed ^ kColorStream);
+  const uint64_t h = splitmix64(key ^ (step * (uint64_t)G + (uint64_t)(first + i)));
+  const int fb = 256 - jb + (int)((((uint32_t)h & 0xFFFFu) * (2u * (uint32_t)jb + 1u)) >> 16);
+  const int fc = 256 - jc + (int)((((uint32_t)(h >> 16) & 0xFFFFu) * (2u * (uint32_t)jc + 1u)) >> 16);
+  const int fs = 256 - js + (int)((((uint32_t)(h >> 32) & 0xFFFFu) * (2u * (uint32_t)js + 1u)) >> 16);
+  color[i] = make_int4(fb, fc, fs, 0);
+}
+
 // ---- aug_swap_actions: a0 <-> a1 for the flipped samples, a copy otherwise -------------------------------------------------------
 __global__ __launch_bounds__(256) void aug_swap_actions_kernel(const int64_t* __restrict__ act, const int4* __restrict__ params, int n,
                                                                int64_t a0, int64_t a1, int64_t* __restrict__ act_out) {
@@ -61,21 +96,33 @@ __global__ __launch_bounds__(256) void aug_swap_actions_kernel(const int64_t* __
 // r and at most 3 apart, so the DISTINCT ones are Ys0 .. Ys3 and output row r reads LDS slot Ys_r - Ys0: every source row of the
 // pair comes from HBM once, as 42 16-byte vectors.  The X remap and the mirror pick which 3 LDS bytes a pixel reads.  The
 // normalisation table is built with the expression of pack_input_rows_kernel: same bits.
+// COLOR: thread t writes table entry t at bc(t), brightness then contrast of byte t under the block's factors, and a pixel's three
+// bytes go through the saturation stage between their LDS read and the table lookup.  COLOR = false is the kernel without any of it.
 constexpr int kPackPairs = 4;
 __device__ __forceinline__ int clamp223(int v) { return min(max(v, 0), 223); }
+__device__ __forceinline__ int clamp255(int v) { return min(max(v, 0), 255); }
 
-template <typename T>
+template <typename T, bool COLOR>
 __global__ __launch_bounds__(256) void pack_input_aug_kernel(const uint8_t* __restrict__ src, T* __restrict__ dst, int frames_per_sample,
-                                                             const int4* __restrict__ params, int n_params) {
+                                                             const int4* __restrict__ params, const int4* __restrict__ color, int n_params) {
   __shared__ uint4 rows[4][42];
   __shared__ T lut[3][256];
   const int n = blockIdx.y;
   const int tid = threadIdx.x;
+  int fs = 256;  // the saturation factor (COLOR only)
   {
     const float mean[3] = {0.485f, 0.456f, 0.406f};
     const float stdv[3] = {0.229f, 0.224f, 0.225f};
+    int t = tid;
+    if constexpr (COLOR) {
+      const int4 f = color[(n / frames_per_sample) % n_params];
+      const int fb = min(max(f.x, 0), kMaxFactor), fc = min(max(f.y, 0), kMaxFactor);
+      fs = min(max(f.z, 0), kMaxFactor);
+      t = min(255, (t * fb + 128) >> 8);            // brightness
+      t = clamp255(128 + (((t - 128) * fc + 128) >> 8));  // contrast about mid-grey (>> of a negative int: arithmetic, i.e. floor)
+    }
 #pragma unroll
-    for (int c = 0; c < 3; ++c) lut[c][tid] = from_f32<T>((((float)tid / 255.0f) - mean[c]) / stdv[c]);
+    for (int c = 0; c < 3; ++c) lut[c][tid] = from_f32<T>((((float)t / 255.0f) - mean[c]) / stdv[c]);
   }
   const int4 p = params[(n / frames_per_sample) % n_params];
   // |shift| > 223 already selects the edge pixel everywhere: clamping the shift first gives the same pixels without int overflow
@@ -116,12 +163,24 @@ __global__ __launch_bounds__(256) void pack_input_aug_kernel(const uint8_t* __re
       const int r0 = clamp223(Y0 + 2 * yy + sy) - Ys0, r1 = clamp223(Y0 + 2 * yy + 1 + sy) - Ys0;  // LDS slots, 0 .. 3
       const uint8_t* b0 = reinterpret_cast<const uint8_t*>(rows[r0]);
       const uint8_t* b1 = reinterpret_cast<const uint8_t*>(rows[r1]);
+      if constexpr (COLOR) {
+        const uint8_t* px[4] = {b0 + o0, b0 + o1, b1 + o0, b1 + o1};
 #pragma unroll
-      for (int c = 0; c < 3; ++c) {
-        v[c] = lut[c][b0[o0 + c]];
-        v[3 + c] = lut[c][b0[o1 + c]];
-        v[6 + c] = lut[c][b1[o0 + c]];
-        v[9 + c] = lut[c][b1[o1 + c]];
+        for (int k = 0; k < 4; ++k) {
+          const int R = px[k][0], G = px[k][1], B = px[k][2];
+          const int g = (77 * R + 150 * G + 29 * B + 128) >> 8;
+          v[3 * k] = lut[0][clamp255(g + (((R - g) * fs + 128) >> 8))];
+          v[3 * k + 1] = lut[1][clamp255(g + (((G - g) * fs + 128) >> 8))];
+          v[3 * k + 2] = lut[2][clamp255(g + (((B - g) * fs + 128) >> 8))];
+        }
+      } else {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+          v[c] = lut[c][b0[o0 + c]];
+          v[3 + c] = lut[c][b0[o1 + c]];
+          v[6 + c] = lut[c][b1[o0 + c]];
+          v[9 + c] = lut[c][b1[o1 + c]];
+        }
       }
     }
     T* d = dst + ((size_t)n * 115 * 115 + (size_t)y * 115 + x) * 16;
@@ -144,6 +203,22 @@ extern "C" int vdqn_aug_draw(uint64_t seed, uint64_t step, int32_t global_batch,
   ProfScope ps_("aug_draw", 0.0, (double)n * 16.0, (hipStream_t)stream);
   hipLaunchKernelGGL(aug_draw_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, seed, step, (int)global_batch, (int)first, (int)n,
                      (int)pad, (int)(flip != 0), (int4*)params);
+  VDQN_LAUNCH_CHECK();
+  return VDQN_OK;
+}
+
+extern "C" int vdqn_aug_draw_color(uint64_t seed, uint64_t step, int32_t global_batch, int32_t first, int32_t n, int32_t jb, int32_t jc,
+                                   int32_t js, int32_t* color, void* stream) {
+  VDQN_CHECK(color, "vdqn_aug_draw_color: null color");
+  VDQN_CHECK(n > 0, "vdqn_aug_draw_color: n = %d", n);
+  VDQN_CHECK(global_batch >= 1 && first >= 0 && (int64_t)first + n <= (int64_t)global_batch,
+             "vdqn_aug_draw_color: samples %d .. %lld outside the global batch of %d", first, (long long)first + n, global_batch);
+  VDQN_CHECK(jb >= 0 && jb <= kMaxJq && jc >= 0 && jc <= kMaxJq && js >= 0 && js <= kMaxJq,
+             "vdqn_aug_draw_color: half-widths (%d, %d, %d) outside [0, %d] (Q8: int(J * 256 + 0.5), J in [0, 1])", jb, jc, js, kMaxJq);
+  VDQN_CHECK(((uintptr_t)color & 15) == 0, "vdqn_aug_draw_color: color must be 16-byte aligned");
+  ProfScope ps_("aug_draw_color", 0.0, (double)n * 16.0, (hipStream_t)stream);
+  hipLaunchKernelGGL(aug_draw_color_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, seed, step, (int)global_batch, (int)first,
+                     (int)n, (int)jb, (int)jc, (int)js, (int4*)color);
   VDQN_LAUNCH_CHECK();
   return VDQN_OK;
 }
@@ -172,11 +247,31 @@ extern "C" int vdqn_pack_input_aug(const void* src, void* dst, int32_t n_img, in
   ProfScope ps_("pack_input_aug", 0.0, (double)n_img * (224.0 * 224 * 3 + 115.0 * 115 * 16 * (dtype == VDQN_BF16 ? 2 : 4)), (hipStream_t)stream);
   const dim3 grid((58 + kPackPairs - 1) / kPackPairs, n_img);
   if (dtype == VDQN_BF16)
-    hipLaunchKernelGGL((pack_input_aug_kernel<bf16raw>), grid, dim3(256), 0, (hipStream_t)stream, (const uint8_t*)src, (bf16raw*)dst,
-                       (int)frames_per_sample, (const int4*)params, (int)n_params);
+    hipLaunchKernelGGL((pack_input_aug_kernel<bf16raw, false>), grid, dim3(256), 0, (hipStream_t)stream, (const uint8_t*)src, (bf16raw*)dst,
+                       (int)frames_per_sample, (const int4*)params, (const int4*)nullptr, (int)n_params);
   else
-    hipLaunchKernelGGL((pack_input_aug_kernel<float>), grid, dim3(256), 0, (hipStream_t)stream, (const uint8_t*)src, (float*)dst,
-                       (int)frames_per_sample, (const int4*)params, (int)n_params);
+    hipLaunchKernelGGL((pack_input_aug_kernel<float, false>), grid, dim3(256), 0, (hipStream_t)stream, (const uint8_t*)src, (float*)dst,
+                       (int)frames_per_sample, (const int4*)params, (const int4*)nullptr, (int)n_params);
+  VDQN_LAUNCH_CHECK();
+  return VDQN_OK;
+}
+
+extern "C" int vdqn_pack_input_aug_color(const void* src, void* dst, int32_t n_img, int32_t frames_per_sample, const int32_t* params,
+                                         const int32_t* color, int32_t n_params, int32_t dtype, void* stream) {
+  VDQN_CHECK(src && dst && params && color, "vdqn_pack_input_aug_color: null arg");
+  VDQN_CHECK(n_img > 0 && frames_per_sample > 0 && n_params > 0, "vdqn_pack_input_aug_color: n_img %d, frames_per_sample %d, n_params %d must be > 0",
+             n_img, frames_per_sample, n_params);
+  VDQN_CHECK(dtype == VDQN_F32 || dtype == VDQN_BF16, "vdqn_pack_input_aug_color: bad dtype");
+  VDQN_CHECK((((uintptr_t)src | (uintptr_t)dst | (uintptr_t)params | (uintptr_t)color) & 15) == 0,
+             "vdqn_pack_input_aug_color: src, dst, params and color must be 16-byte aligned");
+  ProfScope ps_("pack_input_aug_color", 0.0, (double)n_img * (224.0 * 224 * 3 + 115.0 * 115 * 16 * (dtype == VDQN_BF16 ? 2 : 4)), (hipStream_t)stream);
+  const dim3 grid((58 + kPackPairs - 1) / kPackPairs, n_img);
+  if (dtype == VDQN_BF16)
+    hipLaunchKernelGGL((pack_input_aug_kernel<bf16raw, true>), grid, dim3(256), 0, (hipStream_t)stream, (const uint8_t*)src, (bf16raw*)dst,
+                       (int)frames_per_sample, (const int4*)params, (const int4*)color, (int)n_params);
+  else
+    hipLaunchKernelGGL((pack_input_aug_kernel<float, true>), grid, dim3(256), 0, (hipStream_t)stream, (const uint8_t*)src, (float*)dst,
+                       (int)frames_per_sample, (const int4*)params, (const int4*)color, (int)n_params);
   VDQN_LAUNCH_CHECK();
   return VDQN_OK;
 }

@@ -414,7 +414,7 @@ class TDStepper:
             self.net.pack_weights(self.packed_target, with_dgrad=False)
 
     def _args(self, before, after, src_kind, act, rew, term, valid, gt, weights=None, td_error=None, augment=None,
-              discount=None) -> _lib.StepArgs:
+              discount=None, augment_color=None) -> _lib.StepArgs:
         n = self.net
         a = _lib.StepArgs()
         a.params, a.bnstats = _ptr(n.params), _ptr(n.bnstats)
@@ -430,6 +430,7 @@ class TDStepper:
         a.loss_kind = LOSS_KINDS[self.loss_kind]
         a.packed_frames = None
         a.sample_weight, a.sample_err, a.aug_params = _ptr(weights), _ptr(td_error), _ptr(augment)
+        a.aug_color = _ptr(augment_color)
         a.sample_gamma = _ptr(discount)
         return a
 
@@ -487,7 +488,7 @@ class TDStepper:
         self._ahead = (self._frames_key(nb, na, nk), slot, (nb, na))  # (the tensors are kept alive until they are consumed)
 
     def forward_backward(self, before, after, src_kind, act, rew, term, valid=None, gt=None, early_adam: bool = False, next_frames=None,
-                         *, weights=None, td_error=None, augment=None, discount=None):
+                         *, weights=None, td_error=None, augment=None, discount=None, augment_color=None):
         """Everything of one update up to (and including) the gradient all-reduce; no optimiser step.
 
         early_adam (only `step` passes it: single process, no exchange, eval-mode BatchNorm): the optimiser update of stage 0 and stage 1 is
@@ -495,15 +496,15 @@ class TDStepper:
         weight gradients instead of behind them (nothing later in the update reads those master parameters: the kernels work on
         the packed copies); `optimizer_step` then only covers what is left.  Same arithmetic, same results.
 
-        weights, td_error, augment, discount: as `step` describes and validates them (vdqn_step_args.sample_weight / sample_err /
-        aug_params / sample_gamma)."""
+        weights, td_error, augment, discount, augment_color: as `step` describes and validates them (vdqn_step_args.sample_weight /
+        sample_err / aug_params / sample_gamma / aug_color)."""
         n = self.net
         self._adam_done = []
         self._clip_slots = 0
-        keep = (before, after, act, rew, term, valid, gt, weights, td_error, augment, discount)  # keep inputs alive until the launches are queued
+        keep = (before, after, act, rew, term, valid, gt, weights, td_error, augment, discount, augment_color)  # keep inputs alive until the launches are queued
         with torch.cuda.device(n.device):
             a = self._args(before, after, src_kind, act, rew, term, valid if valid is not None else self._ones, gt, weights, td_error, augment,
-                           discount)
+                           discount, augment_color)
             st = _stream()
             ahead, self._ahead = self._ahead, None
             slot = None
@@ -683,7 +684,7 @@ class TDStepper:
         return out
 
     def step(self, before, after, src_kind, act, rew, term, valid=None, gt=None, finish_allreduce=None, next_frames=None,
-             weights=None, td_error=None, augment=None, discount=None) -> torch.Tensor:
+             weights=None, td_error=None, augment=None, discount=None, augment_color=None) -> torch.Tensor:
         """One iteration of the reference loop body (train_q_network.py:213-227).  Returns the device loss scalar
         (no host sync).
 
@@ -708,7 +709,17 @@ class TDStepper:
         discount (n-step returns, video_dqn_amd/nstep.py): f32 [B] on the device — sample b's target is rew[b] + discount[b] * (1 -
         term[b]) * Q(after[b]) where it is rew[b] + gamma * ... otherwise (vdqn_step_args.sample_gamma, this update only; nothing is
         kept between updates).  The caller passes the folded rewards and terminals and the `after` frames of each chain's last row
-        (NStepWalker.walk).  A constant discount == gamma gives the update without it bit for bit.  TD branch without `linear`."""
+        (NStepWalker.walk).  A constant discount == gamma gives the update without it bit for bit.  TD branch without `linear`.
+
+        augment_color (video_dqn_amd/augment.py): int32 [B][4] {f_b, f_c, f_s, 0} on the device, Q8 factors of brightness, contrast and
+        saturation (256 = 1.0) — the frames go through vdqn_pack_input_aug_color with them and with `augment`, which must be given
+        as well (zeros = no shift); the same for `before` and `after` (vdqn_step_args.aug_color, this update only)."""
+        if augment_color is not None:
+            if augment is None:
+                raise _lib.VdqnError("TDStepper.step: augment_color needs augment as well (int32 zeros [B][4] = no shift, no mirror)")
+            if (augment_color.dtype != torch.int32 or tuple(augment_color.shape) != (self.B, 4) or not augment_color.is_contiguous()
+                    or not augment_color.is_cuda):
+                raise _lib.VdqnError(f"TDStepper.step: augment_color must be a contiguous int32 [{self.B}][4] device tensor")
         if discount is not None:
             if self.gtb or self.linear:
                 raise _lib.VdqnError("TDStepper.step: discount applies to the TD branch without LINEAR (TRAIN_ON_GROUND_TRUTH bootstraps "
@@ -747,7 +758,7 @@ class TDStepper:
         # profiles/r03s_ab_rccl_early_adam.txt — with an exchange the whole optimiser update stays behind `finish_allreduce`)
         early = _EARLY_ADAM and self.net.extra_capacity and self.allreduce is None and finish_allreduce is None and self.grad_clip_norm == 0
         self.forward_backward(before, after, src_kind, act, rew, term, valid, gt, early_adam=early, next_frames=next_frames,
-                              weights=weights, td_error=td_error, augment=augment, discount=discount)
+                              weights=weights, td_error=td_error, augment=augment, discount=discount, augment_color=augment_color)
         if finish_allreduce is not None:
             finish_allreduce()
             self._clip_slots = 0  # the gradient has just been reduced: its norm is taken from what `grads` holds now

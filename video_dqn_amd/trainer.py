@@ -138,10 +138,11 @@ def check_prioritized_replay(config, world_size: int = 1) -> None:
                          "and DEVICE_RESIDENT_DATA is 'off'")
 
 
-def check_augment(pad, flip, flip_actions) -> None:
-    """AUG_SHIFT_PAD / AUG_FLIP / AUG_FLIP_ACTIONS: raise ValueError naming the key (before any device work)."""
+def check_augment(pad, flip, flip_actions, brightness=0.0, contrast=0.0, saturation=0.0) -> None:
+    """AUG_SHIFT_PAD / AUG_FLIP / AUG_FLIP_ACTIONS / AUG_BRIGHTNESS / AUG_CONTRAST / AUG_SATURATION: raise ValueError naming the key
+    (before any device work)."""
     from .augment import check_config
-    check_config(pad, flip, flip_actions)
+    check_config(pad, flip, flip_actions, brightness, contrast, saturation)
 
 
 def check_optim(config) -> None:
@@ -294,7 +295,8 @@ def run_train(config, resume_from=-1, max_steps=None, rank=0, world_size=1, log=
     """train_q_network.py:84-250."""
     aug_pad, aug_flip = getattr(config, "AUG_SHIFT_PAD", 0), getattr(config, "AUG_FLIP", False)
     aug_actions = getattr(config, "AUG_FLIP_ACTIONS", [1, 2])
-    check_augment(aug_pad, aug_flip, aug_actions)
+    aug_color = tuple(getattr(config, k, 0.0) for k in ("AUG_BRIGHTNESS", "AUG_CONTRAST", "AUG_SATURATION"))
+    check_augment(aug_pad, aug_flip, aug_actions, *aug_color)
     check_optim(config)
     check_cql(config)
     check_target(config)
@@ -455,14 +457,17 @@ def run_train(config, resume_from=-1, max_steps=None, rank=0, world_size=1, log=
             (f" learning rate {config.LR_SCHEDULE} to {float(config.LR_FINAL_FRACTION):g} x LEARNING_RATE at {int(config.NUM_STEPS)}, "
              f"{int(config.LR_WARMUP_STEPS)} warm-up updates" if lr_fn is not None else ""))
     augmenter = None
-    if aug_pad > 0 or aug_flip:
-        from .augment import Augmenter
+    if aug_pad > 0 or aug_flip or any(j > 0 for j in aug_color):
+        from .augment import COLOR_KEYS, Augmenter
         augmenter = Augmenter(B, model.engine.device, pad=aug_pad, flip=aug_flip, flip_actions=aug_actions, seed=int(config.SEED),
-                              rank=rank, world_size=world_size)
+                              rank=rank, world_size=world_size, brightness=aug_color[0], contrast=aug_color[1], saturation=aug_color[2])
         swap = aug_flip and model.engine.action_dim == 3  # (one action column: nothing to exchange)
-        log(f"augmentation: random shift of up to {aug_pad} pixels" + (", random left-right mirror" if aug_flip else "") +
-            (f" with actions {aug_actions[0]} <-> {aug_actions[1]} exchanged" if swap else "") +
-            ", one draw per sample and update, shared by s and s'")
+        on = [f"random shift of up to {aug_pad} pixels"] if aug_pad > 0 or aug_flip else []
+        if aug_flip:
+            on.append("random left-right mirror" + (f" with actions {aug_actions[0]} <-> {aug_actions[1]} exchanged" if swap else ""))
+        if augmenter.color is not None:
+            on.append("colour jitter " + " ".join(f"{k[4:].lower()} x [{1 - j:g}, {1 + j:g}]" for k, j in zip(COLOR_KEYS, aug_color) if j > 0))
+        log("augmentation: " + ", ".join(on) + ", one draw per sample and update, shared by s and s'")
     if world_size > 1 and config.ARCHITECTURE != "extra_capacity" and getattr(config, "SYNC_BN", True):
         model.engine.set_bn_sync(world_size)  # train-mode BatchNorm over the global batch, as the single-GPU reference sees it
     if replay is not None:
@@ -521,7 +526,7 @@ def run_train(config, resume_from=-1, max_steps=None, rank=0, world_size=1, log=
             log("soft target updates: the checkpoint has no target_state_dict, the target starts from the online weights")
     stepper.sample_number = sample_number
     stepper.replay = replay  # the run's PrioritizedSampler (PRIORITIZED_REPLAY), None otherwise: returned with the stepper
-    stepper.augmenter = augmenter  # the run's Augmenter (AUG_SHIFT_PAD / AUG_FLIP), None otherwise
+    stepper.augmenter = augmenter  # the run's Augmenter (AUG_SHIFT_PAD / AUG_FLIP / the colour keys), None otherwise
     stepper.nstep = walker  # the run's NStepWalker (N_STEP > 1), None otherwise
     # VAL_INTERVAL > 0: the held-out pass (video_dqn_amd/validate.py) on rank 0 alone; the other ranks wait in the next update's
     # first collective.  Off: nothing is built, no launch differs
@@ -554,9 +559,9 @@ def run_train(config, resume_from=-1, max_steps=None, rank=0, world_size=1, log=
             model.set_train()  # :221 (flags only; the engine's BatchNorm is always in eval mode in extra_capacity)
             item = next(iterator)
             before, after, src_kind, act, rew, term, valid, gt = item[:8]
-            aug_params = None
-            if augmenter is not None:  # this update's draw and the mirrored samples' action labels: two launches, nothing read back
-                aug_params = augmenter.draw(sample_number)
+            aug_params = aug_factors = None
+            if augmenter is not None:  # this update's draw(s) and the mirrored samples' action labels: small launches, nothing read back
+                aug_params, aug_factors = augmenter.draw(sample_number), augmenter.color
                 if swap:
                     act = augmenter.actions(act.contiguous())
             # the stepper performs the :215-216 target refresh itself (sample_number % TARGET_UPDATE_INTERVAL == 0)
@@ -565,7 +570,7 @@ def run_train(config, resume_from=-1, max_steps=None, rank=0, world_size=1, log=
                                 gt if config.TRAIN_ON_GROUND_TRUTH else None,
                                 finish_allreduce=(comm.finish if comm else None),
                                 weights=(item[8] if replay is not None else None),
-                                td_error=(replay.err if replay is not None else None), augment=aug_params,
+                                td_error=(replay.err if replay is not None else None), augment=aug_params, augment_color=aug_factors,
                                 discount=(item[-1] if walker is not None else None))  # (gather_nstep appends it)
             if replay is not None:
                 replay.update()  # behind the loss launch (and, with N ranks, the error exchange that finish_allreduce joined)
