@@ -8,7 +8,7 @@ rounds, and nowhere else, so that the bf16 kernels the benchmark times (`win9u`,
 `stem_wgrad_pool`) meet an element-wise check inside a real update:
 
   forward   the normalised frame (vdqn_pack_input), the BatchNorm-folded weights W * gamma * rstd of every convolution and the
-            weights of `features.8` / `top.*` (fold kernels of engine.hip), every stored activation (conv epilogue: f32 accumulator
+            weights of `features.8` / `top.*` (fold kernels of fold.hip), every stored activation (conv epilogue: f32 accumulator
             + f32 bias (+ residual) -> ReLU -> bf16), the downsample branch's output; Q itself stays f32 (`qf`);
   backward  every stored gradient: dL/dQ (td_loss writes dq in bf16), the gradient with respect to every pre-ReLU sum (what a data
             gradient kernel stores: (dgrad + residual path) * mask -> bf16), the pooled gradient and the max-pool backward's

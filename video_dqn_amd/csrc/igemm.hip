@@ -1565,7 +1565,6 @@ extern "C" void vdqn_debug_stamp_buffer(void* p) { g_stamp_buffer = p; }  // dia
 
 extern "C" int vdqn_conv2d(const vdqn_conv_args* a, void* stream) {
   VDQN_CHECK(a != nullptr, "vdqn_conv2d: null args");
-  VDQN_CHECK(a != nullptr, "vdqn_conv2d: null args");
   VDQN_CHECK(a->dtype == VDQN_F32 || a->dtype == VDQN_BF16 || a->dtype == VDQN_F32X3, "vdqn_conv2d: bad dtype %d", a->dtype);
   const int esz = a->dtype == VDQN_BF16 ? 2 : 4;
   const bool x3 = a->dtype == VDQN_F32X3;  // f32 tensors, the f32 kernels' bf16x3 instances
