@@ -216,6 +216,27 @@ int vdqn_td_loss_cql(const vdqn_td_args* a, const float* weight /* NULL = 1 */, 
  * (y = r + (Qa - 0.1) has no discount), a NULL sample_gamma and a negative or non-finite cql_alpha. */
 int vdqn_td_loss_nstep(const vdqn_td_args* a, const float* weight /* NULL ok */, float* err_out /* NULL ok */, float cql_alpha /* 0 = none */,
                        float* penalty /* NULL ok */, const float* sample_gamma, void* stream);
+/* The entries above with the Monte-Carlo return G_bc = mc_return[b][c] of every sampled row (vdqn_mc_returns below: the discounted
+ * return the logged data itself obtained from that row, a lower bound of the optimal value when rewards are non-negative).  The
+ * mode is chosen as vdqn_td_loss_nstep chooses it (cql_alpha > 0, else weight, else plain); sample_gamma may be NULL (a->gamma).
+ *   mc_flags bit 0, the floor (lower-bound Q-learning, He et al. 2017; Oh et al. 2018): y = max(y, G_bc) in front of the rect clip,
+ *     which keeps the last word; err_out follows the floored error.
+ *   mc_flags bit 1, calibrated (Cal-QL, Nakamoto et al., NeurIPS 2023; needs cql_alpha > 0): with qc_a = max(q_a, G_bc),
+ *     m = max_a qc_a, sum = sum_a expf(qc_a - m), p_a = expf(qc_a - m) / sum, pen_bc = logf(sum) + (m - q_{a*}) with the raw
+ *     q_{a*}, and the penalty's part of dq is alpha * (p_a * [q_a >= G_bc] - [a == a*]); at a tie q_a == G_bc the Q value takes the
+ *     gradient.
+ *   mc_stats (f32[2], pre-zeroed, NULL ok), each inv_count times a sum that is formed like the loss's (`deterministic`: one block,
+ *     a fixed order), vm_bc = valid or 1 and no importance weight:
+ *     [0] += vm_bc * [G_bc > y before the floor]   the share of targets the floor raises (under either flag)
+ *     [1] += vm_bc * (q_{a*} - G_bc)               by how far Q sits above the achieved return
+ * A compile-time choice inside the one kernel template: the instances behind the entries above keep their loads and bits, and
+ * with mc_return filled with -inf this entry writes exactly the bits of the matching entry above under any flags, mc_stats[0]
+ * staying 0.  Fails by name, before any launch, for everything those entries refuse and for a NULL mc_return, mc_flags 0 or with
+ * unknown bits, bit 1 with cql_alpha == 0, a negative or non-finite cql_alpha and linear != 0. */
+int vdqn_td_loss_mc(const vdqn_td_args* a, const float* weight /* NULL ok */, float* err_out /* NULL ok */, float cql_alpha /* 0 = none */,
+                    float* penalty /* NULL ok */, const float* sample_gamma /* NULL = a->gamma */,
+                    const float* mc_return /* f32 [batch][n_cat], required */, int32_t mc_flags, float* mc_stats /* f32[2], pre-zeroed, NULL ok */,
+                    void* stream);
 /* Held-out validation metrics of the same loss, forward only: the `eval_losses` list the reference reserves and never fills
  * (train_q_network.py:183-186) and its `# checkpoint and eval` (:240).  One launch adds eight sums per category into
  * acc (device f64 [n_cat][8], 8-byte aligned, ACCUMULATED into: the caller zeroes it once per validation pass).  With d, y and l(d)
@@ -519,6 +540,13 @@ int vdqn_net_td_forward(vdqn_net* net, const vdqn_step_args* a, void* stream);
  * == 0 is vdqn_net_td_forward: the same launches and bits.  Fails by name for a negative or non-finite cql_alpha, and with
  * cql_alpha > 0 for train_on_ground_truth and for action_dim == 1.  Either architecture, every compute mode. */
 int vdqn_net_td_forward_cql(vdqn_net* net, const vdqn_step_args* a, float cql_alpha, float* cql_penalty, void* stream);
+/* vdqn_net_td_forward_cql whose loss launch is vdqn_td_loss_mc(.., mc_return, mc_flags, mc_stats): mc_return is f32 [batch]
+ * [num_classes] on the device, this update's alone (plain arguments: nothing is kept in the engine and no argument struct changes).
+ * mc_stats (device f32[2], NULL ok) is cleared beside `loss`.  mc_return == NULL: vdqn_net_td_forward_cql, the same launches and
+ * bits (mc_flags and mc_stats are then not looked at).  Otherwise fails by name, before any launch, for train_on_ground_truth,
+ * linear, mc_flags 0 or with unknown bits, and bit 1 with cql_alpha == 0. */
+int vdqn_net_td_forward_mc(vdqn_net* net, const vdqn_step_args* a, float cql_alpha, float* cql_penalty, const float* mc_return,
+                           int32_t mc_flags, float* mc_stats, void* stream);
 /* One held-out batch of a validation pass (the reference's unfilled `eval_losses`, train_q_network.py:183-186, and `# checkpoint
  * and eval`, :240): the online network over [before; after] (2 * batch samples), the target network over after on the side stream,
  * then vdqn_td_eval on the two f32 Q tensors (ldq 64) into acc (device f64 [num_classes][8], accumulated into).  Forward only, both
@@ -588,6 +616,29 @@ int vdqn_per_update(float* prio, int64_t n, const int64_t* idx, const float* err
 int vdqn_nstep_walk(const int64_t* idx, int32_t batch, const int32_t* next_row, const float* rew, const float* term, int64_t n_rows,
                     int32_t n_cat, int32_t n, float gamma, float* rew_n, float* term_n, float* disc, int64_t* last_row, int32_t* steps,
                     void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Monte-Carlo return table: per row and category the discounted return the logged data obtained along the row's chain (the chain
+ * vdqn_nstep_walk walks), over the chain's first 2^rounds rows:
+ *   G(i) = sum_{k < 2^rounds} g^k prod_{j<k}(1 - t(i_j)) r(i_k),   i_0 = i, i_{k+1} = next_row[i_k], ending where the chain ends.
+ * Built by pointer doubling, one launch per round and one thread per row, state (j, A[c], B[c]) per row:
+ *   initial state:  j = next_row[i] (a value < 0 or >= n_rows becomes -1),  B = r,  A = g * (1 - t)   (the subtraction rounds, then
+ *                   the product)
+ *   one round, with j = j_old[i]:   j >= 0:  B' = B + (A * B_old[j]),  A' = A * A_old[j],  j' = j_old[j]
+ *                                   j <  0:  B' = B,                   A' = 0,             j' = -1
+ * every product and sum rounded on its own (tests/mc_oracle.py restates it in numpy float32, bit for bit); a round reads one
+ * buffer set and writes the other; no atomics, no LDS, plain stores, so two builds are bit-identical.  After `rounds` rounds B is
+ * G.  Self-loops and cycles are legal.  Against the exact sum, |G - exact| <= (3 * rounds + 3) * 2^-24 * S with S the same sum over
+ * |r|.
+ * ------------------------------------------------------------------------------------------------ */
+/* Bytes of the caller's workspace (two j tables, two A tables and one B table; the other B table is G itself); -1 for n_rows
+ * outside [1, 2^31 - 1] or n_cat outside [1, 8]. */
+int64_t vdqn_mc_returns_workspace_bytes(int64_t n_rows, int32_t n_cat);
+/* next_row int32 [n_rows], rew / term f32 [n_rows][n_cat] (read only), G f32 [n_rows][n_cat], all on the device; workspace 4-byte
+ * aligned, its contents do not matter before and mean nothing after.  Every check fails by name before any launch: null pointers,
+ * n_rows outside [1, 2^31 - 1], n_cat outside [1, 8], rounds outside [1, 31], a non-finite gamma, a workspace that is too small. */
+int vdqn_mc_returns(const int32_t* next_row, const float* rew, const float* term, int64_t n_rows, int32_t n_cat, float gamma, int32_t rounds,
+                    float* G, void* workspace, int64_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Random shift + left-right mirror augmentation of the training minibatch (DrQ / RAD style), fused into the input pack.  The

@@ -57,7 +57,15 @@ whose first `before` frame is r's first `after` frame, found in the shard index 
 gamma^m are folded by one launch on the GPU per update and s' is the `after` frame of the last of the m <= N_STEP rows the chain
 provides, so every sample still costs one s' forward; no importance correction: with non-negative rewards the target is a lower
 bound of the optimal value; the sampled rows are those of N_STEP 1 under the same seed; the TD branch without LINEAR on a
-decoded-frame shard dataset held in full in HBM on every rank; validation stays one-step).
+decoded-frame shard dataset held in full in HBM on every rank; validation stays one-step), MC_RETURN_FLOOR (False = off; True: the
+bootstrapped target of a sampled row is floored by the discounted return G the logged data itself obtained from that row to the end
+of its chain, y <- max(y, G) in front of the rect clip — lower-bound Q-learning; G is a table over all rows, built once at start on
+the GPU by pointer doubling at GAMMA, per category; with N_STEP > 1 the floor is still the sampled row's whole-chain return; logs
+mc_floor_share/train, the share of targets the floor raises, and q_minus_return/train, the mean of Q(s, a_data) - G; the same
+configurations as N_STEP > 1: the TD branch without LINEAR on a decoded-frame shard dataset held in full in HBM on every rank;
+nothing goes into checkpoints, validation is unchanged), CQL_CALIBRATED (False = off; True: calibrated conservative Q-learning,
+Cal-QL — the penalty's logsumexp runs over max(Q(s, a), G) with the same table G, so the penalty stops pushing values below what
+the data achieved; needs CQL_ALPHA > 0 and what MC_RETURN_FLOOR needs; logs the same two scalars).
 """
 from __future__ import annotations
 
@@ -200,6 +208,8 @@ def get_cfg_defaults() -> CfgNode:
     c.VAL_DATASET = ""            # held-out validation set: a path as DATASET takes it, or 'synthetic' (seeded with SEED + 1); '' = off
     c.VAL_INTERVAL = 0            # > 0: a validation pass on rank 0 after every update t with t % VAL_INTERVAL == 0; 0 = off
     c.VAL_BATCHES = 0             # > 0: only the first VAL_BATCHES batches of the validation set; 0 = the whole set
+    c.MC_RETURN_FLOOR = False     # True: y <- max(y, G), G the Monte-Carlo return of the sampled row along its chain (a table built on the GPU at start)
+    c.CQL_CALIBRATED = False      # True: Cal-QL — the CQL penalty's logsumexp over max(Q, G); needs CQL_ALPHA > 0
     c.N_STEP = 1                  # 2 .. 16: n-step returns along each sampled row's chain in the logged data, folded on the GPU; 1 = off
     return c
 

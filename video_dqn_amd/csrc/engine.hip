@@ -394,8 +394,10 @@ static vdqn_td_args fill_td_args(const vdqn_net* net, const vdqn_step_args* a, c
   return t;
 }
 
-// vdqn_net_td_forward (cql_alpha == 0: the launches and bits it always had) and vdqn_net_td_forward_cql (cql_alpha > 0)
-static int td_forward_impl(vdqn_net* net, const vdqn_step_args* a, float cql_alpha, float* cql_penalty, void* stream) {
+// vdqn_net_td_forward (cql_alpha == 0: the launches and bits it always had), vdqn_net_td_forward_cql (cql_alpha > 0) and
+// vdqn_net_td_forward_mc (mc_return != NULL: the loss launch is vdqn_td_loss_mc; NULL: nothing differs)
+static int td_forward_impl(vdqn_net* net, const vdqn_step_args* a, float cql_alpha, float* cql_penalty, void* stream,
+                           const float* mc_return = nullptr, int32_t mc_flags = 0, float* mc_stats = nullptr) {
   VDQN_CHECK(net && a, "vdqn_net_td_forward: null arg");
   VDQN_CHECK(a->params && a->bnstats && a->packed_online && a->before && a->act && a->acts_online && a->bwd && a->loss, "vdqn_net_td_forward: null buffer");
   const int B = a->batch;
@@ -451,6 +453,10 @@ static int td_forward_impl(vdqn_net* net, const vdqn_step_args* a, float cql_alp
     e = hipMemsetAsync(cql_penalty, 0, 4, st);
     VDQN_CHECK(e == hipSuccess, "vdqn_net_td_forward_cql: memset failed: %s", hipGetErrorString(e));
   }
+  if (mc_return && mc_stats) {
+    e = hipMemsetAsync(mc_stats, 0, 8, st);
+    VDQN_CHECK(e == hipSuccess, "vdqn_net_td_forward_mc: memset failed: %s", hipGetErrorString(e));
+  }
 
   const float* qf_online = reinterpret_cast<const float*>(ao + A.qf);
   if (!gtb) {
@@ -463,7 +469,8 @@ static int td_forward_impl(vdqn_net* net, const vdqn_step_args* a, float cql_alp
     t.dtype = dt;
     t.deterministic = net->cfg.deterministic;
     t.q_copy = a->q_before;  // (the compact copy of Q(s) rides in the loss launch: no 2-D copy between the loss and the first data gradient)
-    if (a->sample_gamma) RC(vdqn_td_loss_nstep(&t, a->sample_weight, a->sample_err, cql_alpha, cql_alpha > 0.f ? cql_penalty : nullptr, a->sample_gamma, st));
+    if (mc_return) RC(vdqn_td_loss_mc(&t, a->sample_weight, a->sample_err, cql_alpha, cql_alpha > 0.f ? cql_penalty : nullptr, a->sample_gamma, mc_return, mc_flags, mc_stats, st));
+    else if (a->sample_gamma) RC(vdqn_td_loss_nstep(&t, a->sample_weight, a->sample_err, cql_alpha, cql_alpha > 0.f ? cql_penalty : nullptr, a->sample_gamma, st));
     else if (cql_alpha > 0.f) RC(vdqn_td_loss_cql(&t, a->sample_weight, a->sample_err, cql_alpha, cql_penalty, st));
     else if (a->sample_weight) RC(vdqn_td_loss_weighted(&t, a->sample_weight, a->sample_err, st));
     else RC(vdqn_td_loss(&t, st));
@@ -489,6 +496,22 @@ extern "C" int vdqn_net_td_forward_cql(vdqn_net* net, const vdqn_step_args* a, f
     VDQN_CHECK(net->cfg.action_dim >= 2, "vdqn_net_td_forward_cql: action_dim is 1: with one action the penalty is identically zero");
   }
   return td_forward_impl(net, a, cql_alpha, cql_penalty, stream);
+}
+
+// vdqn_net_td_forward_cql with the Monte-Carlo return of every sampled row (csrc/mcreturn.hip) for the loss launch: per-update
+// inputs, plain arguments, nothing kept in the engine.  Everything the loss launch would refuse is refused here, before the forward.
+extern "C" int vdqn_net_td_forward_mc(vdqn_net* net, const vdqn_step_args* a, float cql_alpha, float* cql_penalty, const float* mc_return,
+                                      int32_t mc_flags, float* mc_stats, void* stream) {
+  if (!mc_return) return vdqn_net_td_forward_cql(net, a, cql_alpha, cql_penalty, stream);
+  VDQN_CHECK(net && a, "vdqn_net_td_forward_mc: null arg");
+  VDQN_CHECK(isfinite(cql_alpha) && cql_alpha >= 0.f, "vdqn_net_td_forward_mc: cql_alpha %g must be finite and >= 0", (double)cql_alpha);
+  VDQN_CHECK(!a->train_on_ground_truth, "vdqn_net_td_forward_mc: mc_return is given, but the ground-truth branch has no target to floor and no penalty to calibrate (train_on_ground_truth)");
+  VDQN_CHECK(!a->linear, "vdqn_net_td_forward_mc: mc_return is given with linear: y = r + (Qa - 0.1) has no discount, and a discounted return bounds nothing of it");
+  VDQN_CHECK((mc_flags & ~3) == 0, "vdqn_net_td_forward_mc: mc_flags 0x%x has unknown bits (bit 0 = floor, bit 1 = calibrated)", (unsigned)mc_flags);
+  VDQN_CHECK(mc_flags != 0, "vdqn_net_td_forward_mc: mc_flags is 0: at least one of bit 0 (floor) and bit 1 (calibrated) must be set");
+  VDQN_CHECK(!(mc_flags & 2) || cql_alpha > 0.f, "vdqn_net_td_forward_mc: mc_flags bit 1 (calibrated) needs cql_alpha > 0");
+  if (cql_alpha > 0.f) VDQN_CHECK(net->cfg.action_dim >= 2, "vdqn_net_td_forward_mc: action_dim is 1: with one action the penalty is identically zero");
+  return td_forward_impl(net, a, cql_alpha, cql_penalty, stream, mc_return, mc_flags, mc_stats);
 }
 
 // One held-out batch of a validation pass (train_q_network.py:183-186 `eval_losses`, :240 `# checkpoint and eval`): the frames

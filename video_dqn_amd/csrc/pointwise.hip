@@ -311,7 +311,12 @@ __device__ __forceinline__ void add_partials(const float (&red)[N][16], int n_wa
 // Q(s'), the target network's value there, terminal mask, LINEAR / gamma, rect clip).  The only statement of the target: the loss
 // terms of every mode and the per-sample error take d from here.  `gamma` is the discount of sample b: a.gamma, or the sample's own
 // (n-step returns: gamma^m of the m rows its chain walked, csrc/nstep.hip) in the instances with a per-sample discount.
-__device__ __forceinline__ float td_error_of(const vdqn_td_args& a, int b, int c, int col, float gamma) {
+// MC (the instances behind vdqn_td_loss_mc, 0 elsewhere: G is then not read): G is the Monte-Carlo return of (b, c)
+// (csrc/mcreturn.hip); *raised = [G > y], taken before the floor, and with MC_FLOOR y = max(y, G) in front of the rect clip — the
+// clip keeps the last word, so a floored target stays inside [0, 1] like every other.
+enum { MC_FLOOR = 1, MC_CALIBRATED = 2 };
+template <int MC = 0>
+__device__ __forceinline__ float td_error_of(const vdqn_td_args& a, int b, int c, int col, float gamma, float G = 0.f, bool* raised = nullptr) {
   const float qb = a.q_before[(size_t)b * a.ldq + col];
   const float* qo = a.q_after_online + (size_t)b * a.ldq + c * a.n_act;
   int best = 0;
@@ -327,6 +332,10 @@ __device__ __forceinline__ float td_error_of(const vdqn_td_args& a, int b, int c
   qa = qa * (1.0f - a.term[b * a.n_cat + c]);
   const float r = a.rew[b * a.n_cat + c];
   float y = a.linear ? r + (qa - 0.1f) : r + gamma * qa;
+  if constexpr (MC != 0) {
+    if (raised) *raised = G > y;
+    if constexpr ((MC & MC_FLOOR) != 0) y = fmaxf(y, G);
+  }
   if (a.clip_rect) y = fminf(fmaxf(y, 0.f), 1.f);
   return qb - y;
 }
@@ -353,10 +362,20 @@ __device__ __forceinline__ float td_error_of(const vdqn_td_args& a, int b, int c
 // SG (vdqn_td_loss_nstep), also chosen at compile time: the discount of sample b is a.sg[b] where the other instances take a.gamma —
 // one more load per taken-action thread, nothing else; with sg[b] == gamma for every b the instance writes the bits of its SG = false
 // twin, and a row depends on its own sample's discount only.
+// MC (vdqn_td_loss_mc), chosen at compile time like MODE and SG; 0 in every instance behind the other entries, which read neither
+// a.mc nor a.mc_stats.  G_bc = a.mc[b][c] is the discounted return the logged data obtained from the sampled row (csrc/mcreturn.hip):
+//   MC_FLOOR       y = max(y, G_bc) inside td_error_of, before the rect clip; err[b] follows the floored error.
+//   MC_CALIBRATED  (TD_CQL only; Cal-QL, Nakamoto et al., NeurIPS 2023) the penalty's logsumexp runs over qc_a = max(q_a, G_bc):
+//                  m = max_a qc_a, sum = sum_a expf(qc_a - m), p_a = expf(qc_a - m) / sum, pen_bc = logf(sum) + (m - q_{a*}) with the
+//                  RAW q_{a*}, and the penalty's part of dq is alpha * (p_a * [q_a >= G_bc] - [a == a*]): where G_bc is the larger
+//                  the term is a constant and carries no gradient; at a tie q_a == G_bc the Q value takes it.
+//   a.mc_stats (f32[2] or NULL), summed and added like the loss, vm_bc = valid or 1 (no importance weight):
+//                  [0] += vm_bc * [G_bc > y before the floor]      [1] += vm_bc * (q_{a*} - G_bc)
+// With G = -inf max(x, G) == x, [q >= G] holds and [G > y] does not: every MC instance then writes the bits of its MC = 0 twin.
 // Launch shapes: 256 threads and one element per thread.  A deterministic launch is ONE block that walks all elements (thread t
 // takes t, t + blockDim.x, ..; the block sum's fixed order): 256 threads for TD_PLAIN and TD_WEIGHTED, 1024 for TD_CQL — a quarter of
 // the serial passes.  __launch_bounds__(1024) is there for that launch alone, and it budgets the TD_CQL instances' 256-thread
-// launches too: 128 VGPRs per thread.  They take 38; should they grow, they have to stay under that.
+// launches too: 128 VGPRs per thread.  They take 38 (the MC instances: DESIGN.md 3o); should they grow, they have to stay under that.
 enum { TD_PLAIN = 0, TD_WEIGHTED = 1, TD_CQL = 2 };
 struct td_kernel_args : vdqn_td_args {
   const float* w;  // [batch]; TD_CQL: or NULL (= 1)
@@ -364,12 +383,16 @@ struct td_kernel_args : vdqn_td_args {
   float* penalty;  // TD_CQL: f32 scalar or NULL
   float alpha;     // TD_CQL
   const float* sg;  // SG: [batch] per-sample discount
+  const float* mc;  // MC: [batch][n_cat] Monte-Carlo returns
+  float* mc_stats;  // MC: f32[2] or NULL
 };
-template <typename T, int MODE, bool SG>
+template <typename T, int MODE, bool SG, int MC>
 __global__ __launch_bounds__(MODE == TD_CQL ? 1024 : 256) void td_loss_kernel(const td_kernel_args a) {
+  static_assert(MC >= 0 && MC <= 3 && (MODE == TD_CQL || (MC & MC_CALIBRATED) == 0), "MC_CALIBRATED belongs to TD_CQL");
   const int total = a.batch * a.ldq;
-  constexpr int N_SUMS = MODE == TD_CQL ? 2 : 1;
-  float sums[N_SUMS] = {};  // this thread's loss terms (TD_CQL: and penalty terms)
+  constexpr int N_LOSS = MODE == TD_CQL ? 2 : 1;
+  constexpr int N_SUMS = N_LOSS + (MC != 0 ? 2 : 0);
+  float sums[N_SUMS] = {};  // this thread's loss terms (TD_CQL: and penalty terms; MC: and the two mc_stats terms)
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
     const int b = i / a.ldq, col = i - b * a.ldq;
     float g = 0.f;
@@ -379,16 +402,32 @@ __global__ __launch_bounds__(MODE == TD_CQL ? 1024 : 256) void td_loss_kernel(co
       const float* q = a.q_before + (size_t)b * a.ldq + c * a.n_act;
       if (a.q_copy) a.q_copy[(size_t)b * (a.n_cat * a.n_act) + col] = q[ac];
       float m = 0.f, sum = 0.f, p = 0.f, s = 0.f;  // TD_CQL only
+      float G = 0.f;                               // MC only
+      if constexpr (MC != 0) G = a.mc[b * a.n_cat + c];
       if constexpr (MODE == TD_CQL) {
-        m = q[0];
-        for (int k = 1; k < a.n_act; ++k) m = fmaxf(m, q[k]);
-        for (int k = 0; k < a.n_act; ++k) sum += expf(q[k] - m);
-        p = expf(q[ac] - m) / sum;
+        if constexpr ((MC & MC_CALIBRATED) != 0) {
+          m = fmaxf(q[0], G);
+          for (int k = 1; k < a.n_act; ++k) m = fmaxf(m, fmaxf(q[k], G));
+          for (int k = 0; k < a.n_act; ++k) sum += expf(fmaxf(q[k], G) - m);
+          p = expf(fmaxf(q[ac], G) - m) / sum;
+          if (!(q[ac] >= G)) p = 0.f;  // (p is from here on the gradient's share alone: the penalty itself is logf(sum) + ...)
+        } else {
+          m = q[0];
+          for (int k = 1; k < a.n_act; ++k) m = fmaxf(m, q[k]);
+          for (int k = 0; k < a.n_act; ++k) sum += expf(q[k] - m);
+          p = expf(q[ac] - m) / sum;
+        }
         s = (a.w ? a.w[b] : 1.0f) * (a.use_valid ? a.valid[b * a.n_cat + c] : 1.0f);
         g = a.alpha * p;
       }
       if (ac == act) {
-        const float d = td_error_of(a, b, c, col, SG ? a.sg[b] : a.gamma);
+        bool raised = false;
+        const float d = td_error_of<MC>(a, b, c, col, SG ? a.sg[b] : a.gamma, G, &raised);
+        if constexpr (MC != 0) {
+          const float vs = a.use_valid ? a.valid[b * a.n_cat + c] : 1.0f;
+          sums[N_LOSS] += raised ? vs : 0.f;
+          sums[N_LOSS + 1] += vs * (q[ac] - G);
+        }
         float l, dl;
         if (a.loss_kind == 1) {  // Huber, beta = 1 (torch.nn.functional.smooth_l1_loss)
           const float ad = fabsf(d);
@@ -418,7 +457,9 @@ __global__ __launch_bounds__(MODE == TD_CQL ? 1024 : 256) void td_loss_kernel(co
     if constexpr (MODE != TD_PLAIN) {
       if (col == 0 && a.err) {
         float e = 0.f;
-        for (int c = 0; c < a.n_cat; ++c) e += fabsf(td_error_of(a, b, c, c * a.n_act + (int)a.act[b], SG ? a.sg[b] : a.gamma)) * (a.use_valid ? a.valid[b * a.n_cat + c] : 1.0f);
+        for (int c = 0; c < a.n_cat; ++c)
+          e += fabsf(td_error_of<MC>(a, b, c, c * a.n_act + (int)a.act[b], SG ? a.sg[b] : a.gamma, MC != 0 ? a.mc[b * a.n_cat + c] : 0.f)) *
+               (a.use_valid ? a.valid[b * a.n_cat + c] : 1.0f);
         a.err[b] = e / (float)a.n_cat;
       }
     }
@@ -432,6 +473,10 @@ __global__ __launch_bounds__(MODE == TD_CQL ? 1024 : 256) void td_loss_kernel(co
     if (sums[0] != 0.f) atomicAdd(a.loss, sums[0] * a.inv_count);
     if constexpr (MODE == TD_CQL) {
       if (a.penalty && sums[1] != 0.f) atomicAdd(a.penalty, sums[1] * a.inv_count);
+    }
+    if constexpr (MC != 0) {
+      if (a.mc_stats && sums[N_LOSS] != 0.f) atomicAdd(a.mc_stats, sums[N_LOSS] * a.inv_count);
+      if (a.mc_stats && sums[N_LOSS + 1] != 0.f) atomicAdd(a.mc_stats + 1, sums[N_LOSS + 1] * a.inv_count);
     }
   }
 }
@@ -624,10 +669,22 @@ extern "C" int vdqn_axpy(float* y, const float* x, float alpha, int64_t n, void*
 }
 
 // The TD-loss entries: every check (each fails by the entry's name before any HIP call), then the one launch.  sample_gamma != NULL
-// (vdqn_td_loss_nstep only) selects the instances with a per-sample discount.
+// (vdqn_td_loss_nstep, vdqn_td_loss_mc) selects the instances with a per-sample discount, mc_flags != 0 (vdqn_td_loss_mc only)
+// those with the Monte-Carlo return: MC_CALIBRATED is instantiated for TD_CQL alone.
+template <int MODE, int MC>
+static void td_loss_launch_instance(int dtype, bool sg, int g, int threads, hipStream_t st, const td_kernel_args& k) {
+  if (sg) {
+    if (dtype == VDQN_BF16) hipLaunchKernelGGL((td_loss_kernel<bf16raw, MODE, true, MC>), dim3(g), dim3(threads), 0, st, k);
+    else hipLaunchKernelGGL((td_loss_kernel<float, MODE, true, MC>), dim3(g), dim3(threads), 0, st, k);
+  } else {
+    if (dtype == VDQN_BF16) hipLaunchKernelGGL((td_loss_kernel<bf16raw, MODE, false, MC>), dim3(g), dim3(threads), 0, st, k);
+    else hipLaunchKernelGGL((td_loss_kernel<float, MODE, false, MC>), dim3(g), dim3(threads), 0, st, k);
+  }
+}
 template <int MODE>
 static int td_loss_launch(const char* entry, const char* prof_name, const vdqn_td_args* a, const float* weight, float* err_out, float cql_alpha,
-                          float* penalty, const float* sample_gamma, void* stream) {
+                          float* penalty, const float* sample_gamma, void* stream, const float* mc_return = nullptr, int mc_flags = 0,
+                          float* mc_stats = nullptr) {
   VDQN_CHECK(a && a->q_before && a->q_after_online && a->q_after_target && a->act && a->rew && a->term && a->loss && (MODE != TD_WEIGHTED || weight),
              "%s: null arg", entry);
   VDQN_CHECK(!a->use_valid || a->valid, "%s: use_valid without valid mask", entry);
@@ -638,6 +695,7 @@ static int td_loss_launch(const char* entry, const char* prof_name, const vdqn_t
   VDQN_CHECK(!sample_gamma || !a->linear, "%s: linear with a per-sample discount: y = r + (Qa - 0.1) has no discount and no n-step form", entry);
   if (MODE == TD_CQL)
     VDQN_CHECK(isfinite(cql_alpha) && cql_alpha > 0.f, "%s: cql_alpha %g must be finite and > 0 (without the penalty: vdqn_td_loss)", entry, (double)cql_alpha);
+  VDQN_CHECK(MODE == TD_CQL || !(mc_flags & MC_CALIBRATED), "%s: mc_flags %d: the calibrated penalty needs cql_alpha > 0", entry, mc_flags);
   const int threads = MODE == TD_CQL && a->deterministic ? 1024 : 256;
   const int g = a->deterministic ? 1 : (a->batch * a->ldq + 255) / 256;
   ProfScope ps_(prof_name, 0.0, (double)a->batch * a->ldq * 16.0 + (MODE == TD_PLAIN ? 0.0 : (double)a->batch * 8.0), (hipStream_t)stream);
@@ -648,12 +706,15 @@ static int td_loss_launch(const char* entry, const char* prof_name, const vdqn_t
   k.penalty = penalty;
   k.alpha = cql_alpha;
   k.sg = sample_gamma;
-  if (sample_gamma) {
-    if (a->dtype == VDQN_BF16) hipLaunchKernelGGL((td_loss_kernel<bf16raw, MODE, true>), dim3(g), dim3(threads), 0, (hipStream_t)stream, k);
-    else hipLaunchKernelGGL((td_loss_kernel<float, MODE, true>), dim3(g), dim3(threads), 0, (hipStream_t)stream, k);
-  } else {
-    if (a->dtype == VDQN_BF16) hipLaunchKernelGGL((td_loss_kernel<bf16raw, MODE, false>), dim3(g), dim3(threads), 0, (hipStream_t)stream, k);
-    else hipLaunchKernelGGL((td_loss_kernel<float, MODE, false>), dim3(g), dim3(threads), 0, (hipStream_t)stream, k);
+  k.mc = mc_return;
+  k.mc_stats = mc_stats;
+  const bool sg = sample_gamma != nullptr;
+  hipStream_t st = (hipStream_t)stream;
+  if (mc_flags == 0) td_loss_launch_instance<MODE, 0>(a->dtype, sg, g, threads, st, k);
+  else if (mc_flags == MC_FLOOR) td_loss_launch_instance<MODE, MC_FLOOR>(a->dtype, sg, g, threads, st, k);
+  else if constexpr (MODE == TD_CQL) {
+    if (mc_flags == MC_CALIBRATED) td_loss_launch_instance<MODE, MC_CALIBRATED>(a->dtype, sg, g, threads, st, k);
+    else td_loss_launch_instance<MODE, MC_FLOOR | MC_CALIBRATED>(a->dtype, sg, g, threads, st, k);
   }
   VDQN_LAUNCH_CHECK();
   return VDQN_OK;
@@ -682,6 +743,25 @@ extern "C" int vdqn_td_loss_nstep(const vdqn_td_args* a, const float* weight, fl
   VDQN_CHECK(weight || !err_out, "vdqn_td_loss_nstep: err_out without weight (the unweighted launch writes no per-sample errors)");
   if (weight) return td_loss_launch<TD_WEIGHTED>("vdqn_td_loss_nstep", "td_loss_w", a, weight, err_out, 0.f, nullptr, sample_gamma, stream);
   return td_loss_launch<TD_PLAIN>("vdqn_td_loss_nstep", "td_loss", a, nullptr, nullptr, 0.f, nullptr, sample_gamma, stream);
+}
+
+// The entries above with the Monte-Carlo return of every sampled row (csrc/mcreturn.hip): the mode is chosen as vdqn_td_loss_nstep
+// chooses it, sample_gamma may be NULL (the scalar a->gamma).
+extern "C" int vdqn_td_loss_mc(const vdqn_td_args* a, const float* weight, float* err_out, float cql_alpha, float* penalty, const float* sample_gamma,
+                               const float* mc_return, int32_t mc_flags, float* mc_stats, void* stream) {
+  VDQN_CHECK(a, "vdqn_td_loss_mc: null arg");
+  VDQN_CHECK(mc_return, "vdqn_td_loss_mc: mc_return is NULL (without the return table: vdqn_td_loss, _weighted, _cql, _nstep)");
+  VDQN_CHECK((mc_flags & ~(MC_FLOOR | MC_CALIBRATED)) == 0, "vdqn_td_loss_mc: mc_flags 0x%x has unknown bits (bit 0 = floor, bit 1 = calibrated)", (unsigned)mc_flags);
+  VDQN_CHECK(mc_flags != 0, "vdqn_td_loss_mc: mc_flags is 0: at least one of bit 0 (floor) and bit 1 (calibrated) must be set");
+  VDQN_CHECK(isfinite(cql_alpha) && cql_alpha >= 0.f, "vdqn_td_loss_mc: cql_alpha %g must be finite and >= 0 (0 = no penalty)", (double)cql_alpha);
+  VDQN_CHECK(!(mc_flags & MC_CALIBRATED) || cql_alpha > 0.f, "vdqn_td_loss_mc: mc_flags bit 1 (calibrated) needs cql_alpha > 0: there is no penalty to calibrate");
+  VDQN_CHECK(!a->linear, "vdqn_td_loss_mc: linear: y = r + (Qa - 0.1) has no discount, and a discounted return bounds nothing of it");
+  if (cql_alpha > 0.f)
+    return td_loss_launch<TD_CQL>("vdqn_td_loss_mc", "td_loss_cql_mc", a, weight, err_out, cql_alpha, penalty, sample_gamma, stream, mc_return, mc_flags, mc_stats);
+  VDQN_CHECK(!penalty, "vdqn_td_loss_mc: penalty is given, but cql_alpha is 0");
+  VDQN_CHECK(weight || !err_out, "vdqn_td_loss_mc: err_out without weight (the unweighted launch writes no per-sample errors)");
+  if (weight) return td_loss_launch<TD_WEIGHTED>("vdqn_td_loss_mc", "td_loss_w_mc", a, weight, err_out, 0.f, nullptr, sample_gamma, stream, mc_return, mc_flags, mc_stats);
+  return td_loss_launch<TD_PLAIN>("vdqn_td_loss_mc", "td_loss_mc", a, nullptr, nullptr, 0.f, nullptr, sample_gamma, stream, mc_return, mc_flags, mc_stats);
 }
 
 extern "C" int vdqn_gt_loss(const float* q_before, const int64_t* act, const float* gt, float* loss, void* dq, float* dq_f32, int32_t batch,

@@ -300,7 +300,7 @@ class TDStepper:
                  target_update_interval: int = 8000, betas=(0.9, 0.999), eps: float = 1e-8, world_size: int = 1,
                  allreduce=None, loss_kind: str = "l2", allreduce_loss=None, allreduce_wait=None, allreduce_errors=None,
                  grad_clip_norm: float = 0.0, weight_decay: float = 0.0, lr_fn=None, cql_alpha: float = 0.0,
-                 target_tau: float = 0.0):
+                 target_tau: float = 0.0, mc_floor: bool = False, cql_calibrated: bool = False):
         net._need_gpu()
         self.net, self.B = net, batch
         self.lib = net.lib
@@ -335,6 +335,16 @@ class TDStepper:
         if cql_alpha > 0 and net.action_dim < 2:
             raise _lib.VdqnError("TDStepper: cql_alpha needs action_dim >= 2 (with one action the penalty is identically zero)")
         self.cql_alpha = cql_alpha
+        # mc_floor / cql_calibrated (video_dqn_amd/mcreturn.py): `step(mc_return=...)` hands the loss launch the Monte-Carlo return of
+        # every sampled row — the floor y = max(y, G) in front of the rect clip (vdqn_td_loss_mc, mc_flags bit 0) and the calibrated
+        # penalty, whose logsumexp runs over max(Q, G) (bit 1) — and `mc_stats` receives this rank's share of {the share of targets the
+        # floor raises, the mean of Q(s, a_data) - G}.  Both off: the entries above, launched as ever.
+        self.mc_flags = (1 if mc_floor else 0) | (2 if cql_calibrated else 0)
+        if self.mc_flags and (train_on_ground_truth or linear):
+            raise _lib.VdqnError("TDStepper: mc_floor / cql_calibrated apply to the TD branch without linear (train_on_ground_truth has no "
+                                 "target to floor; y = r + (Qa - 0.1) has no discount)")
+        if cql_calibrated and not cql_alpha > 0:
+            raise _lib.VdqnError("TDStepper: cql_calibrated needs cql_alpha > 0 (there is no penalty to calibrate)")
         # target_tau > 0 (soft / Polyak target updates): `target_params`, an f32 copy of the whole flat `net.params` (the trainable
         # prefix and the frozen resnet.fc tail), follows the online weights as target <- target + tau (params - target) inside every
         # Adam launch (vdqn_adam_polyak), and `packed_target` is folded from it in front of every update; target_update_interval is
@@ -380,6 +390,7 @@ class TDStepper:
             self.exp_avg_sq = torch.zeros(nt, dtype=torch.float32, device=dev)
             self.loss = torch.zeros(1, dtype=torch.float32, device=dev)
             self.cql_penalty = torch.zeros(1, dtype=torch.float32, device=dev)
+            self.mc_stats = torch.zeros(2, dtype=torch.float32, device=dev)
             self.q_before = torch.zeros((batch, net.num_classes * net.action_dim), dtype=torch.float32, device=dev)
             self._ones = torch.ones((batch, net.num_classes), dtype=torch.float32, device=dev)
             if self.grad_clip_norm > 0:
@@ -488,7 +499,7 @@ class TDStepper:
         self._ahead = (self._frames_key(nb, na, nk), slot, (nb, na))  # (the tensors are kept alive until they are consumed)
 
     def forward_backward(self, before, after, src_kind, act, rew, term, valid=None, gt=None, early_adam: bool = False, next_frames=None,
-                         *, weights=None, td_error=None, augment=None, discount=None, augment_color=None):
+                         *, weights=None, td_error=None, augment=None, discount=None, augment_color=None, mc_return=None):
         """Everything of one update up to (and including) the gradient all-reduce; no optimiser step.
 
         early_adam (only `step` passes it: single process, no exchange, eval-mode BatchNorm): the optimiser update of stage 0 and stage 1 is
@@ -497,11 +508,11 @@ class TDStepper:
         the packed copies); `optimizer_step` then only covers what is left.  Same arithmetic, same results.
 
         weights, td_error, augment, discount, augment_color: as `step` describes and validates them (vdqn_step_args.sample_weight /
-        sample_err / aug_params / sample_gamma / aug_color)."""
+        sample_err / aug_params / sample_gamma / aug_color); mc_return: vdqn_net_td_forward_mc's plain argument."""
         n = self.net
         self._adam_done = []
         self._clip_slots = 0
-        keep = (before, after, act, rew, term, valid, gt, weights, td_error, augment, discount, augment_color)  # keep inputs alive until the launches are queued
+        keep = (before, after, act, rew, term, valid, gt, weights, td_error, augment, discount, augment_color, mc_return)  # keep inputs alive until the launches are queued
         with torch.cuda.device(n.device):
             a = self._args(before, after, src_kind, act, rew, term, valid if valid is not None else self._ones, gt, weights, td_error, augment,
                            discount, augment_color)
@@ -511,7 +522,10 @@ class TDStepper:
             if ahead is not None and ahead[0] == self._frames_key(before, after, src_kind):
                 slot = ahead[1]  # these frames were packed during the previous update (ordered in front of `st` by its last stage)
                 a.packed_frames = self._packed_buffer(slot).data_ptr()
-            if self.cql_alpha > 0:
+            if mc_return is not None:
+                _lib.check(self.lib.vdqn_net_td_forward_mc(n.handle, C.byref(a), self.cql_alpha, self.cql_penalty.data_ptr(), mc_return.data_ptr(),
+                                                           self.mc_flags, self.mc_stats.data_ptr(), st), "vdqn_net_td_forward_mc")
+            elif self.cql_alpha > 0:
                 _lib.check(self.lib.vdqn_net_td_forward_cql(n.handle, C.byref(a), self.cql_alpha, self.cql_penalty.data_ptr(), st),
                            "vdqn_net_td_forward_cql")
             else:
@@ -684,7 +698,7 @@ class TDStepper:
         return out
 
     def step(self, before, after, src_kind, act, rew, term, valid=None, gt=None, finish_allreduce=None, next_frames=None,
-             weights=None, td_error=None, augment=None, discount=None, augment_color=None) -> torch.Tensor:
+             weights=None, td_error=None, augment=None, discount=None, augment_color=None, mc_return=None) -> torch.Tensor:
         """One iteration of the reference loop body (train_q_network.py:213-227).  Returns the device loss scalar
         (no host sync).
 
@@ -713,7 +727,20 @@ class TDStepper:
 
         augment_color (video_dqn_amd/augment.py): int32 [B][4] {f_b, f_c, f_s, 0} on the device, Q8 factors of brightness, contrast and
         saturation (256 = 1.0) — the frames go through vdqn_pack_input_aug_color with them and with `augment`, which must be given
-        as well (zeros = no shift); the same for `before` and `after` (vdqn_step_args.aug_color, this update only)."""
+        as well (zeros = no shift); the same for `before` and `after` (vdqn_step_args.aug_color, this update only).
+
+        mc_return (video_dqn_amd/mcreturn.py): f32 [B][num_classes] on the device, the Monte-Carlo return of every sampled row
+        (ReturnTable.G at the sampled rows; with n-step returns still the sampled row's, the whole-episode return against the n-step
+        target).  Required exactly when the stepper was built with mc_floor or cql_calibrated; this update only.  A table of -inf
+        gives the update without it bit for bit."""
+        if (mc_return is not None) != bool(self.mc_flags):
+            raise _lib.VdqnError("TDStepper.step: mc_return is required exactly when the stepper has mc_floor or cql_calibrated set "
+                                 f"(mc_floor={bool(self.mc_flags & 1)}, cql_calibrated={bool(self.mc_flags & 2)}, "
+                                 f"mc_return {'given' if mc_return is not None else 'missing'})")
+        if mc_return is not None:
+            if (mc_return.dtype != torch.float32 or tuple(mc_return.shape) != (self.B, self.net.num_classes) or not mc_return.is_contiguous()
+                    or not mc_return.is_cuda):
+                raise _lib.VdqnError(f"TDStepper.step: mc_return must be a contiguous f32 [{self.B}][{self.net.num_classes}] device tensor")
         if augment_color is not None:
             if augment is None:
                 raise _lib.VdqnError("TDStepper.step: augment_color needs augment as well (int32 zeros [B][4] = no shift, no mirror)")
@@ -758,7 +785,8 @@ class TDStepper:
         # profiles/r03s_ab_rccl_early_adam.txt — with an exchange the whole optimiser update stays behind `finish_allreduce`)
         early = _EARLY_ADAM and self.net.extra_capacity and self.allreduce is None and finish_allreduce is None and self.grad_clip_norm == 0
         self.forward_backward(before, after, src_kind, act, rew, term, valid, gt, early_adam=early, next_frames=next_frames,
-                              weights=weights, td_error=td_error, augment=augment, discount=discount, augment_color=augment_color)
+                              weights=weights, td_error=td_error, augment=augment, discount=discount, augment_color=augment_color,
+                              mc_return=mc_return)
         if finish_allreduce is not None:
             finish_allreduce()
             self._clip_slots = 0  # the gradient has just been reduced: its norm is taken from what `grads` holds now

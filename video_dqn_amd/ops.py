@@ -256,6 +256,42 @@ def nstep_walk(idx, next_row, rew, term, *, n, gamma):
     return rew_n, term_n, disc, last_row, steps
 
 
+def td_loss_mc(q_before, q_after_online, q_after_target, act, rew, term, valid=None, *, mc_return, floor=False, calibrated=False, weights=None,
+               with_err=False, cql_alpha=0.0, discount=None, n_cat=5, n_act=3, gamma=0.99, inv_count=None, clip_rect=True,
+               out_dtype=torch.float32, loss_kind="l2", deterministic=False, linear=False, mc_flags=None):
+    """The TD loss with the Monte-Carlo return of every sampled row (vdqn_td_loss_mc): mc_return f32 [B, n_cat] on the device.  floor:
+    y = max(y, G) in front of the rect clip; calibrated (needs cql_alpha > 0): the penalty's logsumexp over max(Q, G).  The mode is
+    chosen as td_loss_nstep chooses it; discount (f32 [B]) is optional.  mc_flags overrides the two switches (bit 0 / bit 1).
+    Returns (loss[1], dq[B, ldq] out_dtype, dq_f32, penalty[1] or None, err[B] or None, mc_stats[2])."""
+    lib = _lib.load()
+    a, loss, dq, dq32 = _td_args(q_before, q_after_online, q_after_target, act, rew, term, valid, n_cat, n_act, gamma, inv_count, clip_rect,
+                                 linear, out_dtype, loss_kind, deterministic)
+    if mc_return is not None and (mc_return.dtype != torch.float32 or tuple(mc_return.shape) != (q_before.shape[0], n_cat)
+                                  or not mc_return.is_contiguous()):
+        raise ValueError(f"td_loss_mc: mc_return must be a contiguous f32 [{q_before.shape[0]}, {n_cat}] device tensor")
+    flags = ((1 if floor else 0) | (2 if calibrated else 0)) if mc_flags is None else int(mc_flags)
+    penalty = torch.zeros(1, dtype=torch.float32, device=loss.device) if cql_alpha > 0 else None
+    err = torch.empty(q_before.shape[0], dtype=torch.float32, device=loss.device) if with_err else None
+    stats = torch.zeros(2, dtype=torch.float32, device=loss.device)
+    _lib.check(lib.vdqn_td_loss_mc(C.byref(a), _ptr(weights), _ptr(err), float(cql_alpha), _ptr(penalty), _ptr(discount), _ptr(mc_return), flags,
+                                   _ptr(stats), _stream()), "vdqn_td_loss_mc")
+    return loss, dq, dq32, penalty, err, stats
+
+
+def mc_returns(next_row, rew, term, *, gamma, rounds, out=None, workspace=None):
+    """vdqn_mc_returns: the Monte-Carlo return table G f32 [N, n_cat] over the first 2^rounds rows of every row's chain (next_row int32
+    [N]; rew / term f32 [N, n_cat], all on the device, none written).  workspace: a device byte tensor of at least
+    vdqn_mc_returns_workspace_bytes(N, n_cat) bytes (allocated when None)."""
+    lib = _lib.load()
+    N, n_cat = rew.shape
+    G = torch.empty((N, n_cat), dtype=torch.float32, device=rew.device) if out is None else out
+    if workspace is None:
+        workspace = torch.empty(max(int(lib.vdqn_mc_returns_workspace_bytes(N, n_cat)), 4), dtype=torch.uint8, device=rew.device)
+    _lib.check(lib.vdqn_mc_returns(_ptr(next_row), _ptr(rew), _ptr(term), N, n_cat, float(gamma), int(rounds), _ptr(G), _ptr(workspace),
+                                   workspace.numel() * workspace.element_size(), _stream()), "vdqn_mc_returns")
+    return G
+
+
 def td_eval(q_before, q_after_online, q_after_target, act, rew, term, valid=None, *, acc=None, n_cat=5, n_act=3, gamma=0.99,
             clip_rect=True, linear=False, loss_kind="l2"):
     """Held-out validation metrics of the TD loss (vdqn_td_eval): eight f64 sums per category — count, loss, |TD error|, Q(s, a_data),

@@ -245,33 +245,38 @@ class DeviceFrameStore:
     def bytes(self):
         return self.frames.numel()
 
-    def gather(self, idx: torch.Tensor):
+    def gather(self, idx: torch.Tensor, returns=None):
         """Device batch for sample indices ``idx`` (int64 device tensor), in the order trainer._to_device_batch produces:
-        (before, after, src_kind=0, act, rew, term, valid, gt)."""
+        (before, after, src_kind=0, act, rew, term, valid, gt).  returns (MC_RETURN_FLOOR / CQL_CALIBRATED: a
+        video_dqn_amd.mcreturn.ReturnTable over this store's rows): its G at the sampled rows, f32 [B][n_cat], appended."""
         b = self.frames.index_select(0, self.before.index_select(0, idx).reshape(-1))
         a = self.frames.index_select(0, self.after.index_select(0, idx).reshape(-1))
         if self.nf > 1:
             b = b.view(idx.shape[0], self.nf, 224, 224, 3)
             a = a.view(idx.shape[0], self.nf, 224, 224, 3)
-        return (b, a, 0, self.act.index_select(0, idx), self.rew.index_select(0, idx), self.term.index_select(0, idx),
+        item = (b, a, 0, self.act.index_select(0, idx), self.rew.index_select(0, idx), self.term.index_select(0, idx),
                 self.valid.index_select(0, idx), self.gt.index_select(0, idx))
+        return item if returns is None else item + (returns.G.index_select(0, idx),)
 
-    def gather_nstep(self, idx: torch.Tensor, walker):
+    def gather_nstep(self, idx: torch.Tensor, walker, returns=None):
         """`gather` for n-step returns (video_dqn_amd.nstep.NStepWalker over this store's rew / term tables): one walk launch, then
         `before`, act, valid and gt from the sampled rows idx, `after` from the LAST row of each chain, the folded rewards and terminals
         in place of the rows' own, and the per-sample discount appended: (before, after, 0, act, rew_n, term_n, valid, gt, disc).
-        rew_n, term_n and disc are the walker's buffers: valid until its next walk."""
+        rew_n, term_n and disc are the walker's buffers: valid until its next walk.  returns: as `gather` takes it, appended behind disc —
+        still G at the SAMPLED rows idx, the whole-chain return against the n-step target."""
         rew_n, term_n, disc, last_row, _ = walker.walk(idx)
         b = self.frames.index_select(0, self.before.index_select(0, idx).reshape(-1))
         a = self.frames.index_select(0, self.after.index_select(0, last_row).reshape(-1))
         if self.nf > 1:
             b = b.view(idx.shape[0], self.nf, 224, 224, 3)
             a = a.view(idx.shape[0], self.nf, 224, 224, 3)
-        return (b, a, 0, self.act.index_select(0, idx), rew_n, term_n, self.valid.index_select(0, idx), self.gt.index_select(0, idx), disc)
+        item = (b, a, 0, self.act.index_select(0, idx), rew_n, term_n, self.valid.index_select(0, idx), self.gt.index_select(0, idx), disc)
+        return item if returns is None else item + (returns.G.index_select(0, idx),)
 
-    def batches(self, batch_size: int, seed: int, rank: int = 0, world_size: int = 1, walker=None):
+    def batches(self, batch_size: int, seed: int, rank: int = 0, world_size: int = 1, walker=None, returns=None):
         """Endless stream of device batches: per epoch one seeded permutation (identical on every rank), rank r takes
-        perm[r::world], drop_last.  walker (N_STEP > 1): the same rows through `gather_nstep`."""
+        perm[r::world], drop_last.  walker (N_STEP > 1): the same rows through `gather_nstep`.  returns: handed to the gather, which
+        appends G at the sampled rows behind everything else."""
         epoch = 0
         n = len(self)
         per_rank = (n // world_size // batch_size) * batch_size
@@ -283,27 +288,24 @@ class DeviceFrameStore:
             perm = torch.randperm(n, generator=g)[rank::world_size][:per_rank].to(self.device)
             for lo in range(0, per_rank, batch_size):
                 idx = perm[lo:lo + batch_size]
-                yield self.gather(idx) if walker is None else self.gather_nstep(idx, walker)
+                yield self.gather(idx, returns) if walker is None else self.gather_nstep(idx, walker, returns)
             epoch += 1
             print("reset iterator")
 
-    def prioritized_batches(self, sampler, start_step: int, walker=None):
+    def prioritized_batches(self, sampler, start_step: int, walker=None, returns=None):
         """Endless stream for prioritized replay (video_dqn_amd.replay.PrioritizedSampler over len(self) samples): update
         start_step + 1, + 2, ... draws this rank's indices and importance weights on the device and gathers them; yields the
         `gather` tuple followed by the weights.  Each draw is queued when the caller asks for the batch, i.e. behind the previous
         update's priority update.  walker (N_STEP > 1): the drawn rows through `gather_nstep`; the tuple is then
-        (before, after, 0, act, rew_n, term_n, valid, gt, weight, disc)."""
+        (before, after, 0, act, rew_n, term_n, valid, gt, weight, disc).  returns: as `batches` takes it; G stays last."""
         if sampler.n != len(self):
             raise ValueError(f"prioritized replay: the sampler's table has {sampler.n} entries, the dataset {len(self)} samples")
         step = start_step
         while True:
             step += 1
             idx, weight = sampler.sample(step)
-            if walker is None:
-                yield self.gather(idx) + (weight,)
-            else:
-                item = self.gather_nstep(idx, walker)
-                yield item[:8] + (weight, item[8])
+            item = self.gather(idx, returns) if walker is None else self.gather_nstep(idx, walker, returns)
+            yield item[:8] + (weight,) + item[8:]  # (the weight in front of what the gather appended: disc, G)
 
 
 class RankShardedFrameStore:

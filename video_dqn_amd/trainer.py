@@ -180,6 +180,51 @@ def check_target(config) -> None:
         raise ValueError("TARGET_TAU needs the TD branch: TRAIN_ON_GROUND_TRUTH regresses on given targets and has no target network")
 
 
+def check_full_store(config, key: str, why: str) -> None:
+    """The refusals shared by every key that needs row indices into a full DeviceFrameStore (N_STEP > 1, MC_RETURN_FLOOR,
+    CQL_CALIBRATED): ValueError naming `key` (before any device work) for the ground-truth branch, LINEAR, generated tuples, a
+    feather+JPEG dataset and DEVICE_RESIDENT_DATA 'off'.  `why` says what the key needs the store for."""
+    if getattr(config, "TRAIN_ON_GROUND_TRUTH", False):
+        raise ValueError(f"{key} needs the TD branch: TRAIN_ON_GROUND_TRUTH regresses Q(s, a) on given targets and bootstraps nothing")
+    if getattr(config, "LINEAR", False):
+        raise ValueError(f"{key} does not cover LINEAR: y = r + (Qa - 0.1) has no discount, so neither an n-step form nor a discounted return to compare with")
+    if getattr(config, "SYNTHETIC_DATA", False) or config.DATASET in ("none", "synthetic"):
+        raise ValueError(f"{key} needs a fixed dataset with a successor relation: SYNTHETIC_DATA generates unrelated tuples on the fly")
+    if not is_shard_dir(config.DATASET):
+        raise ValueError(f"{key} needs a decoded-frame shard dataset held in HBM, not a feather+JPEG dataset "
+                         "(build one with python -m video_dqn_amd.shards)")
+    if str(getattr(config, "DEVICE_RESIDENT_DATA", "auto")).lower() == "off":
+        raise ValueError(f"{key} {why}: it needs the dataset in HBM, and DEVICE_RESIDENT_DATA is 'off'")
+
+
+def full_store_keys(config) -> list:
+    """[(key, why)] of the keys that are on and need the FULL dataset in HBM on every rank, whatever RANK_SHARDED_DATA says: the one
+    statement of that policy (run_train sizes, fits and logs by it)."""
+    keys = []
+    if bool(getattr(config, "PRIORITIZED_REPLAY", False)):
+        keys.append(("PRIORITIZED_REPLAY", "any sample may be drawn at any update"))
+    if int(getattr(config, "N_STEP", 1)) > 1:
+        keys.append(("N_STEP", "a chain's last frame may be any frame"))
+    for key in ("MC_RETURN_FLOOR", "CQL_CALIBRATED"):
+        if getattr(config, key, False):
+            keys.append((key, "the return table is indexed by the rows of the full store (the other stores hand out no row indices)"))
+    return keys
+
+
+def check_mc(config) -> None:
+    """MC_RETURN_FLOOR / CQL_CALIBRATED: raise ValueError naming the key (before any device work) for a value that is not a bool, for
+    CQL_CALIBRATED without CQL_ALPHA > 0, and for everything check_nstep refuses when N_STEP > 1 (check_full_store)."""
+    for key in ("MC_RETURN_FLOOR", "CQL_CALIBRATED"):
+        v = getattr(config, key, False)
+        if not isinstance(v, bool):
+            raise ValueError(f"{key} must be True or False, not {v!r}")
+        if not v:
+            continue
+        if key == "CQL_CALIBRATED" and not float(getattr(config, "CQL_ALPHA", 0.0)) > 0:
+            raise ValueError("CQL_CALIBRATED needs CQL_ALPHA > 0: it calibrates the conservative penalty, and there is none")
+        check_full_store(config, key, "indexes its return table by the rows of the resident store")
+
+
 def check_nstep(config, world_size: int = 1) -> None:
     """N_STEP: raise ValueError naming the key (before any device work) for a value that is not an integer in 1 .. 16 and, when it is
     above 1, for every configuration the chain walk does not cover: the ground-truth branch, LINEAR, generated tuples, a
@@ -190,18 +235,7 @@ def check_nstep(config, world_size: int = 1) -> None:
     check_config(n)
     if int(n) == 1:
         return
-    if getattr(config, "TRAIN_ON_GROUND_TRUTH", False):
-        raise ValueError("N_STEP > 1 needs the TD branch: TRAIN_ON_GROUND_TRUTH regresses Q(s, a) on given targets and bootstraps nothing")
-    if getattr(config, "LINEAR", False):
-        raise ValueError("N_STEP > 1 does not cover LINEAR: y = r + (Qa - 0.1) has no discount and no n-step form")
-    if getattr(config, "SYNTHETIC_DATA", False) or config.DATASET in ("none", "synthetic"):
-        raise ValueError("N_STEP > 1 needs a fixed dataset with a successor relation: SYNTHETIC_DATA generates unrelated tuples on the fly")
-    if not is_shard_dir(config.DATASET):
-        raise ValueError("N_STEP > 1 needs a decoded-frame shard dataset held in HBM, not a feather+JPEG dataset "
-                         "(build one with python -m video_dqn_amd.shards)")
-    if str(getattr(config, "DEVICE_RESIDENT_DATA", "auto")).lower() == "off":
-        raise ValueError("N_STEP > 1 ends a chain at any frame of the dataset: it needs the frames in HBM, "
-                         "and DEVICE_RESIDENT_DATA is 'off'")
+    check_full_store(config, "N_STEP > 1", "ends a chain at any frame of the dataset")
 
 
 def check_validation(config) -> None:
@@ -302,7 +336,9 @@ def run_train(config, resume_from=-1, max_steps=None, rank=0, world_size=1, log=
     check_target(config)
     check_validation(config)
     check_nstep(config, world_size)
+    check_mc(config)
     n_step = int(getattr(config, "N_STEP", 1))
+    mc_floor, cql_calibrated = bool(getattr(config, "MC_RETURN_FLOOR", False)), bool(getattr(config, "CQL_CALIBRATED", False))
     cql_alpha = float(getattr(config, "CQL_ALPHA", 0.0))
     target_tau = float(getattr(config, "TARGET_TAU", 0.0))
     clip_norm, weight_decay = float(getattr(config, "GRAD_CLIP_NORM", 0.0)), float(getattr(config, "WEIGHT_DECAY", 0.0))
@@ -337,10 +373,11 @@ def run_train(config, resume_from=-1, max_steps=None, rank=0, world_size=1, log=
             sharded = world_size > 1 and bool(getattr(config, "RANK_SHARDED_DATA", True))
             gather_threads = int(getattr(config, "HOST_GATHER_THREADS", 0))
             headroom = 32 << 30  # activations, workspaces, allocator slack
-            if per or n_step > 1:
-                # prioritized replay may draw any sample at any update, and an n-step chain may end at any frame: the full store on
-                # every rank, whatever RANK_SHARDED_DATA says
-                key = "PRIORITIZED_REPLAY" if per else "N_STEP > 1"
+            full = full_store_keys(config)
+            if full:
+                # prioritized replay may draw any sample at any update, an n-step chain may end at any frame, and the return table is
+                # indexed by the store's rows: the full store on every rank, whatever RANK_SHARDED_DATA says
+                key = full[0][0] + (" > 1" if full[0][0] == "N_STEP" else "")
                 if per:
                     from .replay import check_config
                     check_config(float(config.PER_ALPHA), float(config.PER_BETA), B * world_size, len(dataset))
@@ -352,12 +389,9 @@ def run_train(config, resume_from=-1, max_steps=None, rank=0, world_size=1, log=
                 if not fits:
                     raise ValueError(f"{key} needs the dataset in HBM: its frames ({need / 2**30:.1f} GiB + {headroom >> 30} GiB "
                                      f"of headroom) do not fit in {free / 2**30:.1f} GiB of free HBM" + (" on every rank" if world_size > 1 else ""))
-                if sharded and n_step > 1:
-                    log("N_STEP: every rank holds the full dataset in HBM (RANK_SHARDED_DATA does not apply: "
-                        "a chain's last frame may be any frame)")
-                if sharded and per:
-                    log("PRIORITIZED_REPLAY: every rank holds the full dataset in HBM (RANK_SHARDED_DATA does not apply: "
-                        "any sample may be drawn at any update)")
+                if sharded:
+                    for k_, why in sorted(full, key=lambda kw_: kw_[0] != "N_STEP"):  # (N_STEP's line first, as ever)
+                        log(f"{k_}: every rank holds the full dataset in HBM (RANK_SHARDED_DATA does not apply: {why})")
                 resident = True
             elif sharded and resident != "off":
                 # N ranks: each holds only the frames its samples of the current epoch reference (re-uploaded per epoch), not a full
@@ -434,13 +468,27 @@ def run_train(config, resume_from=-1, max_steps=None, rank=0, world_size=1, log=
                         allreduce_loss=(comm.launch_loss if comm else None), allreduce_wait=(comm.wait_last if comm else None),
                         allreduce_errors=((lambda: comm.launch_errors(replay.err_all)) if comm and replay else None),
                         grad_clip_norm=clip_norm, weight_decay=weight_decay, lr_fn=lr_fn, cql_alpha=cql_alpha,
-                        target_tau=target_tau)
-    walker = None
+                        target_tau=target_tau, mc_floor=mc_floor, cql_calibrated=cql_calibrated)
+    walker = returns = next_row = None
+    if n_step > 1 or mc_floor or cql_calibrated:
+        from .nstep import successors
+        next_row = successors(dataset.before[:, 0], dataset.after[:, 0])  # (host, once: shared by the walker and the return table)
+    if mc_floor or cql_calibrated:
+        # the Monte-Carlo return of every row at GAMMA, built once on the device over store.rew / store.term; every rank builds the
+        # same bits (no atomics), a resume rebuilds it: nothing of it is exchanged or saved.  One read-back, here, for the log line
+        from .mcreturn import ReturnTable
+        with torch.cuda.device(model.engine.device):
+            returns = ReturnTable(next_row, store.rew, store.term, float(config.GAMMA), model.engine.device)
+            g_max, g_mean = returns.summary()
+        log(f"Monte-Carlo returns: {returns.rows} rows, {returns.rounds} rounds of pointer doubling (the first {2 ** returns.rounds} rows "
+            f"of every chain) at GAMMA {float(config.GAMMA):g}; table max {g_max:.6g}, mean {g_mean:.6g}; " +
+            " and ".join((["MC_RETURN_FLOOR: y <- max(y, G) in front of the clip"] if mc_floor else []) +
+                         (["CQL_CALIBRATED: the penalty's logsumexp over max(Q, G)"] if cql_calibrated else [])) +
+            "; validation is unchanged")
     if n_step > 1:
         # the successor table from index.npz as it is (host, once), held on the device beside store.rew / store.term; the shares of
         # chain lengths are host arithmetic on that table: nothing is read back
-        from .nstep import NStepWalker, chain_shares, successors
-        next_row = successors(dataset.before[:, 0], dataset.after[:, 0])
+        from .nstep import NStepWalker, chain_shares
         walker = NStepWalker(next_row, store.rew, store.term, B, n_step, float(config.GAMMA), model.engine.device)
         shares = chain_shares(next_row, n_step)
         log(f"n-step returns: N_STEP {n_step}, one chain walk per update over {len(next_row)} rows; chains of " +
@@ -475,7 +523,7 @@ def run_train(config, resume_from=-1, max_steps=None, rank=0, world_size=1, log=
     elif store is not None:  # minibatches are gathered on the device; no loader, no host copies
         from .shards import RankShardedFrameStore as _RS
         # (N_STEP > 1 always holds the full DeviceFrameStore: `walker` is None on the rank-sharded path)
-        iterator = store.batches(B, config.SEED) if isinstance(store, _RS) else store.batches(B, config.SEED, rank, world_size, walker=walker)
+        iterator = store.batches(B, config.SEED) if isinstance(store, _RS) else store.batches(B, config.SEED, rank, world_size, walker=walker, returns=returns)
     elif stream is not None:
         iterator = stream.batches()
     else:
@@ -528,6 +576,7 @@ def run_train(config, resume_from=-1, max_steps=None, rank=0, world_size=1, log=
     stepper.replay = replay  # the run's PrioritizedSampler (PRIORITIZED_REPLAY), None otherwise: returned with the stepper
     stepper.augmenter = augmenter  # the run's Augmenter (AUG_SHIFT_PAD / AUG_FLIP / the colour keys), None otherwise
     stepper.nstep = walker  # the run's NStepWalker (N_STEP > 1), None otherwise
+    stepper.returns = returns  # the run's ReturnTable (MC_RETURN_FLOOR / CQL_CALIBRATED), None otherwise
     # VAL_INTERVAL > 0: the held-out pass (video_dqn_amd/validate.py) on rank 0 alone; the other ranks wait in the next update's
     # first collective.  Off: nothing is built, no launch differs
     validator = None
@@ -535,7 +584,7 @@ def run_train(config, resume_from=-1, max_steps=None, rank=0, world_size=1, log=
         from .validate import Validator
         validator = Validator(config, log=log)
     if replay is not None:
-        iterator = store.prioritized_batches(replay, sample_number, walker=walker)
+        iterator = store.prioritized_batches(replay, sample_number, walker=walker, returns=returns)
 
     running_loss = None
     late_loss = LateScalar()
@@ -544,6 +593,12 @@ def run_train(config, resume_from=-1, max_steps=None, rank=0, world_size=1, log=
     # CQL_ALPHA: and the penalty, for the `cql_penalty/train` scalar.  This rank's share of the global mean (the kernel divides by the
     # global batch) times the world size is the mean over its own samples: what rank 0 logs, with no collective
     late_pen, cql_pen = (LateScalar() if cql_alpha > 0 else None), None
+    # MC_RETURN_FLOOR / CQL_CALIBRATED: and the two mc_stats, this rank's shares like the penalty
+    late_mc, mc_seen = ((LateScalar(), LateScalar()) if returns is not None else None), [None, None]
+    # what the stores append behind the eight batch tensors, in this order: weight (PRIORITIZED_REPLAY), disc (N_STEP > 1), G
+    pos_weight = 8
+    pos_disc = pos_weight + (replay is not None)
+    pos_mc = pos_disc + (walker is not None)
     loss_stream = None  # N > 1: where the all-reduced loss is waited for and copied to the host
     num_steps = config.NUM_STEPS if max_steps is None else min(config.NUM_STEPS, sample_number + max_steps)
 
@@ -569,9 +624,10 @@ def run_train(config, resume_from=-1, max_steps=None, rank=0, world_size=1, log=
                                 valid if config.REMOVE_BEFORE_REWARD else None,
                                 gt if config.TRAIN_ON_GROUND_TRUTH else None,
                                 finish_allreduce=(comm.finish if comm else None),
-                                weights=(item[8] if replay is not None else None),
+                                weights=(item[pos_weight] if replay is not None else None),
                                 td_error=(replay.err if replay is not None else None), augment=aug_params, augment_color=aug_factors,
-                                discount=(item[-1] if walker is not None else None))  # (gather_nstep appends it)
+                                discount=(item[pos_disc] if walker is not None else None),  # (gather_nstep appends it)
+                                mc_return=(item[pos_mc] if returns is not None else None))
             if replay is not None:
                 replay.update()  # behind the loss launch (and, with N ranks, the error exchange that finish_allreduce joined)
             # every rank's `loss` is its share of the global mean (the TD kernel divides by the global batch): their SUM is the
@@ -592,6 +648,9 @@ def run_train(config, resume_from=-1, max_steps=None, rank=0, world_size=1, log=
                 grad_norm = late_norm.push(stepper.clip_out[:1], sample_number) or grad_norm  # (update number, norm): one late
             if late_pen is not None:
                 cql_pen = late_pen.push(stepper.cql_penalty, sample_number) or cql_pen
+            if late_mc is not None:
+                for k_ in (0, 1):
+                    mc_seen[k_] = late_mc[k_].push(stepper.mc_stats[k_:k_ + 1], sample_number) or mc_seen[k_]
             log_now = sample_number % 100 == 0 and rank == 0 and hasattr(config, "writer")
             if log_now:  # the reference logs the average INCLUDING this update's loss (:228-238): take it in before writing
                 average(late_loss.take())
@@ -603,6 +662,9 @@ def run_train(config, resume_from=-1, max_steps=None, rank=0, world_size=1, log=
                 config.writer.add_scalar("grad_norm/train", grad_norm[1], grad_norm[0])  # (the update it was measured at: one late)
             if log_now and cql_pen is not None:  # the unscaled penalty of the update one back; avg_q_loss/train is the full objective
                 config.writer.add_scalar("cql_penalty/train", cql_pen[1] * world_size, cql_pen[0])
+            if log_now and mc_seen[0] is not None:  # of the update one back, this rank's share times the world size, like the penalty
+                config.writer.add_scalar("mc_floor_share/train", mc_seen[0][1] * world_size, mc_seen[0][0])
+                config.writer.add_scalar("q_minus_return/train", mc_seen[1][1] * world_size, mc_seen[1][0])
             if log_now and replay is not None:
                 config.writer.add_scalar("per/beta", replay.beta(sample_number), sample_number)  # (host arithmetic: nothing read back)
             if validator is not None and validator.due(sample_number):  # :240 `# checkpoint and eval`: in front of the checkpoint
