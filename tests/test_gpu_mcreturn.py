@@ -431,7 +431,9 @@ def shards(tmp_path_factory):
 
 WAYS = {"floor": "MC_RETURN_FLOOR: True\n", "calibrated": "CQL_CALIBRATED: True\nCQL_ALPHA: 1.0\n",
         "both_nstep": "MC_RETURN_FLOOR: True\nCQL_CALIBRATED: True\nCQL_ALPHA: 1.0\nN_STEP: 3\n",
-        "both_per": "MC_RETURN_FLOOR: True\nCQL_CALIBRATED: True\nCQL_ALPHA: 1.0\nPRIORITIZED_REPLAY: True\n"}
+        "both_per": "MC_RETURN_FLOOR: True\nCQL_CALIBRATED: True\nCQL_ALPHA: 1.0\nPRIORITIZED_REPLAY: True\n",
+        # weight, discount and G all present at once
+        "both_nstep_per": "MC_RETURN_FLOOR: True\nCQL_CALIBRATED: True\nCQL_ALPHA: 1.0\nN_STEP: 3\nPRIORITIZED_REPLAY: True\n"}
 
 
 @pytest.mark.parametrize("way", list(WAYS))

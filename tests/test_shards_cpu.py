@@ -70,7 +70,7 @@ def test_host_frame_stream_equals_resident_store(tmp_path):
     sequence as the HBM-resident store for the same seed, bit for bit: frames, labels, order — over more than one epoch (the
     per-epoch permutation), with and without the PREVIOUS_IMAGES gather, and for both ranks of a two-rank job (rank-strided slices
     of one permutation).  Runs on the CPU: the gather is host code of libvdqn.so (no GPU call), the device is 'cpu'."""
-    from video_dqn_amd.shards import DeviceFrameStore, HostFrameStream
+    from video_dqn_amd.shards import Batch, DeviceFrameStore, HostFrameStream
     root = str(tmp_path / "shards")
     _synthetic_shards(root)
     for kw in (dict(inverse_actions=True), dict(inverse_actions=True, previous_images=True), dict(one_action=True, value_learning=True)):
@@ -83,6 +83,8 @@ def test_host_frame_stream_equals_resident_store(tmp_path):
                 per_epoch = (37 // world // 4)
                 for _ in range(2 * per_epoch + 3):  # crosses two epoch boundaries
                     a, b = next(ref), next(got)
+                    assert isinstance(a, Batch) and isinstance(b, Batch)
+                    assert a.weight is a.discount is a.mc_return is None and b.weight is b.discount is b.mc_return is None
                     assert a[2] == b[2] == 0
                     for x, y in zip(a[:2] + a[3:], b[:2] + b[3:]):
                         assert x.dtype == y.dtype and x.shape == y.shape
@@ -95,7 +97,7 @@ def test_rank_sharded_store_holds_a_quarter_and_draws_the_same_batches(tmp_path)
     — a quarter of the dataset when samples do not share frames — and yields bit for bit the minibatch sequence of the full
     per-rank copy (DeviceFrameStore.batches(B, seed, rank, 4)), across an epoch boundary (the subset is re-uploaded per epoch)."""
     import os
-    from video_dqn_amd.shards import FRAME_BYTES, DeviceFrameStore, RankShardedFrameStore
+    from video_dqn_amd.shards import FRAME_BYTES, Batch, DeviceFrameStore, RankShardedFrameStore
     root = str(tmp_path / "shards")
     n_samples, shard_frames = 32, 16
     os.makedirs(root)
@@ -118,6 +120,8 @@ def test_rank_sharded_store_holds_a_quarter_and_draws_the_same_batches(tmp_path)
         got = st.batches(B, 5)
         for k in range(2 * (n_samples // world // B) + 2):
             a, b = next(ref), next(got)
+            assert isinstance(a, Batch) and isinstance(b, Batch)
+            assert a.weight is a.discount is a.mc_return is None and b.weight is b.discount is b.mc_return is None
             for x, y in zip(a[:2] + a[3:], b[:2] + b[3:]):
                 assert x.shape == y.shape and torch.equal(torch.nan_to_num(x.float(), nan=-7.0), torch.nan_to_num(y.float(), nan=-7.0))
             assert st.bytes() == full.bytes() // world == (n_frames // world) * FRAME_BYTES

@@ -63,8 +63,8 @@ def main():
         for _ in range(steps):
             k[0] += 1
             idx = idxs[k[0] % 16]
-            item = store.gather(idx, table if mode == "on" else None)
-            stp.step(item[0], item[1], 0, item[3], item[4], item[5], mc_return=(item[8] if mode == "on" else None))
+            batch = store.gather(idx, returns=(table if mode == "on" else None))
+            stp.step(batch.before, batch.after, 0, batch.act, batch.rew, batch.term, mc_return=batch.mc_return)
         torch.cuda.synchronize()
         return (time.perf_counter() - t0) * 1e3 / steps
 

@@ -81,12 +81,8 @@ def main():
         for _ in range(steps):
             k[0] += 1
             idx = idxs[k[0] % 16]
-            if mode == "n1":
-                item = store.gather(idx)
-                stp.step(item[0], item[1], 0, item[3], item[4], item[5])
-            else:
-                item = store.gather_nstep(idx, walker)
-                stp.step(item[0], item[1], 0, item[3], item[4], item[5], discount=item[8])
+            batch = store.gather(idx, walker=(None if mode == "n1" else walker))
+            stp.step(batch.before, batch.after, 0, batch.act, batch.rew, batch.term, discount=batch.discount)
         torch.cuda.synchronize()
         return (time.perf_counter() - t0) * 1e3 / steps
 

@@ -697,6 +697,14 @@ class TDStepper:
             out[name + "_cat"] = [float(table[c, k] / table[c, 0]) if table[c, 0] > 0 else nan for c in range(table.shape[0])]
         return out
 
+    @staticmethod
+    def _check_input(name, t, dtype, shape):
+        """`step`'s per-update input `t`, when given, is a contiguous `dtype` device tensor of `shape` ((n,): of n elements)."""
+        if t is not None and not (t.dtype == dtype and t.is_contiguous() and t.is_cuda and
+                                  (tuple(t.shape) == shape if len(shape) > 1 else t.numel() == shape[0])):
+            raise _lib.VdqnError(f"TDStepper.step: {name} must be a contiguous {'f32' if dtype == torch.float32 else 'int32'} "
+                                 f"{''.join(f'[{d}]' for d in shape)} device tensor")
+
     def step(self, before, after, src_kind, act, rew, term, valid=None, gt=None, finish_allreduce=None, next_frames=None,
              weights=None, td_error=None, augment=None, discount=None, augment_color=None, mc_return=None) -> torch.Tensor:
         """One iteration of the reference loop body (train_q_network.py:213-227).  Returns the device loss scalar
@@ -737,36 +745,25 @@ class TDStepper:
             raise _lib.VdqnError("TDStepper.step: mc_return is required exactly when the stepper has mc_floor or cql_calibrated set "
                                  f"(mc_floor={bool(self.mc_flags & 1)}, cql_calibrated={bool(self.mc_flags & 2)}, "
                                  f"mc_return {'given' if mc_return is not None else 'missing'})")
-        if mc_return is not None:
-            if (mc_return.dtype != torch.float32 or tuple(mc_return.shape) != (self.B, self.net.num_classes) or not mc_return.is_contiguous()
-                    or not mc_return.is_cuda):
-                raise _lib.VdqnError(f"TDStepper.step: mc_return must be a contiguous f32 [{self.B}][{self.net.num_classes}] device tensor")
-        if augment_color is not None:
-            if augment is None:
-                raise _lib.VdqnError("TDStepper.step: augment_color needs augment as well (int32 zeros [B][4] = no shift, no mirror)")
-            if (augment_color.dtype != torch.int32 or tuple(augment_color.shape) != (self.B, 4) or not augment_color.is_contiguous()
-                    or not augment_color.is_cuda):
-                raise _lib.VdqnError(f"TDStepper.step: augment_color must be a contiguous int32 [{self.B}][4] device tensor")
-        if discount is not None:
-            if self.gtb or self.linear:
-                raise _lib.VdqnError("TDStepper.step: discount applies to the TD branch without LINEAR (TRAIN_ON_GROUND_TRUTH bootstraps "
-                                     "nothing; y = r + (Qa - 0.1) has no discount)")
-            if discount.dtype != torch.float32 or discount.numel() != self.B or not discount.is_contiguous() or not discount.is_cuda:
-                raise _lib.VdqnError(f"TDStepper.step: discount must be a contiguous f32 [{self.B}] device tensor")
+        self._check_input("mc_return", mc_return, torch.float32, (self.B, self.net.num_classes))
+        if augment_color is not None and augment is None:
+            raise _lib.VdqnError("TDStepper.step: augment_color needs augment as well (int32 zeros [B][4] = no shift, no mirror)")
+        self._check_input("augment_color", augment_color, torch.int32, (self.B, 4))
+        if discount is not None and (self.gtb or self.linear):
+            raise _lib.VdqnError("TDStepper.step: discount applies to the TD branch without LINEAR (TRAIN_ON_GROUND_TRUTH bootstraps "
+                                 "nothing; y = r + (Qa - 0.1) has no discount)")
+        self._check_input("discount", discount, torch.float32, (self.B,))
+        self._check_input("augment", augment, torch.int32, (self.B, 4))
         if augment is not None:
-            if augment.dtype != torch.int32 or tuple(augment.shape) != (self.B, 4) or not augment.is_contiguous() or not augment.is_cuda:
-                raise _lib.VdqnError(f"TDStepper.step: augment must be a contiguous int32 [{self.B}][4] device tensor")
             if next_frames is not None:
                 raise _lib.VdqnError("TDStepper.step: next_frames are packed ahead without the augmentation; pass one or the other")
             self._ahead = None  # frames packed ahead by an earlier call were packed without it: this call packs its own
         if td_error is not None and weights is None:
             raise _lib.VdqnError("TDStepper.step: td_error needs weights (it is written by the weighted loss launch)")
-        if weights is not None:
-            if self.gtb:
-                raise _lib.VdqnError("TDStepper.step: sample weights apply to the TD branch only (TRAIN_ON_GROUND_TRUTH has no weighted loss)")
-            for name, t in (("weights", weights), ("td_error", td_error)):
-                if t is not None and (t.dtype != torch.float32 or t.numel() != self.B or not t.is_contiguous() or not t.is_cuda):
-                    raise _lib.VdqnError(f"TDStepper.step: {name} must be a contiguous f32 [{self.B}] device tensor")
+        if weights is not None and self.gtb:
+            raise _lib.VdqnError("TDStepper.step: sample weights apply to the TD branch only (TRAIN_ON_GROUND_TRUTH has no weighted loss)")
+        self._check_input("weights", weights, torch.float32, (self.B,))
+        self._check_input("td_error", td_error, torch.float32, (self.B,))
         self.sample_number += 1
         if self.target_params is not None:
             # Soft target: fold `packed_target` from the averaged weights for every update, on the caller's stream, immediately in

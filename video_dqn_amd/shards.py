@@ -14,9 +14,11 @@ same 7-tuple as ``QLearningRealDataset(as_uint8=True)``; normalisation happens i
 """
 from __future__ import annotations
 
+import itertools
 import os
 import re
 import sys
+from typing import NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -25,6 +27,31 @@ from torch.utils import data
 from .dataset import detection_thresholds, multi_get, resize_center_crop_u8
 
 FRAME_BYTES = 224 * 224 * 3
+
+
+class Batch(NamedTuple):
+    """One minibatch on the device, as every batch source yields it.  The first eight fields are what trainer._to_device_batch
+    produces, and an index or a slice reads those eight alone, as when the batch was that tuple (`item[3:]` ends at gt); the
+    rest are per-sample inputs, read by name, which a source leaves None when the run has no use for them."""
+    before: torch.Tensor
+    after: torch.Tensor
+    src_kind: int  # 0: uint8 NHWC frames, 1: f32
+    act: torch.Tensor
+    rew: torch.Tensor
+    term: torch.Tensor
+    valid: torch.Tensor
+    gt: torch.Tensor
+    weight: Optional[torch.Tensor] = None  # PRIORITIZED_REPLAY: f32 [B] importance weights
+    discount: Optional[torch.Tensor] = None  # N_STEP > 1: f32 [B] per-sample discount
+    mc_return: Optional[torch.Tensor] = None  # MC_RETURN_FLOOR / CQL_CALIBRATED: f32 [B][n_cat], G at the sampled rows
+
+    def __getitem__(self, i):
+        return tuple.__getitem__(self, slice(8))[i]
+
+
+def _stacks(frames: torch.Tensor, n: int, nf: int) -> torch.Tensor:
+    """n * nf gathered frames as [n][nf] stacks where the PREVIOUS_IMAGES gather made them."""
+    return frames.view(n, nf, 224, 224, 3) if nf > 1 else frames
 
 
 def _prev_paths(path: str, start: int):
@@ -245,38 +272,24 @@ class DeviceFrameStore:
     def bytes(self):
         return self.frames.numel()
 
-    def gather(self, idx: torch.Tensor, returns=None):
-        """Device batch for sample indices ``idx`` (int64 device tensor), in the order trainer._to_device_batch produces:
-        (before, after, src_kind=0, act, rew, term, valid, gt).  returns (MC_RETURN_FLOOR / CQL_CALIBRATED: a
-        video_dqn_amd.mcreturn.ReturnTable over this store's rows): its G at the sampled rows, f32 [B][n_cat], appended."""
-        b = self.frames.index_select(0, self.before.index_select(0, idx).reshape(-1))
-        a = self.frames.index_select(0, self.after.index_select(0, idx).reshape(-1))
-        if self.nf > 1:
-            b = b.view(idx.shape[0], self.nf, 224, 224, 3)
-            a = a.view(idx.shape[0], self.nf, 224, 224, 3)
-        item = (b, a, 0, self.act.index_select(0, idx), self.rew.index_select(0, idx), self.term.index_select(0, idx),
-                self.valid.index_select(0, idx), self.gt.index_select(0, idx))
-        return item if returns is None else item + (returns.G.index_select(0, idx),)
-
-    def gather_nstep(self, idx: torch.Tensor, walker, returns=None):
-        """`gather` for n-step returns (video_dqn_amd.nstep.NStepWalker over this store's rew / term tables): one walk launch, then
-        `before`, act, valid and gt from the sampled rows idx, `after` from the LAST row of each chain, the folded rewards and terminals
-        in place of the rows' own, and the per-sample discount appended: (before, after, 0, act, rew_n, term_n, valid, gt, disc).
-        rew_n, term_n and disc are the walker's buffers: valid until its next walk.  returns: as `gather` takes it, appended behind disc —
-        still G at the SAMPLED rows idx, the whole-chain return against the n-step target."""
-        rew_n, term_n, disc, last_row, _ = walker.walk(idx)
-        b = self.frames.index_select(0, self.before.index_select(0, idx).reshape(-1))
-        a = self.frames.index_select(0, self.after.index_select(0, last_row).reshape(-1))
-        if self.nf > 1:
-            b = b.view(idx.shape[0], self.nf, 224, 224, 3)
-            a = a.view(idx.shape[0], self.nf, 224, 224, 3)
-        item = (b, a, 0, self.act.index_select(0, idx), rew_n, term_n, self.valid.index_select(0, idx), self.gt.index_select(0, idx), disc)
-        return item if returns is None else item + (returns.G.index_select(0, idx),)
+    def gather(self, idx: torch.Tensor, walker=None, returns=None) -> Batch:
+        """Device batch for sample indices ``idx`` (int64 device tensor): before, act, valid and gt from the sampled rows, src_kind 0.
+        walker (N_STEP > 1: a video_dqn_amd.nstep.NStepWalker over this store's rew / term tables): one walk launch first, then `after`
+        from the LAST row of each chain, rew / term the folded ones and `discount` the per-sample discount — all three the walker's
+        buffers: valid until its next walk.  returns (MC_RETURN_FLOOR / CQL_CALIBRATED: a video_dqn_amd.mcreturn.ReturnTable over this
+        store's rows): `mc_return` is its G, f32 [B][n_cat], at the SAMPLED rows either way — the whole-chain return against the n-step target."""
+        rew, term, disc, last_row = (None, None, None, idx) if walker is None else walker.walk(idx)[:4]
+        b = _stacks(self.frames.index_select(0, self.before.index_select(0, idx).reshape(-1)), idx.shape[0], self.nf)
+        a = _stacks(self.frames.index_select(0, self.after.index_select(0, last_row).reshape(-1)), idx.shape[0], self.nf)
+        act = self.act.index_select(0, idx)
+        if walker is None:
+            rew, term = self.rew.index_select(0, idx), self.term.index_select(0, idx)
+        return Batch(b, a, 0, act, rew, term, self.valid.index_select(0, idx), self.gt.index_select(0, idx), discount=disc,
+                     mc_return=(None if returns is None else returns.G.index_select(0, idx)))
 
     def batches(self, batch_size: int, seed: int, rank: int = 0, world_size: int = 1, walker=None, returns=None):
         """Endless stream of device batches: per epoch one seeded permutation (identical on every rank), rank r takes
-        perm[r::world], drop_last.  walker (N_STEP > 1): the same rows through `gather_nstep`.  returns: handed to the gather, which
-        appends G at the sampled rows behind everything else."""
+        perm[r::world], drop_last.  walker, returns: handed to `gather`."""
         epoch = 0
         n = len(self)
         per_rank = (n // world_size // batch_size) * batch_size
@@ -287,25 +300,19 @@ class DeviceFrameStore:
             g.manual_seed(seed + epoch)
             perm = torch.randperm(n, generator=g)[rank::world_size][:per_rank].to(self.device)
             for lo in range(0, per_rank, batch_size):
-                idx = perm[lo:lo + batch_size]
-                yield self.gather(idx, returns) if walker is None else self.gather_nstep(idx, walker, returns)
+                yield self.gather(perm[lo:lo + batch_size], walker, returns)
             epoch += 1
             print("reset iterator")
 
     def prioritized_batches(self, sampler, start_step: int, walker=None, returns=None):
-        """Endless stream for prioritized replay (video_dqn_amd.replay.PrioritizedSampler over len(self) samples): update
-        start_step + 1, + 2, ... draws this rank's indices and importance weights on the device and gathers them; yields the
-        `gather` tuple followed by the weights.  Each draw is queued when the caller asks for the batch, i.e. behind the previous
-        update's priority update.  walker (N_STEP > 1): the drawn rows through `gather_nstep`; the tuple is then
-        (before, after, 0, act, rew_n, term_n, valid, gt, weight, disc).  returns: as `batches` takes it; G stays last."""
+        """Endless stream for prioritized replay (video_dqn_amd.replay.PrioritizedSampler over len(self) samples): update start_step + 1,
+        + 2, ... draws this rank's indices and importance weights on the device and gathers them (walker, returns: handed to `gather`)
+        with `weight` set.  Each draw is queued when the caller asks for the batch, i.e. behind the previous update's priority update."""
         if sampler.n != len(self):
             raise ValueError(f"prioritized replay: the sampler's table has {sampler.n} entries, the dataset {len(self)} samples")
-        step = start_step
-        while True:
-            step += 1
+        for step in itertools.count(start_step + 1):
             idx, weight = sampler.sample(step)
-            item = self.gather(idx, returns) if walker is None else self.gather_nstep(idx, walker, returns)
-            yield item[:8] + (weight,) + item[8:]  # (the weight in front of what the gather appended: disc, G)
+            yield self.gather(idx, walker, returns)._replace(weight=weight)
 
 
 class RankShardedFrameStore:
@@ -402,14 +409,11 @@ class RankShardedFrameStore:
             self._load_epoch(idx)
             for lo in range(0, per_rank, batch_size):
                 sl = slice(lo, lo + batch_size)
-                b = self.frames.index_select(0, self._b_local[sl].reshape(-1))
-                a = self.frames.index_select(0, self._a_local[sl].reshape(-1))
-                if self.nf > 1:
-                    b = b.view(batch_size, self.nf, 224, 224, 3)
-                    a = a.view(batch_size, self.nf, 224, 224, 3)
+                b = _stacks(self.frames.index_select(0, self._b_local[sl].reshape(-1)), batch_size, self.nf)
+                a = _stacks(self.frames.index_select(0, self._a_local[sl].reshape(-1)), batch_size, self.nf)
                 i = self._idx_dev[sl]
-                yield (b, a, 0, self.act.index_select(0, i), self.rew.index_select(0, i), self.term.index_select(0, i),
-                       self.valid.index_select(0, i), self.gt.index_select(0, i))
+                yield Batch(b, a, 0, self.act.index_select(0, i), self.rew.index_select(0, i), self.term.index_select(0, i),
+                            self.valid.index_select(0, i), self.gt.index_select(0, i))
             epoch += 1
             print("reset iterator")
 
@@ -527,7 +531,7 @@ class HostFrameStream:
         return False
 
     def batches(self):
-        """Endless stream of device batches, the tuple of DeviceFrameStore.gather: (before, after, 0, act, rew, term, valid, gt)."""
+        """Endless stream of device batches, the `Batch` of DeviceFrameStore.gather without walker or returns."""
         half = self.B * self.nf
         while True:
             item = self._q.get()
@@ -539,12 +543,9 @@ class HostFrameStream:
                 cur.wait_event(ev)
                 dev.record_stream(cur)  # allocated on the prefetch stream, consumed on the compute stream
                 idx.record_stream(cur)
-            b, a = dev[:half], dev[half:]
-            if self.nf > 1:
-                b = b.view(self.B, self.nf, 224, 224, 3)
-                a = a.view(self.B, self.nf, 224, 224, 3)
-            yield (b, a, 0, self.act.index_select(0, idx), self.rew.index_select(0, idx), self.term.index_select(0, idx),
-                   self.valid.index_select(0, idx), self.gt.index_select(0, idx))
+            b, a = _stacks(dev[:half], self.B, self.nf), _stacks(dev[half:], self.B, self.nf)
+            yield Batch(b, a, 0, self.act.index_select(0, idx), self.rew.index_select(0, idx), self.term.index_select(0, idx),
+                        self.valid.index_select(0, idx), self.gt.index_select(0, idx))
 
     def close(self, timeout: float = 30.0):
         """Stop the producer thread and JOIN it (it may be inside vdqn_host_gather, reading the memory maps, or queueing copies

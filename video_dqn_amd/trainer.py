@@ -11,18 +11,22 @@ from pinned memory so the GPU never idles.
 from __future__ import annotations
 
 import os
-from collections import OrderedDict
+from collections import OrderedDict, namedtuple
+from functools import partial
 
 import numpy as np
 import torch
 from torch.utils import data
 
+from .augment import COLOR_KEYS, Augmenter
 from .dataset import QLearningRealDataset, SyntheticTupleDataset
 from .dist import BucketAllReduce, agree_all, broadcast_replica_state
 from .engine import TDStepper
 from .model import build_model
 from .optim import lr_at, schedule_active
-from .shards import ShardDataset, is_shard_dir
+from .shards import (FRAME_BYTES, Batch, DeviceFrameStore, HostFrameStream, RankShardedFrameStore, ShardDataset, collate_batches,
+                     is_shard_dir)
+from .validate import Validator
 
 
 def loopLoader(loader, on_reset=None):
@@ -260,7 +264,7 @@ def _to_device_batch(batch, device, num_classes=5):
     if gt.dim() == 1:
         gt = gt.view(-1, 1).expand(-1, num_classes)
     gt = gt.contiguous().to(device, **nb)
-    return before.contiguous(), after.contiguous(), src_kind, act, rew, term, valid, gt
+    return Batch(before.contiguous(), after.contiguous(), src_kind, act, rew, term, valid, gt)
 
 
 class DevicePrefetcher:
@@ -297,9 +301,10 @@ class LateScalar:
     """A device f32 scalar read on the host one update late: push() queues a copy into one of two pinned slots and an event behind
     it, waits for nothing, and hands back what the push before it queued — complete long ago, the GPU is busy with this update."""
 
-    def __init__(self):
+    def __init__(self, tag=None, source=None, scaled=False):
         self.host = torch.zeros(2, dtype=torch.float32).pin_memory()
         self.pending = None  # (slot, event, update number) of the copy not read yet
+        self.tag, self.source, self.scaled, self.seen = tag, source, scaled, None  # (late_scalars; seen: the last (number, value) kept)
 
     def push(self, src, number, stream=None, wait=None):
         """Queue the copy of update `number`'s value (on `stream`, behind wait(), when given: neither touches the compute stream).
@@ -325,39 +330,30 @@ class LateScalar:
         return number, float(self.host[slot])
 
 
-def run_train(config, resume_from=-1, max_steps=None, rank=0, world_size=1, log=print):
-    """train_q_network.py:84-250."""
-    aug_pad, aug_flip = getattr(config, "AUG_SHIFT_PAD", 0), getattr(config, "AUG_FLIP", False)
-    aug_actions = getattr(config, "AUG_FLIP_ACTIONS", [1, 2])
-    aug_color = tuple(getattr(config, k, 0.0) for k in ("AUG_BRIGHTNESS", "AUG_CONTRAST", "AUG_SATURATION"))
-    check_augment(aug_pad, aug_flip, aug_actions, *aug_color)
+def check_run(config, world_size: int = 1) -> None:
+    """Every check of the config, before any device work.  The order decides which error a config with several meets first."""
+    check_augment(getattr(config, "AUG_SHIFT_PAD", 0), getattr(config, "AUG_FLIP", False), getattr(config, "AUG_FLIP_ACTIONS", [1, 2]),
+                  *(getattr(config, k, 0.0) for k in COLOR_KEYS))
     check_optim(config)
     check_cql(config)
     check_target(config)
     check_validation(config)
     check_nstep(config, world_size)
     check_mc(config)
-    n_step = int(getattr(config, "N_STEP", 1))
-    mc_floor, cql_calibrated = bool(getattr(config, "MC_RETURN_FLOOR", False)), bool(getattr(config, "CQL_CALIBRATED", False))
-    cql_alpha = float(getattr(config, "CQL_ALPHA", 0.0))
-    target_tau = float(getattr(config, "TARGET_TAU", 0.0))
-    clip_norm, weight_decay = float(getattr(config, "GRAD_CLIP_NORM", 0.0)), float(getattr(config, "WEIGHT_DECAY", 0.0))
-    lr_fn = None
     if schedule_active(getattr(config, "LR_WARMUP_STEPS", 0), getattr(config, "LR_SCHEDULE", "constant")):
-        lr_args = (float(config.LEARNING_RATE), int(config.LR_WARMUP_STEPS), config.LR_SCHEDULE, float(config.LR_FINAL_FRACTION), int(config.NUM_STEPS))
-
-        def lr_fn(t):  # host arithmetic on the update number alone: a resumed run uses the uninterrupted run's rates
-            return lr_at(t, *lr_args)
-    per = bool(getattr(config, "PRIORITIZED_REPLAY", False))
-    if per:
+        float(config.LEARNING_RATE)  # (no check above looks at it: what is no number is refused here, not when the schedule is built)
+    if getattr(config, "PRIORITIZED_REPLAY", False):
         check_prioritized_replay(config, world_size)
-    torch.manual_seed(config.SEED)
-    np.random.seed(config.SEED)
-    log(f"Using: {config.device}")
+
+
+RunData = namedtuple("RunData", "dataset loader sampler store stream")
+
+
+def open_data(config, rank, world_size, log) -> RunData:
+    """The dataset, its loader and sampler and, for decoded-frame shards, where the frames live: `store` (resident in HBM, whole or
+    sharded by rank) or `stream` (streamed from memory-mapped shards); with neither, batches come from `loader`."""
     B = int(config.BATCH_SIZE)
-    params = {"batch_size": B, "num_workers": int(config.NUM_WORKERS), "drop_last": True}
-    store = None  # DeviceFrameStore when the decoded frames live in HBM
-    stream = None  # HostFrameStream when they are streamed from memory-mapped shards
+    store = stream = None
     if config.SYNTHETIC_DATA or config.DATASET in ("none", "synthetic"):
         nf = config.NUM_FRAMES or (4 if (config.PANORAMA or config.PREVIOUS_IMAGES) else 1)
         dataset = SyntheticTupleDataset(length=max(4 * B * world_size, 1024), num_frames=nf,
@@ -373,16 +369,17 @@ def run_train(config, resume_from=-1, max_steps=None, rank=0, world_size=1, log=
             sharded = world_size > 1 and bool(getattr(config, "RANK_SHARDED_DATA", True))
             gather_threads = int(getattr(config, "HOST_GATHER_THREADS", 0))
             headroom = 32 << 30  # activations, workspaces, allocator slack
+            dataset_bytes = lambda: sum(np.load(p_, mmap_mode="r").shape[0] for p_ in dataset._paths) * FRAME_BYTES  # noqa: E731
+            free_hbm = lambda: torch.cuda.mem_get_info(torch.device(config.device))[0]  # noqa: E731
             full = full_store_keys(config)
             if full:
                 # prioritized replay may draw any sample at any update, an n-step chain may end at any frame, and the return table is
                 # indexed by the store's rows: the full store on every rank, whatever RANK_SHARDED_DATA says
                 key = full[0][0] + (" > 1" if full[0][0] == "N_STEP" else "")
-                if per:
+                if getattr(config, "PRIORITIZED_REPLAY", False):
                     from .replay import check_config
                     check_config(float(config.PER_ALPHA), float(config.PER_BETA), B * world_size, len(dataset))
-                need = sum(np.load(p_, mmap_mode="r").shape[0] for p_ in dataset._paths) * 224 * 224 * 3
-                free, _ = torch.cuda.mem_get_info(torch.device(config.device))
+                need, free = dataset_bytes(), free_hbm()
                 fits = need + headroom < free
                 if world_size > 1:
                     fits = agree_all(fits, device=config.device)
@@ -398,17 +395,15 @@ def run_train(config, resume_from=-1, max_steps=None, rank=0, world_size=1, log=
                 # copy of the dataset; same minibatch sequence as the full per-rank copy.  Residency is decided from THIS rank's
                 # subset (epoch 0's distinct frames + 10 % for later epochs), one decision for the whole job: a rank on another
                 # input path would draw from a different sharding of the epoch than the resident ones
-                from .shards import RankShardedFrameStore
                 store = RankShardedFrameStore(config.DATASET, config.device, rank, world_size, threads=gather_threads, **kw)
-                need = store.epoch_frames(B, config.SEED) * 224 * 224 * 3
-                free, _ = torch.cuda.mem_get_info(torch.device(config.device))
+                need, free = store.epoch_frames(B, config.SEED) * FRAME_BYTES, free_hbm()
                 fits = agree_all(need + need // 10 + headroom < free, device=config.device)
                 if not fits and resident == "on":
                     raise RuntimeError(f"DEVICE_RESIDENT_DATA: 'on', but this rank's share of the frames ({need / 2**30:.1f} GiB + "
                                        f"{headroom >> 30} GiB of headroom) does not fit in {free / 2**30:.1f} GiB of free HBM on every rank")
                 if fits:
                     log(f"dataset resident in HBM, sharded by rank: the frames of this rank's samples are uploaded per epoch "
-                        f"({need / 2**30:.2f} GiB of the dataset's {store.total_frames * 224 * 224 * 3 / 2**30:.2f} GiB)")
+                        f"({need / 2**30:.2f} GiB of the dataset's {store.total_frames * FRAME_BYTES / 2**30:.2f} GiB)")
                 else:
                     store = None
                     log(f"this rank's share of the frames ({need / 2**30:.1f} GiB) does not fit in HBM on every rank: streaming")
@@ -416,21 +411,15 @@ def run_train(config, resume_from=-1, max_steps=None, rank=0, world_size=1, log=
             elif resident != "auto":
                 resident = resident == "on"
             else:  # frames + 32 GiB of headroom must fit in the GPU's free memory
-                n_frames = sum(np.load(p_, mmap_mode="r").shape[0] for p_ in dataset._paths)
-                free, _ = torch.cuda.mem_get_info(torch.device(config.device))
-                resident = n_frames * 224 * 224 * 3 + headroom < free
+                resident = dataset_bytes() + headroom < free_hbm()
                 if world_size > 1:
                     resident = agree_all(resident, device=config.device)
-            if store is not None:
-                pass
-            elif resident:
-                from .shards import DeviceFrameStore
+            if store is None and resident:
                 store = DeviceFrameStore(config.DATASET, config.device, **kw)
                 log(f"dataset resident in HBM: {store.bytes() / 2**30:.2f} GiB of frames")
-            elif str(getattr(config, "SHARD_INPUT", "stream")).lower() == "stream":
+            elif store is None and str(getattr(config, "SHARD_INPUT", "stream")).lower() == "stream":
                 # the frames do not fit (or residency is off): memory-mapped shards, native gather into pinned double buffers,
                 # host-to-device copies on a prefetch stream — same minibatch sequence as the resident store
-                from .shards import HostFrameStream
                 stream = HostFrameStream(config.DATASET, config.device, B, config.SEED, rank, world_size,
                                          threads=gather_threads, **kw)
                 log(f"dataset streamed from memory-mapped shards: {stream.threads} gather threads, {len(stream._slots)} pinned staging buffers")
@@ -442,21 +431,34 @@ def run_train(config, resume_from=-1, max_steps=None, rank=0, world_size=1, log=
     if world_size > 1:
         sampler = data.distributed.DistributedSampler(dataset, num_replicas=world_size, rank=rank, shuffle=True,
                                                       seed=config.SEED, drop_last=True)
-    extra = {}
-    if isinstance(dataset, ShardDataset):  # batched fetch: one gather per shard and batch instead of per-sample copies + collate
-        from .shards import collate_batches
+    batched = isinstance(dataset, ShardDataset)  # batched fetch: one gather per shard and batch instead of per-sample copies + collate
+    if batched:
         dataset.batched_fetch = True
-        extra["collate_fn"] = collate_batches
-    loader = data.DataLoader(dataset, **params, shuffle=(sampler is None), sampler=sampler, pin_memory=True,
-                             persistent_workers=params["num_workers"] > 0, **extra)
+    loader = data.DataLoader(dataset, batch_size=B, num_workers=int(config.NUM_WORKERS), drop_last=True, shuffle=(sampler is None),
+                             sampler=sampler, pin_memory=True, persistent_workers=int(config.NUM_WORKERS) > 0,
+                             collate_fn=(collate_batches if batched else None))
     log(len(dataset))
+    return RunData(dataset, loader, sampler, store, stream)
 
-    model = build_model(config, max_batch=2 * B)
-    comm = BucketAllReduce(world_size) if world_size > 1 else None
+
+def build_helpers(config, dataset, store, model, comm, rank, world_size, log):
+    """-> (stepper, replay, walker, returns, augmenter): the TDStepper and what the config's keys put beside it, each None when its keys
+    are off — PrioritizedSampler, NStepWalker, ReturnTable, Augmenter — with their banner lines."""
+    B, device = int(config.BATCH_SIZE), model.engine.device
+    n_step = int(getattr(config, "N_STEP", 1))
+    mc_floor, cql_calibrated = bool(getattr(config, "MC_RETURN_FLOOR", False)), bool(getattr(config, "CQL_CALIBRATED", False))
+    cql_alpha, target_tau = float(getattr(config, "CQL_ALPHA", 0.0)), float(getattr(config, "TARGET_TAU", 0.0))
+    clip_norm, weight_decay = float(getattr(config, "GRAD_CLIP_NORM", 0.0)), float(getattr(config, "WEIGHT_DECAY", 0.0))
+    aug_pad, aug_flip = getattr(config, "AUG_SHIFT_PAD", 0), getattr(config, "AUG_FLIP", False)
+    aug_actions, aug_color = getattr(config, "AUG_FLIP_ACTIONS", [1, 2]), tuple(getattr(config, k, 0.0) for k in COLOR_KEYS)
+    lr_fn = None  # (when on, host arithmetic on the update number alone: a resumed run uses the uninterrupted run's rates)
+    if schedule_active(getattr(config, "LR_WARMUP_STEPS", 0), getattr(config, "LR_SCHEDULE", "constant")):
+        lr_fn = partial(lr_at, base=float(config.LEARNING_RATE), warmup=int(config.LR_WARMUP_STEPS), schedule=config.LR_SCHEDULE,
+                        final_fraction=float(config.LR_FINAL_FRACTION), num_steps=int(config.NUM_STEPS))
     replay = None
-    if per:
+    if getattr(config, "PRIORITIZED_REPLAY", False):
         from .replay import PrioritizedSampler
-        replay = PrioritizedSampler(len(store), B, model.engine.device, alpha=float(config.PER_ALPHA), beta=float(config.PER_BETA),
+        replay = PrioritizedSampler(len(store), B, device, alpha=float(config.PER_ALPHA), beta=float(config.PER_BETA),
                                      num_steps=int(config.NUM_STEPS), seed=int(config.SEED), rank=rank, world_size=world_size)
         log(f"prioritized replay over {len(store)} samples: alpha {replay.alpha}, beta {replay.beta0} -> 1.0 at {replay.num_steps}")
     stepper = TDStepper(model.engine, B, lr=config.LEARNING_RATE, gamma=config.GAMMA,
@@ -477,8 +479,8 @@ def run_train(config, resume_from=-1, max_steps=None, rank=0, world_size=1, log=
         # the Monte-Carlo return of every row at GAMMA, built once on the device over store.rew / store.term; every rank builds the
         # same bits (no atomics), a resume rebuilds it: nothing of it is exchanged or saved.  One read-back, here, for the log line
         from .mcreturn import ReturnTable
-        with torch.cuda.device(model.engine.device):
-            returns = ReturnTable(next_row, store.rew, store.term, float(config.GAMMA), model.engine.device)
+        with torch.cuda.device(device):
+            returns = ReturnTable(next_row, store.rew, store.term, float(config.GAMMA), device)
             g_max, g_mean = returns.summary()
         log(f"Monte-Carlo returns: {returns.rows} rows, {returns.rounds} rounds of pointer doubling (the first {2 ** returns.rounds} rows "
             f"of every chain) at GAMMA {float(config.GAMMA):g}; table max {g_max:.6g}, mean {g_mean:.6g}; " +
@@ -489,7 +491,7 @@ def run_train(config, resume_from=-1, max_steps=None, rank=0, world_size=1, log=
         # the successor table from index.npz as it is (host, once), held on the device beside store.rew / store.term; the shares of
         # chain lengths are host arithmetic on that table: nothing is read back
         from .nstep import NStepWalker, chain_shares
-        walker = NStepWalker(next_row, store.rew, store.term, B, n_step, float(config.GAMMA), model.engine.device)
+        walker = NStepWalker(next_row, store.rew, store.term, B, n_step, float(config.GAMMA), device)
         shares = chain_shares(next_row, n_step)
         log(f"n-step returns: N_STEP {n_step}, one chain walk per update over {len(next_row)} rows; chains of " +
             ", ".join(f"{k + 1} row{'s' if k else ''}: {100 * s:.1f} %" for k, s in enumerate(shares)) +
@@ -506,30 +508,19 @@ def run_train(config, resume_from=-1, max_steps=None, rank=0, world_size=1, log=
              f"{int(config.LR_WARMUP_STEPS)} warm-up updates" if lr_fn is not None else ""))
     augmenter = None
     if aug_pad > 0 or aug_flip or any(j > 0 for j in aug_color):
-        from .augment import COLOR_KEYS, Augmenter
-        augmenter = Augmenter(B, model.engine.device, pad=aug_pad, flip=aug_flip, flip_actions=aug_actions, seed=int(config.SEED),
+        augmenter = Augmenter(B, device, pad=aug_pad, flip=aug_flip, flip_actions=aug_actions, seed=int(config.SEED),
                               rank=rank, world_size=world_size, brightness=aug_color[0], contrast=aug_color[1], saturation=aug_color[2])
-        swap = aug_flip and model.engine.action_dim == 3  # (one action column: nothing to exchange)
         on = [f"random shift of up to {aug_pad} pixels"] if aug_pad > 0 or aug_flip else []
-        if aug_flip:
-            on.append("random left-right mirror" + (f" with actions {aug_actions[0]} <-> {aug_actions[1]} exchanged" if swap else ""))
+        if aug_flip:  # (one action column: nothing to exchange)
+            on.append("random left-right mirror" + (f" with actions {aug_actions[0]} <-> {aug_actions[1]} exchanged" if model.engine.action_dim == 3 else ""))
         if augmenter.color is not None:
             on.append("colour jitter " + " ".join(f"{k[4:].lower()} x [{1 - j:g}, {1 + j:g}]" for k, j in zip(COLOR_KEYS, aug_color) if j > 0))
         log("augmentation: " + ", ".join(on) + ", one draw per sample and update, shared by s and s'")
-    if world_size > 1 and config.ARCHITECTURE != "extra_capacity" and getattr(config, "SYNC_BN", True):
-        model.engine.set_bn_sync(world_size)  # train-mode BatchNorm over the global batch, as the single-GPU reference sees it
-    if replay is not None:
-        iterator = None  # store.prioritized_batches, from the update after the resume point (below)
-    elif store is not None:  # minibatches are gathered on the device; no loader, no host copies
-        from .shards import RankShardedFrameStore as _RS
-        # (N_STEP > 1 always holds the full DeviceFrameStore: `walker` is None on the rank-sharded path)
-        iterator = store.batches(B, config.SEED) if isinstance(store, _RS) else store.batches(B, config.SEED, rank, world_size, walker=walker, returns=returns)
-    elif stream is not None:
-        iterator = stream.batches()
-    else:
-        iterator = DevicePrefetcher(loopLoader(loader, on_reset=(sampler.set_epoch if sampler else None)), model.engine.device)
-    os.makedirs(f"{config.folder}/models", exist_ok=True)
-    sample_number = resume_from + 1
+    return stepper, replay, walker, returns, augmenter
+
+
+def restore_state(config, model, stepper, replay, resume_from, rank, world_size, log) -> None:
+    """Resume (:192-198), bootstrap (:200-206), the replica broadcast, the :208 target sync and, behind it, the resumed soft target."""
     resumed_target = None  # TARGET_TAU: the checkpoint's averaged target weights, loaded behind the :208 sync below
     if resume_from > -1:  # :192-198
         model_loc = f"{config.folder}/models/sample{resume_from}.torch"
@@ -560,45 +551,66 @@ def run_train(config, resume_from=-1, max_steps=None, rank=0, world_size=1, log=
         # targets stay identical with no collective of their own — a resumed target comes from the one file every rank reads)
         eng = model.engine
         broadcast_replica_state([eng.params, eng.bnstats, eng.num_batches_tracked, stepper.exp_avg, stepper.exp_avg_sq] +
-                                ([stepper.target_params] if target_tau > 0 else []))
+                                ([stepper.target_params] if stepper.target_tau > 0 else []))
         steps = torch.tensor([stepper.adam_step], dtype=torch.int64, device=eng.device)
         torch.distributed.broadcast(steps, src=0)
         stepper.adam_step = int(steps.item())
         eng.mark_dirty()
     stepper.sync_target()  # :208
-    if target_tau > 0 and resume_from > -1:  # the averaged target of the interrupted run, in place of the copy :208 has just made
+    if stepper.target_tau > 0 and resume_from > -1:  # the averaged target of the interrupted run, in place of the copy :208 has just made
         if resumed_target is not None:
             load_target_state_dict(stepper, resumed_target)
             log("soft target updates: target weights restored from the checkpoint")
         else:
             log("soft target updates: the checkpoint has no target_state_dict, the target starts from the online weights")
+
+
+def late_scalars(stepper, returns):
+    """The device scalars logged beside the loss, each a LateScalar with its tag and source; scaled: this rank's share of a global mean."""
+    late = []
+    if stepper.grad_clip_norm > 0:  # the norm BEFORE clipping, as clip_grad_norm_ returns it; non-finite values show here
+        late.append(LateScalar("grad_norm/train", stepper.clip_out[:1]))
+    if stepper.cql_alpha > 0:  # the unscaled penalty; avg_q_loss/train is the full objective
+        late.append(LateScalar("cql_penalty/train", stepper.cql_penalty, scaled=True))
+    if returns is not None:
+        late += [LateScalar("mc_floor_share/train", stepper.mc_stats[0:1], scaled=True), LateScalar("q_minus_return/train", stepper.mc_stats[1:2], scaled=True)]
+    return late
+
+
+def run_train(config, resume_from=-1, max_steps=None, rank=0, world_size=1, log=print):
+    """train_q_network.py:84-250."""
+    check_run(config, world_size)
+    torch.manual_seed(config.SEED)
+    np.random.seed(config.SEED)
+    log(f"Using: {config.device}")
+    B = int(config.BATCH_SIZE)
+    dataset, loader, sampler, store, stream = open_data(config, rank, world_size, log)
+    model = build_model(config, max_batch=2 * B)
+    comm = BucketAllReduce(world_size) if world_size > 1 else None
+    stepper, replay, walker, returns, augmenter = build_helpers(config, dataset, store, model, comm, rank, world_size, log)
+    swap = augmenter is not None and augmenter.flip and model.engine.action_dim == 3  # mirrored samples exchange their action labels
+    if world_size > 1 and config.ARCHITECTURE != "extra_capacity" and getattr(config, "SYNC_BN", True):
+        model.engine.set_bn_sync(world_size)  # train-mode BatchNorm over the global batch, as the single-GPU reference sees it
+    if replay is not None:  # (nothing is drawn before the first update asks for its batch, behind the resume below)
+        iterator = store.prioritized_batches(replay, resume_from + 1, walker=walker, returns=returns)
+    elif isinstance(store, RankShardedFrameStore):  # (a key that needs a walker or a return table holds the full store instead)
+        iterator = store.batches(B, config.SEED)
+    elif store is not None:  # minibatches are gathered on the device; no loader, no host copies
+        iterator = store.batches(B, config.SEED, rank, world_size, walker=walker, returns=returns)
+    elif stream is not None:
+        iterator = stream.batches()
+    else:
+        iterator = DevicePrefetcher(loopLoader(loader, on_reset=(sampler.set_epoch if sampler else None)), model.engine.device)
+    os.makedirs(f"{config.folder}/models", exist_ok=True)
+    sample_number = resume_from + 1
+    restore_state(config, model, stepper, replay, resume_from, rank, world_size, log)
     stepper.sample_number = sample_number
-    stepper.replay = replay  # the run's PrioritizedSampler (PRIORITIZED_REPLAY), None otherwise: returned with the stepper
-    stepper.augmenter = augmenter  # the run's Augmenter (AUG_SHIFT_PAD / AUG_FLIP / the colour keys), None otherwise
-    stepper.nstep = walker  # the run's NStepWalker (N_STEP > 1), None otherwise
-    stepper.returns = returns  # the run's ReturnTable (MC_RETURN_FLOOR / CQL_CALIBRATED), None otherwise
-    # VAL_INTERVAL > 0: the held-out pass (video_dqn_amd/validate.py) on rank 0 alone; the other ranks wait in the next update's
-    # first collective.  Off: nothing is built, no launch differs
-    validator = None
-    if int(getattr(config, "VAL_INTERVAL", 0)) > 0 and rank == 0:
-        from .validate import Validator
-        validator = Validator(config, log=log)
-    if replay is not None:
-        iterator = store.prioritized_batches(replay, sample_number, walker=walker, returns=returns)
+    stepper.replay, stepper.augmenter, stepper.nstep, stepper.returns = replay, augmenter, walker, returns  # returned with the stepper
+    # VAL_INTERVAL > 0: the held-out pass (validate.py) on rank 0 alone, the others wait in the next update's first collective; off: nothing is built
+    validator = Validator(config, log=log) if int(getattr(config, "VAL_INTERVAL", 0)) > 0 and rank == 0 else None
 
     running_loss = None
-    late_loss = LateScalar()
-    # GRAD_CLIP_NORM: the gradient norm is read back the same way for the `grad_norm/train` scalar
-    late_norm, grad_norm = (LateScalar() if clip_norm > 0 else None), None
-    # CQL_ALPHA: and the penalty, for the `cql_penalty/train` scalar.  This rank's share of the global mean (the kernel divides by the
-    # global batch) times the world size is the mean over its own samples: what rank 0 logs, with no collective
-    late_pen, cql_pen = (LateScalar() if cql_alpha > 0 else None), None
-    # MC_RETURN_FLOOR / CQL_CALIBRATED: and the two mc_stats, this rank's shares like the penalty
-    late_mc, mc_seen = ((LateScalar(), LateScalar()) if returns is not None else None), [None, None]
-    # what the stores append behind the eight batch tensors, in this order: weight (PRIORITIZED_REPLAY), disc (N_STEP > 1), G
-    pos_weight = 8
-    pos_disc = pos_weight + (replay is not None)
-    pos_mc = pos_disc + (walker is not None)
+    late_loss, late = LateScalar(), late_scalars(stepper, returns)
     loss_stream = None  # N > 1: where the all-reduced loss is waited for and copied to the host
     num_steps = config.NUM_STEPS if max_steps is None else min(config.NUM_STEPS, sample_number + max_steps)
 
@@ -612,22 +624,20 @@ def run_train(config, resume_from=-1, max_steps=None, rank=0, world_size=1, log=
         while sample_number < num_steps:
             sample_number += 1
             model.set_train()  # :221 (flags only; the engine's BatchNorm is always in eval mode in extra_capacity)
-            item = next(iterator)
-            before, after, src_kind, act, rew, term, valid, gt = item[:8]
+            batch = next(iterator)
+            act = batch.act
             aug_params = aug_factors = None
             if augmenter is not None:  # this update's draw(s) and the mirrored samples' action labels: small launches, nothing read back
                 aug_params, aug_factors = augmenter.draw(sample_number), augmenter.color
                 if swap:
                     act = augmenter.actions(act.contiguous())
             # the stepper performs the :215-216 target refresh itself (sample_number % TARGET_UPDATE_INTERVAL == 0)
-            loss = stepper.step(before, after, src_kind, act, rew, term,
-                                valid if config.REMOVE_BEFORE_REWARD else None,
-                                gt if config.TRAIN_ON_GROUND_TRUTH else None,
-                                finish_allreduce=(comm.finish if comm else None),
-                                weights=(item[pos_weight] if replay is not None else None),
+            loss = stepper.step(batch.before, batch.after, batch.src_kind, act, batch.rew, batch.term,
+                                batch.valid if config.REMOVE_BEFORE_REWARD else None,
+                                batch.gt if config.TRAIN_ON_GROUND_TRUTH else None,
+                                finish_allreduce=(comm.finish if comm else None), weights=batch.weight,
                                 td_error=(replay.err if replay is not None else None), augment=aug_params, augment_color=aug_factors,
-                                discount=(item[pos_disc] if walker is not None else None),  # (gather_nstep appends it)
-                                mc_return=(item[pos_mc] if returns is not None else None))
+                                discount=batch.discount, mc_return=batch.mc_return)
             if replay is not None:
                 replay.update()  # behind the loss launch (and, with N ranks, the error exchange that finish_allreduce joined)
             # every rank's `loss` is its share of the global mean (the TD kernel divides by the global batch): their SUM is the
@@ -644,13 +654,8 @@ def run_train(config, resume_from=-1, max_steps=None, rank=0, world_size=1, log=
                 average(late_loss.push(buf, sample_number, stream=loss_stream, wait=work.wait))
             else:
                 average(late_loss.push(loss, sample_number))
-            if late_norm is not None:
-                grad_norm = late_norm.push(stepper.clip_out[:1], sample_number) or grad_norm  # (update number, norm): one late
-            if late_pen is not None:
-                cql_pen = late_pen.push(stepper.cql_penalty, sample_number) or cql_pen
-            if late_mc is not None:
-                for k_ in (0, 1):
-                    mc_seen[k_] = late_mc[k_].push(stepper.mc_stats[k_:k_ + 1], sample_number) or mc_seen[k_]
+            for s in late:
+                s.seen = s.push(s.source, sample_number) or s.seen  # (update number, value): one late
             log_now = sample_number % 100 == 0 and rank == 0 and hasattr(config, "writer")
             if log_now:  # the reference logs the average INCLUDING this update's loss (:228-238): take it in before writing
                 average(late_loss.take())
@@ -658,13 +663,10 @@ def run_train(config, resume_from=-1, max_steps=None, rank=0, world_size=1, log=
                 print(f"\rbatch:{sample_number}/{config.NUM_STEPS} avg_loss: {running_loss}", end="")
             if log_now and running_loss is not None:
                 config.writer.add_scalar("avg_q_loss/train", running_loss, sample_number)  # :236-238
-            if log_now and grad_norm is not None:  # the norm BEFORE clipping, as clip_grad_norm_ returns it; non-finite values show here
-                config.writer.add_scalar("grad_norm/train", grad_norm[1], grad_norm[0])  # (the update it was measured at: one late)
-            if log_now and cql_pen is not None:  # the unscaled penalty of the update one back; avg_q_loss/train is the full objective
-                config.writer.add_scalar("cql_penalty/train", cql_pen[1] * world_size, cql_pen[0])
-            if log_now and mc_seen[0] is not None:  # of the update one back, this rank's share times the world size, like the penalty
-                config.writer.add_scalar("mc_floor_share/train", mc_seen[0][1] * world_size, mc_seen[0][0])
-                config.writer.add_scalar("q_minus_return/train", mc_seen[1][1] * world_size, mc_seen[1][0])
+            if log_now:
+                for s in late:
+                    if s.seen is not None:  # at the update it was measured at, one back; a share times the world size: rank 0's own mean
+                        config.writer.add_scalar(s.tag, s.seen[1] * world_size if s.scaled else s.seen[1], s.seen[0])
             if log_now and replay is not None:
                 config.writer.add_scalar("per/beta", replay.beta(sample_number), sample_number)  # (host arithmetic: nothing read back)
             if validator is not None and validator.due(sample_number):  # :240 `# checkpoint and eval`: in front of the checkpoint
@@ -673,7 +675,7 @@ def run_train(config, resume_from=-1, max_steps=None, rank=0, world_size=1, log=
                 torch.cuda.synchronize()
                 save_checkpoint(f"{config.folder}/models/sample{sample_number}.torch", sample_number, model, stepper,
                                 replay_state=(replay.state_dict() if replay is not None else None),
-                                target_state_dict=(target_state_dict(stepper, model) if target_tau > 0 else None))
+                                target_state_dict=(target_state_dict(stepper, model) if stepper.target_tau > 0 else None))
         average(late_loss.take())
         torch.cuda.synchronize()
     finally:
