@@ -526,6 +526,11 @@ typedef struct vdqn_step_args {
                                  same factors for both).  NULL: no colour jitter.  vdqn_net_td_eval refuses it.  Added beside aug_params without a change
                                  of vdqn_abi_version(), as sample_gamma was: a binding that predates it fails the
                                  vdqn_abi_struct_size(6) comparison at load time. */
+  const int32_t* aug_zoom;    /* optional device int32 [batch][4] {ax, ay, bx, by}, 16-byte aligned, indexed like aug_params (which must
+                                 be given as well): vdqn_net_td_forward packs `before` and `after` with vdqn_pack_input_aug_zoom (the
+                                 same window for both; aug_color, when given, goes through the same launch).  NULL: no zoom.
+                                 vdqn_net_td_eval refuses it.  Added directly behind aug_color without a change of vdqn_abi_version(),
+                                 as aug_color was. */
   const float* sample_gamma;  /* optional [batch] per-sample discount (n-step returns: `after`, rew, term are then those vdqn_nstep_walk
                                  folded along each sample's chain): the loss launch is vdqn_td_loss_nstep with it, and `gamma` is not
                                  read.  TD branch without `linear` only: vdqn_net_td_forward(_cql) fail by name otherwise, and
@@ -556,7 +561,7 @@ int vdqn_net_td_forward_mc(vdqn_net* net, const vdqn_step_args* a, float cql_alp
  * packed_target, before, after, src_kind, batch, act, rew, term, valid, gamma, clip_rect, linear, use_valid, loss_kind, acts_online,
  * acts_target; reads neither params, bnstats, bwd, grads, loss nor q_before.  1 <= batch and 2 * batch <= max_batch: the activation
  * layouts are those of 2 * batch and batch samples, which fit the workspaces of any larger batch, so a short last batch needs no
- * workspace of its own.  Refuses by name train_on_ground_truth, sample_weight, sample_err, aug_params, aug_color, packed_frames,
+ * workspace of its own.  Refuses by name train_on_ground_truth, sample_weight, sample_err, aug_params, aug_color, aug_zoom, packed_frames,
  * sample_gamma (validation is one-step whatever the training target, so runs with different N_STEP are judged alike) and
  * acts_samples != 0. */
 int vdqn_net_td_eval(vdqn_net* net, const vdqn_step_args* a, double* acc, void* stream);
@@ -671,8 +676,8 @@ int vdqn_pack_input_aug(const void* src, void* dst, int32_t n_img, int32_t frame
  *   saturation:  g = (77 R + 150 G + 29 B + 128) / 256;   v = clamp(g + ((v - g) * f_s + 128) / 256, 0, 255)   for v in R, G, B
  *   brightness:  v = min(255, (v * f_b + 128) / 256)
  *   contrast:    v = clamp(128 + ((v - 128) * f_c + 128) / 256, 0, 255)          (pivot: mid-grey 128, no per-frame mean)
- * then vdqn_pack_input's normalisation.  (256, 256, 256) is the identity on every byte.  Hue, white balance, blur and resized crops
- * are not covered. */
+ * then vdqn_pack_input's normalisation.  (256, 256, 256) is the identity on every byte.  Hue, white balance and blur are not
+ * covered. */
 /* color[i] (int32 [n][4], 16-byte aligned) = the draw of sample first + i of a global batch of `global_batch` samples at update `step`:
  *   h = splitmix64(splitmix64(seed ^ 0x415547434F4C5231 "AUGCOLR1") ^ (step * global_batch + first + i))
  *   f_k = 256 - j_k + ((((h >> 16 k) & 0xFFFF) * (2 j_k + 1)) >> 16)     k = 0 brightness (jb), 1 contrast (jc), 2 saturation (js)
@@ -685,6 +690,32 @@ int vdqn_aug_draw_color(uint64_t seed, uint64_t step, int32_t global_batch, int3
  * [0, 512] before use and word 3 is ignored: any int32 content is safe.  Factors (256, 256, 256) give vdqn_pack_input_aug's output. */
 int vdqn_pack_input_aug_color(const void* src, void* dst, int32_t n_img, int32_t frames_per_sample, const int32_t* params,
                               const int32_t* color, int32_t n_params, int32_t dtype, void* stream);
+
+/* Random zoom (a change of focal length): a window of [1 - J, 1] of the frame's side, J <= 0.5, at a uniform position inside the frame,
+ * resampled back to 224 x 224 — bilinear with Q16 coordinates and Q8 weights in integer arithmetic on the uint8 pixels, so the packed
+ * operand still equals vdqn_pack_input of host-augmented frames bit for bit (tests/aug_zoom_oracle.py).  One int32 {ax, ay, bx, by} per
+ * SAMPLE, shared by its frames and by s and s': ax, ay the Q16 source step per output pixel (65536 = 1.0, never more: no zoom-out), bx,
+ * by the Q16 source coordinate of output pixel 0.  ">>" is arithmetic.  Output pixel (Y, X) of a frame Z, per channel:
+ *   u = bx + X * ax;  x0 = u >> 16;  wx = (u >> 8) & 255;   v = by + Y * ay;  y0 = v >> 16;  wy = (v >> 8) & 255
+ *   xa = clamp(x0, 0, 223), xb = clamp(x0 + 1, 0, 223), ya, yb likewise
+ *   top = Z[ya][xa] * (256 - wx) + Z[ya][xb] * wx;   bot = the same on row yb;   out = (top * (256 - wy) + bot * wy + 32768) >> 16
+ * Z is the frame after shift and mirror (vdqn_pack_input_aug's remap applied to each tap); the colour transform works on the
+ * resampled bytes.  {65536, 65536, 0, 0} is the identity on every byte.  Zoom-out and rotation are not covered. */
+/* zoom[i] (int32 [n][4], 16-byte aligned) = the draw of sample first + i of a global batch of `global_batch` samples at update `step`:
+ *   h = splitmix64(splitmix64(seed ^ 0x4155475A4F4F4D31 "AUGZOOM1") ^ (step * global_batch + first + i));   h_k = (h >> 16 k) & 0xFFFF
+ *   ax = 65536 - ((h_0 * (jz + 1)) >> 16);   ay = aspect ? 65536 - ((h_1 * (jz + 1)) >> 16) : ax
+ *   origin(a, hk) = ((((hk * (((224 * 65536 - 224 * a) >> 8) + 1)) >> 16) << 8) + (a >> 1) - 32768;   bx = origin(ax, h_2), by = origin(ay, h_3)
+ * jz is the Q16 width int(J * 65536 + 0.5), 0 .. 32768; jz = 0 gives the identity row.  The window always lies inside the frame:
+ * bx + 223 ax < 224 * 65536.  A stream of its own: the other draws at the same seed and update do not depend on it.  Slices as
+ * vdqn_aug_draw. */
+int vdqn_aug_draw_zoom(uint64_t seed, uint64_t step, int32_t global_batch, int32_t first, int32_t n, int32_t jz /* Q16 width, 0 .. 32768 */,
+                       int32_t aspect, int32_t* zoom, void* stream);
+/* vdqn_pack_input_aug(_color) of the resampled frames: frame i takes params, color and zoom row (i / frames_per_sample) % n_params (each
+ * int32 [n_params][4], 16-byte aligned; color may be NULL: no colour transform).  ax, ay are clamped to [0, 65536] and bx, by to
+ * +-224 * 65536 before use, and every tap is clamped into the frame: any int32 content is safe.  The identity row gives
+ * vdqn_pack_input_aug's (vdqn_pack_input_aug_color's) output. */
+int vdqn_pack_input_aug_zoom(const void* src, void* dst, int32_t n_img, int32_t frames_per_sample, const int32_t* params,
+                             const int32_t* color /* NULL ok */, const int32_t* zoom, int32_t n_params, int32_t dtype, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Data-parallel exchange: one process per GPU, the flat f32 gradient SUM-all-reduced over RCCL (xGMI)

@@ -70,7 +70,7 @@ class StepArgs(C.Structure):
                 ("acts_online", c_vp), ("acts_target", c_vp), ("bwd", c_vp), ("grads", c_vp), ("loss", c_vp),
                 ("q_before", c_vp), ("loss_kind", c_i32), ("packed_frames", c_vp), ("acts_samples", c_i32),
                 ("sample_weight", c_vp), ("sample_err", c_vp), ("aug_params", c_vp), ("aug_color", c_vp),
-                ("sample_gamma", c_vp)]
+                ("aug_zoom", c_vp), ("sample_gamma", c_vp)]
 
 
 ALLREDUCE_FN = C.CFUNCTYPE(None, c_vp, c_vp, c_i64, c_vp)  # vdqn_allreduce_fn(user, buf, count, stream)
@@ -144,6 +144,8 @@ _SIGS = {
     "vdqn_pack_input_aug": (C.c_int, [c_vp, c_vp, c_i32, c_i32, c_vp, c_i32, c_i32, c_vp]),
     "vdqn_aug_draw_color": (C.c_int, [C.c_uint64, C.c_uint64, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp]),
     "vdqn_pack_input_aug_color": (C.c_int, [c_vp, c_vp, c_i32, c_i32, c_vp, c_vp, c_i32, c_i32, c_vp]),
+    "vdqn_aug_draw_zoom": (C.c_int, [C.c_uint64, C.c_uint64, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp]),
+    "vdqn_pack_input_aug_zoom": (C.c_int, [c_vp, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_i32, c_i32, c_vp]),
     "vdqn_clip_workspace_bytes": (c_i64, [c_i32]),
     "vdqn_grad_sumsq": (C.c_int, [c_vp, c_i64, c_vp, c_i32, c_vp]),
     "vdqn_clip_finalize": (C.c_int, [c_vp, c_i32, C.c_double, c_vp, c_vp]),

@@ -16,6 +16,14 @@ saturation, then brightness, then contrast about mid-grey 128 — inside the sam
 operand still equals ``vdqn_pack_input`` of host-augmented frames bit for bit (tests/aug_color_oracle.py).  One more small launch
 per update.
 
+Random zoom (``AUG_ZOOM``: J in [0, 0.5], ``AUG_ZOOM_ASPECT``) is the scale axis, a change of focal length: a window whose side is uniform
+in [1 - J, 1] of the frame's (the two sides independently with ``AUG_ZOOM_ASPECT``), at a uniform position inside the frame, resampled
+back to 224 x 224 — never a zoom-out.  One ``{ax, ay, bx, by}`` (Q16 step and origin) per update and per sample from a stream of its
+own, shared by the sample's frames and by s and s'.  The resample is bilinear in integer arithmetic on the uint8 pixels (Q16
+coordinates, Q8 weights), applied to the shifted / mirrored frame and in front of the colour transform, inside one pack launch
+(``vdqn_pack_input_aug_zoom``), so the operand still equals ``vdqn_pack_input`` of host-augmented frames bit for bit
+(tests/aug_zoom_oracle.py).  One more small launch per update.
+
 Data parallelism keeps N ranks == one process on the big batch: every rank draws its slice of the one global draw.
 """
 from __future__ import annotations
@@ -26,6 +34,7 @@ from . import _lib
 
 MAX_PAD = 32  # vdqn_aug_draw (include/vdqn.h)
 COLOR_KEYS = ("AUG_BRIGHTNESS", "AUG_CONTRAST", "AUG_SATURATION")  # the order of the factors in a colour row
+MAX_ZOOM = 0.5  # vdqn_aug_draw_zoom: the window's side is at least half the frame's (a magnification of 2 at the most)
 
 
 def jq(j: float) -> int:
@@ -33,8 +42,20 @@ def jq(j: float) -> int:
     return int(float(j) * 256 + 0.5)
 
 
-def check_config(pad, flip, flip_actions, brightness=0.0, contrast=0.0, saturation=0.0) -> None:
+def jz(j: float) -> int:
+    """The Q16 width vdqn_aug_draw_zoom takes: int(J * 65536 + 0.5), 0 .. 32768 for J in [0, 0.5]."""
+    return int(float(j) * 65536 + 0.5)
+
+
+def check_config(pad, flip, flip_actions, brightness=0.0, contrast=0.0, saturation=0.0, zoom=0.0, zoom_aspect=False) -> None:
     """Raise ValueError, naming the config key, for values the augmentation does not take (host only: no device work)."""
+    if isinstance(zoom, bool) or not isinstance(zoom, (int, float)) or not 0 <= zoom <= MAX_ZOOM:  # (NaN fails both comparisons)
+        raise ValueError(f"AUG_ZOOM must be a number in [0, {MAX_ZOOM}] (0 = off: the window's side is drawn from [1 - AUG_ZOOM, 1] of the "
+                         f"frame's), got {zoom!r}")
+    if not isinstance(zoom_aspect, bool):
+        raise ValueError(f"AUG_ZOOM_ASPECT must be True or False (got {zoom_aspect!r})")
+    if zoom_aspect and jz(zoom) == 0:
+        raise ValueError(f"AUG_ZOOM_ASPECT is True, but AUG_ZOOM is {zoom!r}: there is no window to stretch (set AUG_ZOOM > 0)")
     for key, j in zip(COLOR_KEYS, (brightness, contrast, saturation)):
         if isinstance(j, bool) or not isinstance(j, (int, float)) or not 0 <= j <= 1:  # (NaN fails both comparisons)
             raise ValueError(f"{key} must be a number in [0, 1] (0 = off: the factor is drawn from [1 - {key}, 1 + {key}]), got {j!r}")
@@ -77,21 +98,41 @@ def aug_draw_color(seed: int, step: int, global_batch: int, first: int, n: int, 
     return out
 
 
+def aug_draw_zoom(seed: int, step: int, global_batch: int, first: int, n: int, jz: int, aspect: bool, device="cuda",
+                  out: torch.Tensor = None) -> torch.Tensor:
+    """vdqn_aug_draw_zoom on the current stream -> int32 [n][4] {ax, ay, bx, by} (Q16, 65536 = 1.0) of samples first .. first + n of
+    the global batch; jz is the Q16 width (`jz`)."""
+    dev = torch.device(device) if out is None else out.device
+    with torch.cuda.device(dev):
+        if out is None:
+            out = torch.empty((n, 4), dtype=torch.int32, device=dev)
+        _lib.check(_lib.load().vdqn_aug_draw_zoom(_u64(seed), _u64(step), global_batch, first, n, jz, int(bool(aspect)), out.data_ptr(),
+                                                  torch.cuda.current_stream().cuda_stream), "vdqn_aug_draw_zoom")
+    return out
+
+
 def pack_input_aug(src: torch.Tensor, params: torch.Tensor, frames_per_sample: int, dtype: torch.dtype,
-                   color: torch.Tensor = None) -> torch.Tensor:
-    """uint8 NHWC [n][224][224][3] frames + int32 [*][4] params (+ int32 [*][4] colour factors, as many rows as params) -> the
-    augmented stem operand [n][115][115][16]."""
+                   color: torch.Tensor = None, zoom: torch.Tensor = None) -> torch.Tensor:
+    """uint8 NHWC [n][224][224][3] frames + int32 [*][4] params (+ int32 [*][4] colour factors and / or zoom rows, each as many rows as
+    params) -> the augmented stem operand [n][115][115][16]."""
     if src.dtype != torch.uint8 or not src.is_contiguous() or params.dtype != torch.int32 or not params.is_contiguous():
         raise _lib.VdqnError("pack_input_aug: src must be contiguous uint8 NHWC frames and params contiguous int32 [*][4]")
     if color is not None and (color.dtype != torch.int32 or not color.is_contiguous() or color.numel() != params.numel()
                               or color.device != params.device):
         raise _lib.VdqnError("pack_input_aug: color must be contiguous int32 [*][4] with as many rows as params, on their device")
+    if zoom is not None and (zoom.dtype != torch.int32 or not zoom.is_contiguous() or zoom.numel() != params.numel()
+                             or zoom.device != params.device):
+        raise _lib.VdqnError("pack_input_aug: zoom must be contiguous int32 [*][4] with as many rows as params, on their device")
     n_img = src.numel() // (224 * 224 * 3)
     with torch.cuda.device(src.device):
         dst = torch.empty((n_img, 115, 115, 16), dtype=dtype, device=src.device)
         code = _lib.VDQN_BF16 if dtype == torch.bfloat16 else _lib.VDQN_F32
         st = torch.cuda.current_stream().cuda_stream
-        if color is not None:
+        if zoom is not None:
+            _lib.check(_lib.load().vdqn_pack_input_aug_zoom(src.data_ptr(), dst.data_ptr(), n_img, frames_per_sample, params.data_ptr(),
+                                                            None if color is None else color.data_ptr(), zoom.data_ptr(),
+                                                            params.numel() // 4, code, st), "vdqn_pack_input_aug_zoom")
+        elif color is not None:
             _lib.check(_lib.load().vdqn_pack_input_aug_color(src.data_ptr(), dst.data_ptr(), n_img, frames_per_sample, params.data_ptr(),
                                                              color.data_ptr(), params.numel() // 4, code, st), "vdqn_pack_input_aug_color")
         else:
@@ -103,11 +144,13 @@ def pack_input_aug(src: torch.Tensor, params: torch.Tensor, frames_per_sample: i
 class Augmenter:
     """The per-update draw of one rank: ``draw(step)`` -> this rank's int32 [B][4] on the device (valid until the next call),
     ``actions(act)`` -> the action labels with ``flip_actions`` exchanged for the mirrored samples of that draw.  With a colour
-    half-width above 0, ``draw`` also fills ``color`` (int32 [B][4] {f_b, f_c, f_s, 0}; None when all three are 0)."""
+    half-width above 0, ``draw`` also fills ``color`` (int32 [B][4] {f_b, f_c, f_s, 0}; None when all three are 0), and with ``zoom``
+    above 0 ``zoom`` (int32 [B][4] {ax, ay, bx, by}; None when off)."""
 
     def __init__(self, batch: int, device, pad: int = 0, flip: bool = False, flip_actions=(1, 2), seed: int = 0, rank: int = 0,
-                 world_size: int = 1, brightness: float = 0.0, contrast: float = 0.0, saturation: float = 0.0):
-        check_config(pad, flip, flip_actions, brightness, contrast, saturation)
+                 world_size: int = 1, brightness: float = 0.0, contrast: float = 0.0, saturation: float = 0.0,
+                 zoom: float = 0.0, zoom_aspect: bool = False):
+        check_config(pad, flip, flip_actions, brightness, contrast, saturation, zoom, zoom_aspect)
         self.lib = _lib.load()
         self.B, self.rank, self.world = int(batch), int(rank), int(world_size)
         self.G = self.B * self.world
@@ -118,13 +161,18 @@ class Augmenter:
             self._act = torch.zeros(self.B, dtype=torch.int64, device=self.device)
             self.jq = (jq(brightness), jq(contrast), jq(saturation))
             self.color = torch.empty((self.B, 4), dtype=torch.int32, device=self.device) if any(self.jq) else None
-        self.last_step = None  # the update number of the draw `params` (and `color`) hold
+            self.jz, self.zoom_aspect = jz(zoom), bool(zoom_aspect)
+            self.zoom = torch.empty((self.B, 4), dtype=torch.int32, device=self.device) if self.jz else None
+        self.last_step = None  # the update number of the draw `params` (and `color`, `zoom`) hold
 
     def draw(self, step: int) -> torch.Tensor:
-        if self.pad > 0 or self.flip or self.color is None:  # (colour alone: `params` stays the zeros vdqn_aug_draw gives for pad 0)
+        # (colour or zoom alone: `params` stays the zeros vdqn_aug_draw gives for pad 0)
+        if self.pad > 0 or self.flip or (self.color is None and self.zoom is None):
             aug_draw(self.seed, step, self.G, self.rank * self.B, self.B, self.pad, self.flip, out=self.params)
         if self.color is not None:
             aug_draw_color(self.seed, step, self.G, self.rank * self.B, self.B, *self.jq, out=self.color)
+        if self.zoom is not None:
+            aug_draw_zoom(self.seed, step, self.G, self.rank * self.B, self.B, self.jz, self.zoom_aspect, out=self.zoom)
         self.last_step = int(step)
         return self.params
 

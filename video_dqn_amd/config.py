@@ -30,7 +30,11 @@ and turn right; from dataloaders/gibson.py:76 and habitat_test_env.py:242 under 
 RIGHT 3, unverified here, hence a key), AUG_BRIGHTNESS, AUG_CONTRAST, AUG_SATURATION (0.0 = off, each in [0, 1]: colour jitter — the
 half-width J of a uniform factor range [1 - J, 1 + J] as torchvision's ColorJitter; one factor triple per update and sample, shared by
 its frames and by s and s', applied to the uint8 pixels in integer arithmetic, saturation then brightness then contrast about
-mid-grey 128, inside the same input pack on the GPU), GRAD_CLIP_NORM (0.0 = off; > 0: the whole gradient is rescaled so that its global L2 norm
+mid-grey 128, inside the same input pack on the GPU), AUG_ZOOM (0.0 = off, in [0, 0.5]: random zoom — a window whose side is uniform in
+[1 - AUG_ZOOM, 1] of the frame's, at a uniform position inside the frame, resampled back to 224 x 224 with an integer bilinear filter
+inside the same input pack; a magnification of at most 2, never a zoom-out; one window per update and sample, shared by its frames
+and by s and s'), AUG_ZOOM_ASPECT (False: the window's two sides are drawn independently, each from [1 - AUG_ZOOM, 1], which also
+stretches the picture; needs AUG_ZOOM > 0), GRAD_CLIP_NORM (0.0 = off; > 0: the whole gradient is rescaled so that its global L2 norm
 is at most this, torch.nn.utils.clip_grad_norm_: coef = min(1, max_norm / (norm + 1e-6)), norm and coefficient computed on the GPU
 and never read back for the update), WEIGHT_DECAY (0.0: decoupled, as torch.optim.AdamW: p <- p * (1 - lr * wd) in front of the
 Adam update, over every trainable element; resnet.fc, which never receives a gradient, stays untouched), LR_WARMUP_STEPS (0:
@@ -198,6 +202,8 @@ def get_cfg_defaults() -> CfgNode:
     c.AUG_BRIGHTNESS = 0.0        # colour jitter: brightness factor uniform in [1 - AUG_BRIGHTNESS, 1 + AUG_BRIGHTNESS] (0 = off, <= 1)
     c.AUG_CONTRAST = 0.0          # contrast factor about mid-grey 128, uniform in [1 - AUG_CONTRAST, 1 + AUG_CONTRAST] (0 = off, <= 1)
     c.AUG_SATURATION = 0.0        # saturation factor, uniform in [1 - AUG_SATURATION, 1 + AUG_SATURATION] (0 = off, <= 1)
+    c.AUG_ZOOM = 0.0              # random zoom: the window's side is uniform in [1 - AUG_ZOOM, 1] of the frame's, resampled to 224 (0 = off, <= 0.5)
+    c.AUG_ZOOM_ASPECT = False     # draw the window's two sides independently (a stretch); needs AUG_ZOOM > 0
     c.GRAD_CLIP_NORM = 0.0        # > 0: rescale the gradient to this global L2 norm at most (clip_grad_norm_, on the GPU); 0 = off
     c.WEIGHT_DECAY = 0.0          # decoupled weight decay (AdamW): p <- p * (1 - lr * WEIGHT_DECAY) in front of the Adam update
     c.LR_WARMUP_STEPS = 0         # the learning rate of update t is multiplied by min(1, t / LR_WARMUP_STEPS)

@@ -37,6 +37,30 @@
 // brightness then contrast, is a byte -> byte map bc(t) that folds into the per-block normalisation table, lut[c][t] = norm_c(bc(t)),
 // so only saturation costs per-pixel work.  The shift / mirror remap only picks the source pixel: the two compose in either order.
 // The kernel clamps every factor to [0, 512] first: no int32 value overflows a product or indexes outside a table; word 3 is ignored.
+//
+// Random zoom (a change of focal length: a window of [1 - J, 1] of the frame's side, resampled back to 224 x 224; never a zoom-out),
+// bilinear with Q16 coordinates and Q8 weights in integer arithmetic, so the operand is still EXACTLY vdqn_pack_input of host-augmented
+// frames (tests/aug_zoom_oracle.py restates it in numpy).  One int32 {ax, ay, bx, by} per update and per SAMPLE, shared by its F frames
+// and by s and s': ax, ay the Q16 source step per output pixel (65536 = 1.0), bx, by the Q16 source coordinate of output pixel 0.
+// ">>" is arithmetic.
+// Draw of sample j of the global batch G at update `step`, Jz = int(J * 65536 + 0.5) in 0 .. 32768:
+//   key = splitmix64(seed ^ 0x4155475A4F4F4D31)           "AUGZOOM1": a stream of its own, the shift / mirror / colour draws do not move
+//   h   = splitmix64(key ^ (step * G + j));   h_k = (h >> 16 k) & 0xFFFF
+//   ax  = 65536 - ((h_0 * (Jz + 1)) >> 16)                                in [65536 - Jz, 65536]
+//   ay  = aspect ? 65536 - ((h_1 * (Jz + 1)) >> 16) : ax
+//   origin(a, hk):  R = (224 * 65536 - 224 * a) >> 8                      the free range of the window's edge, in 1/256 pixel
+//                   o = ((hk * (R + 1)) >> 16) << 8                       the window's edge, Q16, uniform over where it fits
+//                   b = o + (a >> 1) - 32768                              pixel centres: output centre X + 1/2 maps to o + (X + 1/2) a
+//   bx = origin(ax, h_2);  by = origin(ay, h_3);   zoom[j] = int32 {ax, ay, bx, by};   Jz = 0 gives {65536, 65536, 0, 0}, the identity
+// Resample of one frame Z into the output pixel (Y, X), per channel:
+//   u = bx + X * ax;  x0 = u >> 16;  wx = (u >> 8) & 255;     v = by + Y * ay;  y0 = v >> 16;  wy = (v >> 8) & 255
+//   xa = clamp(x0, 0, 223), xb = clamp(x0 + 1, 0, 223), ya, yb likewise
+//   top = Z[ya][xa] * (256 - wx) + Z[ya][xb] * wx;   bot = the same on row yb
+//   out = (top * (256 - wy) + bot * wy + 32768) >> 16         (at most 255 * 65536 + 32768: fits int32; 0 .. 255)
+// Z is the frame after shift and mirror, Z[y][x] = in[clamp(y + sy)][mirror(clamp(x + sx))]: the remap above applied to each tap.
+// Colour jitter works on the resampled bytes: operand = pack(color(zoom(shift_mirror(frames)))).
+// The kernel clamps ax, ay to [0, 65536] and bx, by to +-224 * 65536 first: |u|, |v| < 2^25, and every tap is clamped into the frame,
+// whatever int32 the row holds.  A step of at most 1.0 is also what bounds the rows a pair of packed rows needs (below).
 #include "common.h"
 
 namespace {
@@ -46,6 +70,10 @@ constexpr uint64_t kColorStream = 0x415547434F4C5231ull;
 constexpr int kMaxPad = 32;
 constexpr int kMaxJq = 256;      // Q8 half-width of a colour factor: J in [0, 1]
 constexpr int kMaxFactor = 512;  // 256 + kMaxJq
+constexpr uint64_t kZoomStream = 0x4155475A4F4F4D31ull;
+constexpr int kMaxJz = 32768;              // Q16 width of the zoom's side range: J in [0, 0.5]
+constexpr int kZoomOne = 65536;            // Q16 1.0: the largest source step (no zoom-out)
+constexpr int kZoomMaxOrigin = 224 << 16;  // |bx|, |by| beyond it already select an edge pixel everywhere
 
 __host__ __device__ inline uint64_t splitmix64(uint64_t x) {
   uint64_t z = x + 0x9E3779B97F4A7C15ull;
@@ -78,6 +106,24 @@ __global__ __launch_bounds__(256) void aug_draw_color_kernel(uint64_t seed, uint
   const int fc = 256 - jc + (int)((((uint32_t)(h >> 16) & 0xFFFFu) * (2u * (uint32_t)jc + 1u)) >> 16);
   const int fs = 256 - js + (int)((((uint32_t)(h >> 32) & 0xFFFFu) * (2u * (uint32_t)js + 1u)) >> 16);
   color[i] = make_int4(fb, fc, fs, 0);
+}
+
+// ---- aug_draw_zoom: one thread per sample -------------------------------------------------------------------------------------
+__device__ __forceinline__ int zoom_origin(int a, uint32_t hk) {
+  const uint32_t R = (uint32_t)(224 * kZoomOne - 224 * a) >> 8;  // 0 .. 28672 for a in [32768, 65536]: hk * (R + 1) < 2^31
+  return (int)(((hk * (R + 1u)) >> 16) << 8) + (a >> 1) - 32768;
+}
+
+__global__ __launch_bounds__(256) void aug_draw_zoom_kernel(uint64_t seed, uint64_t step, int G, int first, int n, int jz, int aspect,
+                                                            int4* __restrict__ zoom) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const uint64_t key = splitmix64(seed ^ kZoomStream);
+  const uint64_t h = splitmix64(key ^ (step * (uint64_t)G + (uint64_t)(first + i)));
+  const uint32_t span = (uint32_t)jz + 1u;  // <= 32769: a 16-bit draw times it stays below 2^31
+  const int ax = kZoomOne - (int)((((uint32_t)h & 0xFFFFu) * span) >> 16);
+  const int ay = aspect ? kZoomOne - (int)((((uint32_t)(h >> 16) & 0xFFFFu) * span) >> 16) : ax;
+  zoom[i] = make_int4(ax, ay, zoom_origin(ax, (uint32_t)(h >> 32) & 0xFFFFu), zoom_origin(ay, (uint32_t)(h >> 48) & 0xFFFFu));
 }
 
 // ---- aug_swap_actions: a0 <-> a1 for the flipped samples, a copy otherwise -------------------------------------------------------
@@ -190,6 +236,122 @@ __global__ __launch_bounds__(256) void pack_input_aug_kernel(const uint8_t* __re
   }
 }
 
+// ---- pack_input_zoom: pack_input_aug_kernel with four taps per output pixel ----------------------------------------------------------
+// The same grid and the same walk over pairs of packed rows; a kernel of its own, so the four instances above keep their registers.
+// A pair's output rows Y0 .. Y0 + 3 read the tap rows ya(Y0) .. yb(Y0 + 3) of Z.  The step ay is at most 1.0, so y0(Y0 + 3) <=
+// y0(Y0) + 3 and the taps span at most y0(Y0) .. y0(Y0) + 4; the clamp into the frame and the shift clamp are non-decreasing and
+// move neighbours by at most 1, so the DISTINCT source rows are at most five consecutive ones, first .. last, staged once per pair as
+// 42 16-byte vectors each.  A tap reads slot clamp(y + sy) - first, which lies in 0 .. last - first for every row of the pair.
+// A thread's four x-tap byte offsets and two wx do not depend on the pair: computed once per block, as o0 / o1 above.
+struct ZoomRow {
+  int ax, ay, bx, by;
+};
+__device__ __forceinline__ ZoomRow zoom_clamped(const int4 z) {
+  return {min(max(z.x, 0), kZoomOne), min(max(z.y, 0), kZoomOne), min(max(z.z, -kZoomMaxOrigin), kZoomMaxOrigin),
+          min(max(z.w, -kZoomMaxOrigin), kZoomMaxOrigin)};
+}
+
+template <typename T, bool COLOR>
+__global__ __launch_bounds__(256) void pack_input_zoom_kernel(const uint8_t* __restrict__ src, T* __restrict__ dst, int frames_per_sample,
+                                                              const int4* __restrict__ params, const int4* __restrict__ color,
+                                                              const int4* __restrict__ zoom, int n_params) {
+  __shared__ uint4 rows[5][42];
+  __shared__ T lut[3][256];
+  const int n = blockIdx.y;
+  const int tid = threadIdx.x;
+  const int row = (n / frames_per_sample) % n_params;
+  int fs = 256;  // the saturation factor (COLOR only)
+  {
+    const float mean[3] = {0.485f, 0.456f, 0.406f};
+    const float stdv[3] = {0.229f, 0.224f, 0.225f};
+    int t = tid;
+    if constexpr (COLOR) {
+      const int4 f = color[row];
+      const int fb = min(max(f.x, 0), kMaxFactor), fc = min(max(f.y, 0), kMaxFactor);
+      fs = min(max(f.z, 0), kMaxFactor);
+      t = min(255, (t * fb + 128) >> 8);                  // brightness
+      t = clamp255(128 + (((t - 128) * fc + 128) >> 8));  // contrast about mid-grey
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) lut[c][tid] = from_f32<T>((((float)t / 255.0f) - mean[c]) / stdv[c]);
+  }
+  const int4 p = params[row];
+  const int sx = min(max(p.x, -224), 224), sy = min(max(p.y, -224), 224);
+  const bool flip = p.z != 0;
+  const ZoomRow z = zoom_clamped(zoom[row]);
+  const int yy = tid / 115, x = tid - yy * 115;
+  // this thread's two output pixels X = 2 xs, 2 xs + 1: byte offsets of their taps xa, xb inside a staged row, and their weights
+  int oa[2], ob[2], wx[2];
+#pragma unroll
+  for (int k = 0; k < 2; ++k) {
+    const int u = z.bx + (2 * (x - 2) + k) * z.ax;
+    const int x0 = u >> 16;
+    int Xa = clamp223(clamp223(x0) + sx), Xb = clamp223(clamp223(x0 + 1) + sx);
+    if (flip) {
+      Xa = 223 - Xa;
+      Xb = 223 - Xb;
+    }
+    oa[k] = 3 * Xa;
+    ob[k] = 3 * Xb;
+    wx[k] = (u >> 8) & 255;
+  }
+  for (int pr = 0; pr < kPackPairs; ++pr) {
+    const int y0 = 2 * ((int)blockIdx.x * kPackPairs + pr);  // packed rows y0, y0 + 1 -> output rows 2 (y0 - 2) .. + 3
+    if (y0 >= 115) break;
+    const int Y0 = 2 * (y0 - 2);
+    const bool inside = (unsigned)Y0 < 224u;
+    // source rows of the pair's first and last tap row (Y0 in -4 .. 228: no overflow whether inside or not)
+    const int first = clamp223(clamp223((z.by + Y0 * z.ay) >> 16) + sy);
+    const int last = clamp223(clamp223(((z.by + (Y0 + 3) * z.ay) >> 16) + 1) + sy);
+    __syncthreads();  // the previous pair's readers are done (first pass: the table is written)
+    if (tid < 210 && inside) {
+      const int s = tid / 42, c = tid - s * 42;
+      if (first + s <= last) rows[s][c] = reinterpret_cast<const uint4*>(src + ((size_t)n * 224 + (first + s)) * 672)[c];
+    }
+    __syncthreads();
+    const int y = y0 + yy;
+    if (tid >= 230 || y >= 115) continue;
+    const int ys = y - 2, xs = x - 2;
+    __attribute__((aligned(16))) T v[16];
+#pragma unroll
+    for (int e = 0; e < 16; ++e) v[e] = from_f32<T>(0.f);
+    if (inside && (unsigned)ys < 112u && (unsigned)xs < 112u) {
+#pragma unroll
+      for (int r = 0; r < 2; ++r) {
+        const int vq = z.by + (Y0 + 2 * yy + r) * z.ay;
+        const int yq = vq >> 16, wy = (vq >> 8) & 255;
+        // LDS slots, 0 .. last - first <= 4 by the argument above; the clamp keeps a slot inside `rows` whatever happens
+        const int sa = min(max(clamp223(clamp223(yq) + sy) - first, 0), 4), sb = min(max(clamp223(clamp223(yq + 1) + sy) - first, 0), 4);
+        const uint8_t* ra = reinterpret_cast<const uint8_t*>(rows[sa]);
+        const uint8_t* rb = reinterpret_cast<const uint8_t*>(rows[sb]);
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+          int px[3];
+#pragma unroll
+          for (int c = 0; c < 3; ++c) {
+            const int top = ra[oa[k] + c] * (256 - wx[k]) + ra[ob[k] + c] * wx[k];
+            const int bot = rb[oa[k] + c] * (256 - wx[k]) + rb[ob[k] + c] * wx[k];
+            px[c] = (top * (256 - wy) + bot * wy + 32768) >> 16;
+          }
+          T* o = v + 3 * (2 * r + k);
+          if constexpr (COLOR) {
+            const int g = (77 * px[0] + 150 * px[1] + 29 * px[2] + 128) >> 8;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) o[c] = lut[c][clamp255(g + (((px[c] - g) * fs + 128) >> 8))];
+          } else {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) o[c] = lut[c][px[c]];
+          }
+        }
+      }
+    }
+    T* d = dst + ((size_t)n * 115 * 115 + (size_t)y * 115 + x) * 16;
+    constexpr int V16 = (int)(16 * sizeof(T) / 16);
+#pragma unroll
+    for (int q = 0; q < V16; ++q) reinterpret_cast<uint4*>(d)[q] = reinterpret_cast<const uint4*>(v)[q];
+  }
+}
+
 }  // namespace
 
 extern "C" int vdqn_aug_draw(uint64_t seed, uint64_t step, int32_t global_batch, int32_t first, int32_t n, int32_t pad, int32_t flip,
@@ -272,6 +434,46 @@ extern "C" int vdqn_pack_input_aug_color(const void* src, void* dst, int32_t n_i
   else
     hipLaunchKernelGGL((pack_input_aug_kernel<float, true>), grid, dim3(256), 0, (hipStream_t)stream, (const uint8_t*)src, (float*)dst,
                        (int)frames_per_sample, (const int4*)params, (const int4*)color, (int)n_params);
+  VDQN_LAUNCH_CHECK();
+  return VDQN_OK;
+}
+
+extern "C" int vdqn_aug_draw_zoom(uint64_t seed, uint64_t step, int32_t global_batch, int32_t first, int32_t n, int32_t jz, int32_t aspect,
+                                  int32_t* zoom, void* stream) {
+  VDQN_CHECK(zoom, "vdqn_aug_draw_zoom: null zoom");
+  VDQN_CHECK(n > 0, "vdqn_aug_draw_zoom: n = %d", n);
+  VDQN_CHECK(global_batch >= 1 && first >= 0 && (int64_t)first + n <= (int64_t)global_batch,
+             "vdqn_aug_draw_zoom: samples %d .. %lld outside the global batch of %d", first, (long long)first + n, global_batch);
+  VDQN_CHECK(jz >= 0 && jz <= kMaxJz, "vdqn_aug_draw_zoom: width %d outside [0, %d] (Q16: int(J * 65536 + 0.5), J in [0, 0.5])", jz, kMaxJz);
+  VDQN_CHECK(((uintptr_t)zoom & 15) == 0, "vdqn_aug_draw_zoom: zoom must be 16-byte aligned");
+  ProfScope ps_("aug_draw_zoom", 0.0, (double)n * 16.0, (hipStream_t)stream);
+  hipLaunchKernelGGL(aug_draw_zoom_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, seed, step, (int)global_batch, (int)first,
+                     (int)n, (int)jz, (int)(aspect != 0), (int4*)zoom);
+  VDQN_LAUNCH_CHECK();
+  return VDQN_OK;
+}
+
+extern "C" int vdqn_pack_input_aug_zoom(const void* src, void* dst, int32_t n_img, int32_t frames_per_sample, const int32_t* params,
+                                        const int32_t* color, const int32_t* zoom, int32_t n_params, int32_t dtype, void* stream) {
+  VDQN_CHECK(src && dst && params && zoom, "vdqn_pack_input_aug_zoom: null arg");
+  VDQN_CHECK(n_img > 0 && frames_per_sample > 0 && n_params > 0, "vdqn_pack_input_aug_zoom: n_img %d, frames_per_sample %d, n_params %d must be > 0",
+             n_img, frames_per_sample, n_params);
+  VDQN_CHECK(dtype == VDQN_F32 || dtype == VDQN_BF16, "vdqn_pack_input_aug_zoom: bad dtype");
+  VDQN_CHECK((((uintptr_t)src | (uintptr_t)dst | (uintptr_t)params | (uintptr_t)color | (uintptr_t)zoom) & 15) == 0,
+             "vdqn_pack_input_aug_zoom: src, dst, params, color and zoom must be 16-byte aligned");
+  ProfScope ps_("pack_input_aug_zoom", 0.0, (double)n_img * (224.0 * 224 * 3 + 115.0 * 115 * 16 * (dtype == VDQN_BF16 ? 2 : 4)), (hipStream_t)stream);
+  const dim3 grid((58 + kPackPairs - 1) / kPackPairs, n_img);
+  const hipStream_t st = (hipStream_t)stream;
+  const uint8_t* s = (const uint8_t*)src;
+  const int F = (int)frames_per_sample, np = (int)n_params;
+  const int4 *p = (const int4*)params, *c = (const int4*)color, *z = (const int4*)zoom;
+  if (dtype == VDQN_BF16) {
+    if (c) hipLaunchKernelGGL((pack_input_zoom_kernel<bf16raw, true>), grid, dim3(256), 0, st, s, (bf16raw*)dst, F, p, c, z, np);
+    else hipLaunchKernelGGL((pack_input_zoom_kernel<bf16raw, false>), grid, dim3(256), 0, st, s, (bf16raw*)dst, F, p, c, z, np);
+  } else {
+    if (c) hipLaunchKernelGGL((pack_input_zoom_kernel<float, true>), grid, dim3(256), 0, st, s, (float*)dst, F, p, c, z, np);
+    else hipLaunchKernelGGL((pack_input_zoom_kernel<float, false>), grid, dim3(256), 0, st, s, (float*)dst, F, p, c, z, np);
+  }
   VDQN_LAUNCH_CHECK();
   return VDQN_OK;
 }

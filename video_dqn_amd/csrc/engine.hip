@@ -365,7 +365,10 @@ static int pack_step_frames(const vdqn_net* net, const vdqn_step_args* a, unsign
   const int F = net->cfg.num_frames, dt = net->cfg.dtype;
   const bool gtb = a->train_on_ground_truth != 0;
   unsigned char* dst_after = dst + (int64_t)B * F * frame_bytes(net);
-  if (a->aug_color) {  // the same [B][4] shift / mirror and colour factors for s and s'
+  if (a->aug_zoom) {  // the same [B][4] shift / mirror, zoom window and (NULL: none) colour factors for s and s'
+    RC(vdqn_pack_input_aug_zoom(a->before, dst, B * F, F, a->aug_params, a->aug_color, a->aug_zoom, B, dt, st));
+    if (!gtb) RC(vdqn_pack_input_aug_zoom(a->after, dst_after, B * F, F, a->aug_params, a->aug_color, a->aug_zoom, B, dt, st));
+  } else if (a->aug_color) {  // the same [B][4] shift / mirror and colour factors for s and s'
     RC(vdqn_pack_input_aug_color(a->before, dst, B * F, F, a->aug_params, a->aug_color, B, dt, st));
     if (!gtb) RC(vdqn_pack_input_aug_color(a->after, dst_after, B * F, F, a->aug_params, a->aug_color, B, dt, st));
   } else if (a->aug_params) {  // the same [B][4] shift / mirror for s and s'
@@ -412,6 +415,8 @@ static int td_forward_impl(vdqn_net* net, const vdqn_step_args* a, float cql_alp
   VDQN_CHECK(!a->aug_params || !a->packed_frames, "vdqn_net_td_forward: aug_params are given, but packed_frames were packed without them");
   VDQN_CHECK(!a->aug_color || a->aug_params, "vdqn_net_td_forward: aug_color is given without aug_params (all-zero params are the plain geometry)");
   VDQN_CHECK(((uintptr_t)a->aug_color & 15) == 0, "vdqn_net_td_forward: aug_color must be 16-byte aligned");
+  VDQN_CHECK(!a->aug_zoom || a->aug_params, "vdqn_net_td_forward: aug_zoom is given without aug_params (all-zero params are the plain geometry)");
+  VDQN_CHECK(((uintptr_t)a->aug_zoom & 15) == 0, "vdqn_net_td_forward: aug_zoom must be 16-byte aligned");
   VDQN_CHECK(!a->sample_gamma || !gtb, "vdqn_net_td_forward: sample_gamma is given, but the ground-truth branch bootstraps nothing (train_on_ground_truth)");
   VDQN_CHECK(!a->sample_gamma || !a->linear, "vdqn_net_td_forward: sample_gamma is given with linear: y = r + (Qa - 0.1) has no discount and no n-step form");
   hipStream_t st = (hipStream_t)stream;
@@ -526,6 +531,7 @@ extern "C" int vdqn_net_td_eval(vdqn_net* net, const vdqn_step_args* a, double* 
   VDQN_CHECK(!a->sample_err, "vdqn_net_td_eval: sample_err is given: the metrics launch writes no per-sample errors");
   VDQN_CHECK(!a->aug_params, "vdqn_net_td_eval: aug_params are given: validation frames are not augmented");
   VDQN_CHECK(!a->aug_color, "vdqn_net_td_eval: aug_color is given: validation frames are not augmented");
+  VDQN_CHECK(!a->aug_zoom, "vdqn_net_td_eval: aug_zoom is given: validation frames are not augmented");
   VDQN_CHECK(!a->packed_frames, "vdqn_net_td_eval: packed_frames are given: the validation pass packs its own frames");
   VDQN_CHECK(!a->sample_gamma, "vdqn_net_td_eval: sample_gamma is given: validation is one-step (the scalar gamma), whatever the training target");
   VDQN_CHECK(a->acts_samples == 0, "vdqn_net_td_eval: acts_samples %d must be 0", a->acts_samples);

@@ -425,7 +425,7 @@ class TDStepper:
             self.net.pack_weights(self.packed_target, with_dgrad=False)
 
     def _args(self, before, after, src_kind, act, rew, term, valid, gt, weights=None, td_error=None, augment=None,
-              discount=None, augment_color=None) -> _lib.StepArgs:
+              discount=None, augment_color=None, augment_zoom=None) -> _lib.StepArgs:
         n = self.net
         a = _lib.StepArgs()
         a.params, a.bnstats = _ptr(n.params), _ptr(n.bnstats)
@@ -441,7 +441,7 @@ class TDStepper:
         a.loss_kind = LOSS_KINDS[self.loss_kind]
         a.packed_frames = None
         a.sample_weight, a.sample_err, a.aug_params = _ptr(weights), _ptr(td_error), _ptr(augment)
-        a.aug_color = _ptr(augment_color)
+        a.aug_color, a.aug_zoom = _ptr(augment_color), _ptr(augment_zoom)
         a.sample_gamma = _ptr(discount)
         return a
 
@@ -499,7 +499,8 @@ class TDStepper:
         self._ahead = (self._frames_key(nb, na, nk), slot, (nb, na))  # (the tensors are kept alive until they are consumed)
 
     def forward_backward(self, before, after, src_kind, act, rew, term, valid=None, gt=None, early_adam: bool = False, next_frames=None,
-                         *, weights=None, td_error=None, augment=None, discount=None, augment_color=None, mc_return=None):
+                         *, weights=None, td_error=None, augment=None, discount=None, augment_color=None, mc_return=None,
+                         augment_zoom=None):
         """Everything of one update up to (and including) the gradient all-reduce; no optimiser step.
 
         early_adam (only `step` passes it: single process, no exchange, eval-mode BatchNorm): the optimiser update of stage 0 and stage 1 is
@@ -507,15 +508,15 @@ class TDStepper:
         weight gradients instead of behind them (nothing later in the update reads those master parameters: the kernels work on
         the packed copies); `optimizer_step` then only covers what is left.  Same arithmetic, same results.
 
-        weights, td_error, augment, discount, augment_color: as `step` describes and validates them (vdqn_step_args.sample_weight /
-        sample_err / aug_params / sample_gamma / aug_color); mc_return: vdqn_net_td_forward_mc's plain argument."""
+        weights, td_error, augment, discount, augment_color, augment_zoom: as `step` describes and validates them (vdqn_step_args.
+        sample_weight / sample_err / aug_params / sample_gamma / aug_color / aug_zoom); mc_return: vdqn_net_td_forward_mc's plain argument."""
         n = self.net
         self._adam_done = []
         self._clip_slots = 0
-        keep = (before, after, act, rew, term, valid, gt, weights, td_error, augment, discount, augment_color, mc_return)  # keep inputs alive until the launches are queued
+        keep = (before, after, act, rew, term, valid, gt, weights, td_error, augment, discount, augment_color, mc_return, augment_zoom)  # keep inputs alive until the launches are queued
         with torch.cuda.device(n.device):
             a = self._args(before, after, src_kind, act, rew, term, valid if valid is not None else self._ones, gt, weights, td_error, augment,
-                           discount, augment_color)
+                           discount, augment_color, augment_zoom)
             st = _stream()
             ahead, self._ahead = self._ahead, None
             slot = None
@@ -706,7 +707,8 @@ class TDStepper:
                                  f"{''.join(f'[{d}]' for d in shape)} device tensor")
 
     def step(self, before, after, src_kind, act, rew, term, valid=None, gt=None, finish_allreduce=None, next_frames=None,
-             weights=None, td_error=None, augment=None, discount=None, augment_color=None, mc_return=None) -> torch.Tensor:
+             weights=None, td_error=None, augment=None, discount=None, augment_color=None, mc_return=None,
+             augment_zoom=None) -> torch.Tensor:
         """One iteration of the reference loop body (train_q_network.py:213-227).  Returns the device loss scalar
         (no host sync).
 
@@ -737,6 +739,11 @@ class TDStepper:
         saturation (256 = 1.0) — the frames go through vdqn_pack_input_aug_color with them and with `augment`, which must be given
         as well (zeros = no shift); the same for `before` and `after` (vdqn_step_args.aug_color, this update only).
 
+        augment_zoom (video_dqn_amd/augment.py): int32 [B][4] {ax, ay, bx, by} on the device, the Q16 source step and origin of each
+        sample's zoom window (65536, 65536, 0, 0 = the whole frame) — the frames go through vdqn_pack_input_aug_zoom with them, with
+        `augment`, which must be given as well (zeros = no shift), and with `augment_color` when that is given; the same for `before`
+        and `after` (vdqn_step_args.aug_zoom, this update only).
+
         mc_return (video_dqn_amd/mcreturn.py): f32 [B][num_classes] on the device, the Monte-Carlo return of every sampled row
         (ReturnTable.G at the sampled rows; with n-step returns still the sampled row's, the whole-episode return against the n-step
         target).  Required exactly when the stepper was built with mc_floor or cql_calibrated; this update only.  A table of -inf
@@ -749,6 +756,9 @@ class TDStepper:
         if augment_color is not None and augment is None:
             raise _lib.VdqnError("TDStepper.step: augment_color needs augment as well (int32 zeros [B][4] = no shift, no mirror)")
         self._check_input("augment_color", augment_color, torch.int32, (self.B, 4))
+        if augment_zoom is not None and augment is None:
+            raise _lib.VdqnError("TDStepper.step: augment_zoom needs augment as well (int32 zeros [B][4] = no shift, no mirror)")
+        self._check_input("augment_zoom", augment_zoom, torch.int32, (self.B, 4))
         if discount is not None and (self.gtb or self.linear):
             raise _lib.VdqnError("TDStepper.step: discount applies to the TD branch without LINEAR (TRAIN_ON_GROUND_TRUTH bootstraps "
                                  "nothing; y = r + (Qa - 0.1) has no discount)")
@@ -782,7 +792,7 @@ class TDStepper:
         # profiles/r03s_ab_rccl_early_adam.txt — with an exchange the whole optimiser update stays behind `finish_allreduce`)
         early = _EARLY_ADAM and self.net.extra_capacity and self.allreduce is None and finish_allreduce is None and self.grad_clip_norm == 0
         self.forward_backward(before, after, src_kind, act, rew, term, valid, gt, early_adam=early, next_frames=next_frames,
-                              weights=weights, td_error=td_error, augment=augment, discount=discount, augment_color=augment_color,
+                              weights=weights, td_error=td_error, augment=augment, discount=discount, augment_color=augment_color, augment_zoom=augment_zoom,
                               mc_return=mc_return)
         if finish_allreduce is not None:
             finish_allreduce()
