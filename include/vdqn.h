@@ -237,6 +237,24 @@ int vdqn_td_loss_mc(const vdqn_td_args* a, const float* weight /* NULL ok */, fl
                     float* penalty /* NULL ok */, const float* sample_gamma /* NULL = a->gamma */,
                     const float* mc_return /* f32 [batch][n_cat], required */, int32_t mc_flags, float* mc_stats /* f32[2], pre-zeroed, NULL ok */,
                     void* stream);
+/* Implicit Q-learning (IQL; Kostrikov et al., ICLR 2022) in one launch (video_dqn_amd/csrc/iql.hip): a row of ldq columns holds
+ * Q(c, a) at column c * n_act + a and a state value V(c) at column n_cat * n_act + c, so n_cat * n_act + n_cat <= ldq.  With
+ * a* = act[b], tau = expectile, w_b = weight[b] (NULL = 1), vm_bc = valid or 1 and gamma_b = sample_gamma[b] (NULL = a->gamma):
+ *   v  = q_before[b][V(c)]     v' = q_after_online[b][V(c)]     qt = q_after_target[b][Q(c, a*)]
+ *        (q_after_target is read as the TARGET network's Q(s), not Q(s'); no gradient flows through v' or qt)
+ *   u  = qt - v;  omega = u > 0 ? tau : 1 - tau;  L_V = omega u^2;  dL_V/dv = -2 omega u        (expectile regression of V on qt)
+ *   y  = rew + gamma_b * (v' * (1 - term)), rect clip as vdqn_td_loss;  d = q_before[b][Q(c, a*)] - y;  L_Q = l(d), dl(d) by loss_kind
+ *   loss += inv_count * sum w_b vm_bc (L_Q + L_V)
+ *   stats[0] += inv_count * sum w_b vm_bc L_V        stats[1] += inv_count * sum vm_bc u      (f32[2], pre-zeroed, NULL ok)
+ *   dq[b][Q(c, a*)] = dl(d) w_b vm_bc inv_count      dq[b][V(c)] = -2 omega u w_b vm_bc inv_count      every other column 0
+ *   err_out[b] = sum_c |d_bc| vm_bc / n_cat          (NULL ok; priorities follow the Q error)
+ * y is formed in vdqn_td_loss's expression order: with a q_after_target row whose actions all hold v', vdqn_td_loss_weighted
+ * writes the same bits into the taken-action columns of dq and into err_out.  `deterministic` sums in one block in a fixed order;
+ * q_copy and dq_f32 as in vdqn_td_loss.  Fails by name, before any launch, for a null required pointer, bad dims, columns that do
+ * not fit in ldq, linear != 0 and an expectile outside [0.5, 1). */
+int vdqn_td_loss_iql(const vdqn_td_args* a, const float* weight /* NULL = 1 */, float* err_out /* NULL ok */,
+                     const float* sample_gamma /* NULL = a->gamma */, float expectile, float* stats /* f32[2], pre-zeroed, NULL ok */,
+                     void* stream);
 /* Held-out validation metrics of the same loss, forward only: the `eval_losses` list the reference reserves and never fills
  * (train_q_network.py:183-186) and its `# checkpoint and eval` (:240).  One launch adds eight sums per category into
  * acc (device f64 [n_cat][8], 8-byte aligned, ACCUMULATED into: the caller zeroes it once per validation pass).  With d, y and l(d)
@@ -398,6 +416,16 @@ typedef struct vdqn_net_config {
 typedef struct vdqn_net vdqn_net;
 
 int vdqn_net_create(const vdqn_net_config* cfg, vdqn_net** out);
+/* vdqn_net_create with a state-value head behind the Q head (implicit Q-learning, vdqn_net_td_forward_iql).  value_head = 0 is
+ * vdqn_net_create: the same tables, offsets and bits.  value_head = 1: the Q layer (`top.4`, or `top` in 'basic') computes
+ * action_dim * num_classes + num_classes columns, Q(c, a) at c * action_dim + a and V(c) behind them; its extra rows are the
+ * parameters `value.weight` [num_classes, in] and `value.bias` [num_classes], registered directly behind `<top>.weight` and
+ * `<top>.bias` in the flat arrays (the layer's operand is one contiguous block) with param_ids after the reference's.  Every
+ * entry that reads Q (vdqn_net_forward, vdqn_net_td_forward*, vdqn_net_td_eval, vdqn_net_backward_begin) keeps reading the
+ * first action_dim * num_classes columns and leaves the V columns of dq at 0.  Needs action_dim >= 2 and
+ * action_dim * num_classes + num_classes <= 64; value_head outside {0, 1} fails. */
+int vdqn_net_create_v(const vdqn_net_config* cfg, int32_t value_head, vdqn_net** out);
+int vdqn_net_value_head(const vdqn_net* net); /* 1 when the net was created with the value head, else 0 */
 /* The engine runs weight gradients and the target-network forward on a second, internal HIP stream (joined back
  * into the caller's stream before their results are consumed).  on = 0 serialises everything on the caller's
  * stream (used for per-kernel roofline timing, where each kernel must have the chip to itself).  Default: on
@@ -552,6 +580,13 @@ int vdqn_net_td_forward_cql(vdqn_net* net, const vdqn_step_args* a, float cql_al
  * linear, mc_flags 0 or with unknown bits, and bit 1 with cql_alpha == 0. */
 int vdqn_net_td_forward_mc(vdqn_net* net, const vdqn_step_args* a, float cql_alpha, float* cql_penalty, const float* mc_return,
                            int32_t mc_flags, float* mc_stats, void* stream);
+/* vdqn_net_td_forward for implicit Q-learning on a net with the value head (vdqn_net_create_v): the same update with two
+ * differences.  The target pass runs over the `before` half of the packed frames (Q_target(s), where the others need Q_target(s')):
+ * the same 3 * batch forward samples.  The loss launch is vdqn_td_loss_iql on the online pass's Q(s), V(s), V(s') and the target's
+ * Q(s); iql_stats (device f32[2], NULL ok) is cleared beside `loss`.  sample_weight, sample_err, sample_gamma, aug_params,
+ * aug_color, aug_zoom, packed_frames and the engine's `deterministic` behave as in vdqn_net_td_forward.  Fails by name, before
+ * any launch, for a net without the value head, train_on_ground_truth, linear and an expectile outside [0.5, 1). */
+int vdqn_net_td_forward_iql(vdqn_net* net, const vdqn_step_args* a, float expectile, float* iql_stats, void* stream);
 /* One held-out batch of a validation pass (the reference's unfilled `eval_losses`, train_q_network.py:183-186, and `# checkpoint
  * and eval`, :240): the online network over [before; after] (2 * batch samples), the target network over after on the side stream,
  * then vdqn_td_eval on the two f32 Q tensors (ldq 64) into acc (device f64 [num_classes][8], accumulated into).  Forward only, both

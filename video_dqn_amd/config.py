@@ -69,7 +69,15 @@ mc_floor_share/train, the share of targets the floor raises, and q_minus_return/
 configurations as N_STEP > 1: the TD branch without LINEAR on a decoded-frame shard dataset held in full in HBM on every rank;
 nothing goes into checkpoints, validation is unchanged), CQL_CALIBRATED (False = off; True: calibrated conservative Q-learning,
 Cal-QL — the penalty's logsumexp runs over max(Q(s, a), G) with the same table G, so the penalty stops pushing values below what
-the data achieved; needs CQL_ALPHA > 0 and what MC_RETURN_FLOOR needs; logs the same two scalars).
+the data achieved; needs CQL_ALPHA > 0 and what MC_RETURN_FLOOR needs; logs the same two scalars), IQL_EXPECTILE (0.0 = off; in
+[0.5, 1): implicit Q-learning, Kostrikov et al. 2022 — the network gets a value head V(s), five more rows of its Q layer stored as
+value.weight / value.bias, fitted by expectile regression at IQL_EXPECTILE to the target network's Q(s, a_data), and Q(s, a_data) is
+regressed on r + GAMMA (1 - t) V(s') where Double DQN takes Q_target(s', argmax_a Q(s', .)): no action outside the logged data is
+evaluated; 0.7 is the usual setting, 0.5 fits the mean; the target pass runs over s instead of s', so an update costs what it did;
+logs iql_v_loss/train and iql_advantage/train, the mean of Q_target(s, a_data) - V(s); the TD branch with three action columns and
+without LINEAR; not together with CQL_ALPHA, CQL_CALIBRATED or MC_RETURN_FLOOR; composes with N_STEP, PRIORITIZED_REPLAY, AUG_*
+and TARGET_TAU; checkpoints keep the reference's keys and shapes and carry the head under a key of their own, `value_head`;
+validation is unchanged, the one-step Double-DQN metrics on the Q columns).
 """
 from __future__ import annotations
 
@@ -216,6 +224,7 @@ def get_cfg_defaults() -> CfgNode:
     c.VAL_BATCHES = 0             # > 0: only the first VAL_BATCHES batches of the validation set; 0 = the whole set
     c.MC_RETURN_FLOOR = False     # True: y <- max(y, G), G the Monte-Carlo return of the sampled row along its chain (a table built on the GPU at start)
     c.CQL_CALIBRATED = False      # True: Cal-QL — the CQL penalty's logsumexp over max(Q, G); needs CQL_ALPHA > 0
+    c.IQL_EXPECTILE = 0.0         # in [0.5, 1): implicit Q-learning — a value head fitted to Q_target(s, a_data) at this expectile, the bootstrap from V(s'); 0 = off
     c.N_STEP = 1                  # 2 .. 16: n-step returns along each sampled row's chain in the logged data, folded on the GPU; 1 = off
     return c
 

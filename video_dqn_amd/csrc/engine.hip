@@ -398,9 +398,12 @@ static vdqn_td_args fill_td_args(const vdqn_net* net, const vdqn_step_args* a, c
 }
 
 // vdqn_net_td_forward (cql_alpha == 0: the launches and bits it always had), vdqn_net_td_forward_cql (cql_alpha > 0) and
-// vdqn_net_td_forward_mc (mc_return != NULL: the loss launch is vdqn_td_loss_mc; NULL: nothing differs)
+// vdqn_net_td_forward_mc (mc_return != NULL: the loss launch is vdqn_td_loss_mc; NULL: nothing differs).  iql_expectile > 0
+// (vdqn_net_td_forward_iql alone, on a net with the value head): the target pass runs over the `before` half of the packed frames
+// and the loss launch is vdqn_td_loss_iql; 0: nothing differs.
 static int td_forward_impl(vdqn_net* net, const vdqn_step_args* a, float cql_alpha, float* cql_penalty, void* stream,
-                           const float* mc_return = nullptr, int32_t mc_flags = 0, float* mc_stats = nullptr) {
+                           const float* mc_return = nullptr, int32_t mc_flags = 0, float* mc_stats = nullptr, float iql_expectile = 0.f,
+                           float* iql_stats = nullptr) {
   VDQN_CHECK(net && a, "vdqn_net_td_forward: null arg");
   VDQN_CHECK(a->params && a->bnstats && a->packed_online && a->before && a->act && a->acts_online && a->bwd && a->loss, "vdqn_net_td_forward: null buffer");
   const int B = a->batch;
@@ -421,6 +424,7 @@ static int td_forward_impl(vdqn_net* net, const vdqn_step_args* a, float cql_alp
   VDQN_CHECK(!a->sample_gamma || !a->linear, "vdqn_net_td_forward: sample_gamma is given with linear: y = r + (Qa - 0.1) has no discount and no n-step form");
   hipStream_t st = (hipStream_t)stream;
   const int F = net->cfg.num_frames, dt = net->cfg.dtype;
+  const bool iql = iql_expectile > 0.f;
   const int ns_online = step_layout_samples(net, a);
   const ActLayout A = act_layout(net, ns_online);
   const BwdLayout W = bwd_layout(net, B);
@@ -440,7 +444,8 @@ static int td_forward_impl(vdqn_net* net, const vdqn_step_args* a, float cql_alp
   if (tst != st) join(net, net->side, st);  // packed input ready for the online pass
   if (!gtb) {
     const ActLayout T = act_layout(net, B);
-    RC(forward_impl(net, (const unsigned char*)a->packed_target, tin + (int64_t)B * F * frame_bytes(net), B, (unsigned char*)a->acts_target, T, tst, false, 0));  // (no backward: no arg-max bytes)
+    const unsigned char* tin_target = iql ? tin : tin + (int64_t)B * F * frame_bytes(net);  // implicit Q-learning: Q_target(s), not Q_target(s')
+    RC(forward_impl(net, (const unsigned char*)a->packed_target, tin_target, B, (unsigned char*)a->acts_target, T, tst, false, 0));  // (no backward: no arg-max bytes)
   }
   if (net->basic())  // two model calls (before, after), each with its own batch statistics; running stats updated in place
     RC(forward_train_impl(net, (const unsigned char*)a->packed_online, a->params, a->bnstats, tin, ns_online, gtb ? 1 : 2, ao, A, st));
@@ -462,6 +467,10 @@ static int td_forward_impl(vdqn_net* net, const vdqn_step_args* a, float cql_alp
     e = hipMemsetAsync(mc_stats, 0, 8, st);
     VDQN_CHECK(e == hipSuccess, "vdqn_net_td_forward_mc: memset failed: %s", hipGetErrorString(e));
   }
+  if (iql && iql_stats) {
+    e = hipMemsetAsync(iql_stats, 0, 8, st);
+    VDQN_CHECK(e == hipSuccess, "vdqn_net_td_forward_iql: memset failed: %s", hipGetErrorString(e));
+  }
 
   const float* qf_online = reinterpret_cast<const float*>(ao + A.qf);
   if (!gtb) {
@@ -474,7 +483,8 @@ static int td_forward_impl(vdqn_net* net, const vdqn_step_args* a, float cql_alp
     t.dtype = dt;
     t.deterministic = net->cfg.deterministic;
     t.q_copy = a->q_before;  // (the compact copy of Q(s) rides in the loss launch: no 2-D copy between the loss and the first data gradient)
-    if (mc_return) RC(vdqn_td_loss_mc(&t, a->sample_weight, a->sample_err, cql_alpha, cql_alpha > 0.f ? cql_penalty : nullptr, a->sample_gamma, mc_return, mc_flags, mc_stats, st));
+    if (iql) RC(vdqn_td_loss_iql(&t, a->sample_weight, a->sample_err, a->sample_gamma, iql_expectile, iql_stats, st));
+    else if (mc_return) RC(vdqn_td_loss_mc(&t, a->sample_weight, a->sample_err, cql_alpha, cql_alpha > 0.f ? cql_penalty : nullptr, a->sample_gamma, mc_return, mc_flags, mc_stats, st));
     else if (a->sample_gamma) RC(vdqn_td_loss_nstep(&t, a->sample_weight, a->sample_err, cql_alpha, cql_alpha > 0.f ? cql_penalty : nullptr, a->sample_gamma, st));
     else if (cql_alpha > 0.f) RC(vdqn_td_loss_cql(&t, a->sample_weight, a->sample_err, cql_alpha, cql_penalty, st));
     else if (a->sample_weight) RC(vdqn_td_loss_weighted(&t, a->sample_weight, a->sample_err, st));
@@ -517,6 +527,17 @@ extern "C" int vdqn_net_td_forward_mc(vdqn_net* net, const vdqn_step_args* a, fl
   VDQN_CHECK(!(mc_flags & 2) || cql_alpha > 0.f, "vdqn_net_td_forward_mc: mc_flags bit 1 (calibrated) needs cql_alpha > 0");
   if (cql_alpha > 0.f) VDQN_CHECK(net->cfg.action_dim >= 2, "vdqn_net_td_forward_mc: action_dim is 1: with one action the penalty is identically zero");
   return td_forward_impl(net, a, cql_alpha, cql_penalty, stream, mc_return, mc_flags, mc_stats);
+}
+
+// vdqn_net_td_forward for implicit Q-learning (csrc/iql.hip): everything the loss launch would refuse is refused here, before the
+// forward; then td_forward_impl with the target pass over `before` and vdqn_td_loss_iql for the loss launch.
+extern "C" int vdqn_net_td_forward_iql(vdqn_net* net, const vdqn_step_args* a, float expectile, float* iql_stats, void* stream) {
+  VDQN_CHECK(net && a, "vdqn_net_td_forward_iql: null arg");
+  VDQN_CHECK(net->value_head, "vdqn_net_td_forward_iql: the net has no value head (create it with vdqn_net_create_v(cfg, 1, ..))");
+  VDQN_CHECK(!a->train_on_ground_truth, "vdqn_net_td_forward_iql: the ground-truth branch regresses Q(s, a) on given targets and bootstraps nothing (train_on_ground_truth)");
+  VDQN_CHECK(!a->linear, "vdqn_net_td_forward_iql: linear: y = r + (Qa - 0.1) is the reference's undiscounted Double-DQN target and has no V(s') form");
+  VDQN_CHECK(isfinite(expectile) && expectile >= 0.5f && expectile < 1.0f, "vdqn_net_td_forward_iql: expectile %g must be in [0.5, 1)", (double)expectile);
+  return td_forward_impl(net, a, 0.f, nullptr, stream, nullptr, 0, nullptr, expectile, iql_stats);
 }
 
 // One held-out batch of a validation pass (train_q_network.py:183-186 `eval_losses`, :240 `# checkpoint and eval`): the frames

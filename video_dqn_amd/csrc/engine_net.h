@@ -89,6 +89,7 @@ inline int64_t align_up(int64_t v, int64_t a = 256) { return (v + a - 1) / a * a
 
 struct vdqn_net {
   vdqn_net_config cfg;  // cfg.dtype is the STORAGE dtype: VDQN_F32 for a VDQN_F32X3 engine (every pointwise entry takes that)
+  int value_head = 0;   // 1: the Q layer also computes num_classes state values V(c) behind its Q columns (vdqn_net_create_v)
   int gemm_dtype;       // dtype of the GEMM calls (convolutions, linear layers, weight gradients, stem): the requested one
   int esz;  // bytes per activation element
   std::vector<Layer> layers;
@@ -101,6 +102,7 @@ struct vdqn_net {
   // layer indices
   int l_conv1, l_f8, l_top0, l_top2, l_top4;  // 'basic': l_top4 is the single `top` Linear, the other head layers are -1
   bool basic() const { return cfg.extra_capacity == 0; }
+  int n_q() const { return cfg.action_dim * cfg.num_classes; }  // the Q columns; with the value head, V(c) is column n_q() + c
   int l_b_conv1[8], l_b_conv2[8], l_b_ds[8];
   // A second HIP stream for work that is independent of the main dependency chain: the weight gradients (they only
   // need gy, the data-gradient chain does not wait for them) and the target-network forward.  Blocks of the side

@@ -94,6 +94,8 @@ Layer make_linear(const std::string& name, int out_f, int in_f, int stage, bool 
 void build_layers(vdqn_net* net) {
   const int F = net->cfg.num_frames;
   std::vector<Layer> fwd;  // forward order
+  // the value head (vdqn_net_create_v): num_classes more rows of the Q layer, registered below as value.weight / value.bias
+  const int n_value = net->value_head ? net->cfg.num_classes : 0;
   {
     Layer L = make_conv("resnet.conv1", "resnet.bn1", 64, 3, 7, 2, 3, 224, 2);
     L.kind = K_CONV1_S2D;
@@ -124,9 +126,9 @@ void build_layers(vdqn_net* net) {
     fwd.push_back(make_conv("features.8", "", 64, 512, 3, 1, 0, 7, 0));
     fwd.push_back(make_linear("top.0", 512, 1600 * F, 0, true));
     fwd.push_back(make_linear("top.2", 256, 512, 0, false));
-    fwd.push_back(make_linear("top.4", net->cfg.action_dim * net->cfg.num_classes, 256, 0, false));
+    fwd.push_back(make_linear("top.4", net->n_q() + n_value, 256, 0, false));
   } else {  // :32-34: global average pool, then one Linear over the F concatenated 512-vectors
-    fwd.push_back(make_linear("top", net->cfg.action_dim * net->cfg.num_classes, 512 * F, 0, false));
+    fwd.push_back(make_linear("top", net->n_q() + n_value, 512 * F, 0, false));
   }
 
   // store layers ordered by backward stage (stable), so each stage's gradients are one contiguous range
@@ -164,7 +166,11 @@ void build_layers(vdqn_net* net) {
     for (int i = net->layer_stage_first[st]; i < net->layer_stage_first[st] + net->layer_stage_count[st]; ++i) {
       Layer& L = net->layers[i];
       L.w_off = poff;
-      if (L.kind == K_LINEAR || L.kind == K_LINEAR_PERM) add_param(net, L.name + ".weight", poff, {L.co, L.ci}, 0, st);
+      const bool q_layer = n_value > 0 && (L.name == "top.4" || L.name == "top");  // its last n_value rows are the value head's
+      if (q_layer) {  // <top>.weight {C*A, in} with value.weight {C, in} directly behind it: one contiguous [co, in] operand
+        add_param(net, L.name + ".weight", poff, {L.co - n_value, L.ci}, 0, st);
+        add_param(net, "value.weight", poff + (int64_t)(L.co - n_value) * L.ci, {n_value, L.ci}, 0, st);
+      } else if (L.kind == K_LINEAR || L.kind == K_LINEAR_PERM) add_param(net, L.name + ".weight", poff, {L.co, L.ci}, 0, st);
       else add_param(net, L.name + ".weight", poff, {L.co, L.ci, L.r, L.s}, 0, st);
       poff += (int64_t)L.co * L.ci * L.r * L.s;
       poff = (poff + 3) / 4 * 4;  // keep every tensor 16-byte aligned
@@ -184,7 +190,8 @@ void build_layers(vdqn_net* net) {
         soff += L.co;
       } else if (L.has_bias) {
         L.b_off = poff;
-        add_param(net, L.name + ".bias", poff, {L.co}, 0, st);
+        add_param(net, L.name + ".bias", poff, {q_layer ? L.co - n_value : L.co}, 0, st);
+        if (q_layer) add_param(net, "value.bias", poff + L.co - n_value, {n_value}, 0, st);
         poff += L.co;
         poff = (poff + 3) / 4 * 4;
       }
@@ -238,6 +245,10 @@ void build_layers(vdqn_net* net) {
     } else {
       order.push_back("top.weight");
       order.push_back("top.bias");
+    }
+    if (n_value > 0) {  // behind the reference's ids: the reference's Adam state keeps its numbering
+      order.push_back("value.weight");
+      order.push_back("value.bias");
     }
     for (auto& pi : net->params)
       for (size_t i = 0; i < order.size(); ++i)
@@ -463,7 +474,22 @@ BwdLayout bwd_layout(const vdqn_net* net, int n_samples) {
 // ---------------------------------------------------------------------------------------------------------
 // C ABI
 // ---------------------------------------------------------------------------------------------------------
-extern "C" int vdqn_net_create(const vdqn_net_config* cfg, vdqn_net** out) {
+static int net_create(const vdqn_net_config* cfg, int value_head, vdqn_net** out);
+extern "C" int vdqn_net_create(const vdqn_net_config* cfg, vdqn_net** out) { return net_create(cfg, 0, out); }
+// vdqn_net_create with num_classes state values V(c) behind the Q columns of the Q layer (implicit Q-learning, csrc/iql.hip)
+extern "C" int vdqn_net_create_v(const vdqn_net_config* cfg, int32_t value_head, vdqn_net** out) {
+  VDQN_CHECK(value_head == 0 || value_head == 1, "vdqn_net_create_v: value_head must be 0 or 1, not %d", value_head);
+  if (value_head) {
+    VDQN_CHECK(cfg && out, "vdqn_net_create_v: null arg");
+    VDQN_CHECK(cfg->action_dim >= 2, "vdqn_net_create_v: action_dim is %d: with one action Q(s, a) is the state value already (value_head needs action_dim >= 2)", cfg->action_dim);
+    VDQN_CHECK(cfg->num_classes >= 1 && (int64_t)cfg->action_dim * cfg->num_classes + cfg->num_classes <= 64,
+               "vdqn_net_create_v: action_dim*num_classes + num_classes must be in 1..64 (the Q columns and one V per category share a 64-wide row)");
+  }
+  return net_create(cfg, value_head, out);
+}
+extern "C" int vdqn_net_value_head(const vdqn_net* net) { return net ? net->value_head : 0; }
+
+static int net_create(const vdqn_net_config* cfg, int value_head, vdqn_net** out) {
   VDQN_CHECK(cfg && out, "vdqn_net_create: null arg");
   VDQN_CHECK(cfg->extra_capacity == 0 || cfg->extra_capacity == 1, "vdqn_net_create: extra_capacity must be 0 or 1");
   VDQN_CHECK(cfg->dtype == VDQN_F32 || cfg->dtype == VDQN_BF16 || cfg->dtype == VDQN_F32X3, "vdqn_net_create: bad dtype %d", cfg->dtype);
@@ -473,6 +499,7 @@ extern "C" int vdqn_net_create(const vdqn_net_config* cfg, vdqn_net** out) {
   VDQN_CHECK(cfg->deterministic == 0 || cfg->deterministic == 1, "vdqn_net_create: deterministic must be 0 or 1");
   vdqn_net* net = new vdqn_net();
   net->cfg = *cfg;
+  net->value_head = value_head;
   net->gemm_dtype = cfg->dtype;
   if (cfg->dtype == VDQN_F32X3) net->cfg.dtype = VDQN_F32;  // f32 layout, tensors and pointwise kernels; only the GEMMs differ
   net->esz = cfg->dtype == VDQN_BF16 ? 2 : 4;

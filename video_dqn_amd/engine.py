@@ -38,6 +38,16 @@ _DIST_EARLY_ADAM_MODE = os.environ.get("VDQN_DIST_EARLY_ADAM", "0")
 
 
 
+_SAID = set()
+
+
+def _say_once(text: str) -> None:
+    """Print `text` the first time it is said in this process."""
+    if text not in _SAID:
+        _SAID.add(text)
+        print(text)
+
+
 def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
     return None if t is None else t.data_ptr()
 
@@ -67,7 +77,7 @@ class NetEngine:
     """One HabitatDQNMultiAction instance on the device: flat f32 master parameters + BN statistics."""
 
     def __init__(self, action_dim=3, num_classes=5, num_frames=1, extra_capacity=True, dtype="bf16",
-                 max_batch=512, device=None, deterministic=None):
+                 max_batch=512, device=None, deterministic=None, value_head=False):
         self.lib = _lib.load()
         # device="cpu" gives a storage-only instance (state_dict / checkpoint plumbing); every compute entry
         # point still requires the GPU and raises otherwise — there is no CPU arithmetic in this package.
@@ -86,8 +96,14 @@ class NetEngine:
         self.deterministic = bool(deterministic)
         self.cfg = _lib.NetConfig(action_dim, num_classes, num_frames, int(self.extra_capacity), DTYPES[dtype], max_batch,
                                   int(self.deterministic))
+        # value_head (implicit Q-learning): num_classes state values V(c) behind the Q columns of the Q layer, its extra rows the
+        # parameters `value.weight` / `value.bias` (vdqn_net_create_v); False: vdqn_net_create, the same tables and bits
+        self.value_head = bool(value_head)
         h = C.c_void_p()
-        _lib.check(self.lib.vdqn_net_create(C.byref(self.cfg), C.byref(h)), "vdqn_net_create")
+        if self.value_head:
+            _lib.check(self.lib.vdqn_net_create_v(C.byref(self.cfg), 1, C.byref(h)), "vdqn_net_create_v")
+        else:
+            _lib.check(self.lib.vdqn_net_create(C.byref(self.cfg), C.byref(h)), "vdqn_net_create")
         self.handle = h
         self.max_batch = max_batch
         self.slots: "OrderedDict[str, ParamSlot]" = OrderedDict()
@@ -134,7 +150,11 @@ class NetEngine:
         """Copy every tensor the engine owns (by its reference state_dict name) from ``state_dict``."""
         with torch.no_grad():
             for name in self.slots:
+                if name.startswith("value.") and name not in state_dict:
+                    continue  # a DQN checkpoint into a value-head engine (warm start): the initialised value.* stay
                 self.view(name).copy_(state_dict[name].to(torch.float32))
+        if self.value_head and not all(n in state_dict for n in ("value.weight", "value.bias")):
+            _say_once("value head: the state_dict has no value.weight / value.bias, the value head keeps its initialisation")
         self.mark_dirty()
 
     def mark_dirty(self):
@@ -187,6 +207,19 @@ class NetEngine:
             _lib.check(self.lib.vdqn_net_forward(self.handle, _ptr(self.packed), _ptr(frames), src_kind, n_samples,
                                                  _ptr(acts), _ptr(q), _stream()), "vdqn_net_forward")
         return q
+
+    def state_values(self, n_samples: int) -> torch.Tensor:
+        """V(s) f32 [n_samples, num_classes] of the LAST `forward(.., n_samples)` call: the value head's columns of the f32 Q rows
+        that call left in its workspace (no second pass)."""
+        self._need_gpu()
+        if not self.value_head:
+            raise _lib.VdqnError("state_values: this NetEngine has no value head (NetEngine(value_head=True))")
+        acts = self._acts.get(n_samples)
+        if acts is None:
+            raise _lib.VdqnError(f"state_values: no forward over {n_samples} samples has run")
+        off = self.lib.vdqn_net_act_offset(self.handle, n_samples, b"qf")
+        nq = self.num_classes * self.action_dim
+        return acts[off:off + n_samples * 64 * 4].view(torch.float32).view(n_samples, 64)[:, nq:nq + self.num_classes].clone()
 
     # ---- one model call with its own backward (torch.autograd over the module, model.py) ----------------------------
     def forward_saved(self, frames: torch.Tensor, src_kind: int, n_samples: int, packed: torch.Tensor):
@@ -300,7 +333,7 @@ class TDStepper:
                  target_update_interval: int = 8000, betas=(0.9, 0.999), eps: float = 1e-8, world_size: int = 1,
                  allreduce=None, loss_kind: str = "l2", allreduce_loss=None, allreduce_wait=None, allreduce_errors=None,
                  grad_clip_norm: float = 0.0, weight_decay: float = 0.0, lr_fn=None, cql_alpha: float = 0.0,
-                 target_tau: float = 0.0, mc_floor: bool = False, cql_calibrated: bool = False):
+                 target_tau: float = 0.0, mc_floor: bool = False, cql_calibrated: bool = False, iql_expectile: float = 0.0):
         net._need_gpu()
         self.net, self.B = net, batch
         self.lib = net.lib
@@ -345,6 +378,23 @@ class TDStepper:
                                  "target to floor; y = r + (Qa - 0.1) has no discount)")
         if cql_calibrated and not cql_alpha > 0:
             raise _lib.VdqnError("TDStepper: cql_calibrated needs cql_alpha > 0 (there is no penalty to calibrate)")
+        # iql_expectile > 0 (implicit Q-learning, csrc/iql.hip; needs NetEngine(value_head=True)): the update is
+        # vdqn_net_td_forward_iql — the target pass over s instead of s', the loss launch vdqn_td_loss_iql, which fits V(s) to the
+        # target network's Q(s, a_data) by expectile regression and bootstraps Q from V(s') — and `iql_stats` receives this rank's
+        # share of {the V loss, the mean of Q_target(s, a_data) - V(s)}.  0: the entries above, launched as ever.
+        iql_expectile = float(iql_expectile)
+        if iql_expectile != 0.0 and not (0.5 <= iql_expectile < 1.0):
+            raise _lib.VdqnError(f"TDStepper: iql_expectile must be 0 (off) or in [0.5, 1), not {iql_expectile}")
+        if iql_expectile > 0:
+            if not getattr(net, "value_head", False):
+                raise _lib.VdqnError("TDStepper: iql_expectile needs a network with the value head (NetEngine(value_head=True))")
+            if train_on_ground_truth or linear:
+                raise _lib.VdqnError("TDStepper: iql_expectile applies to the TD branch without linear (train_on_ground_truth bootstraps "
+                                     "nothing; y = r + (Qa - 0.1) has no V(s') form)")
+            if cql_alpha > 0 or self.mc_flags:
+                raise _lib.VdqnError("TDStepper: iql_expectile does not combine with cql_alpha, mc_floor or cql_calibrated (out of scope: "
+                                     "the IQL loss launch has neither the penalty nor the return floor)")
+        self.iql_expectile = iql_expectile
         # target_tau > 0 (soft / Polyak target updates): `target_params`, an f32 copy of the whole flat `net.params` (the trainable
         # prefix and the frozen resnet.fc tail), follows the online weights as target <- target + tau (params - target) inside every
         # Adam launch (vdqn_adam_polyak), and `packed_target` is folded from it in front of every update; target_update_interval is
@@ -391,6 +441,7 @@ class TDStepper:
             self.loss = torch.zeros(1, dtype=torch.float32, device=dev)
             self.cql_penalty = torch.zeros(1, dtype=torch.float32, device=dev)
             self.mc_stats = torch.zeros(2, dtype=torch.float32, device=dev)
+            self.iql_stats = torch.zeros(2, dtype=torch.float32, device=dev)
             self.q_before = torch.zeros((batch, net.num_classes * net.action_dim), dtype=torch.float32, device=dev)
             self._ones = torch.ones((batch, net.num_classes), dtype=torch.float32, device=dev)
             if self.grad_clip_norm > 0:
@@ -523,7 +574,10 @@ class TDStepper:
             if ahead is not None and ahead[0] == self._frames_key(before, after, src_kind):
                 slot = ahead[1]  # these frames were packed during the previous update (ordered in front of `st` by its last stage)
                 a.packed_frames = self._packed_buffer(slot).data_ptr()
-            if mc_return is not None:
+            if self.iql_expectile > 0:
+                _lib.check(self.lib.vdqn_net_td_forward_iql(n.handle, C.byref(a), self.iql_expectile, self.iql_stats.data_ptr(), st),
+                           "vdqn_net_td_forward_iql")
+            elif mc_return is not None:
                 _lib.check(self.lib.vdqn_net_td_forward_mc(n.handle, C.byref(a), self.cql_alpha, self.cql_penalty.data_ptr(), mc_return.data_ptr(),
                                                            self.mc_flags, self.mc_stats.data_ptr(), st), "vdqn_net_td_forward_mc")
             elif self.cql_alpha > 0:

@@ -32,7 +32,9 @@ from collections import OrderedDict
 import torch
 import torch.nn as nn
 
-from .engine import NetEngine
+from .engine import NetEngine, _say_once
+
+VALUE_KEYS = ("value.weight", "value.bias")  # the value head's parameters: never among the reference's keys
 
 
 class _QFunction(torch.autograd.Function):
@@ -142,7 +144,7 @@ def load_torchvision_resnet18(engine: NetEngine, sd, source: str = "state_dict")
 
 class HabitatDQNMultiAction(nn.Module):
     def __init__(self, action_dim, num_classes=5, extra_capacity=False, panorama=True, num_frames=None,
-                 dtype=None, device=None, max_batch=64, pretrained_weights=None, deterministic=None):
+                 dtype=None, device=None, max_batch=64, pretrained_weights=None, deterministic=None, value_head=False):
         super().__init__()
         self.extra_capacity = extra_capacity
         self.num_classes = num_classes
@@ -154,7 +156,11 @@ class HabitatDQNMultiAction(nn.Module):
         dtype = dtype or os.environ.get("VDQN_DTYPE", "bf16")
         if extra_capacity:
             print("Model loading with extra_capacity")  # :28
-        self.engine = NetEngine(action_dim, num_classes, num_frames, extra_capacity, dtype, max_batch, device, deterministic)
+        # value_head (implicit Q-learning, IQL_EXPECTILE): a child `value` with `weight` [num_classes, in] and `bias` [num_classes],
+        # the rows of the Q layer behind the reference's; `forward` still returns the Q values alone, `state_values` the head's
+        self.value_head = bool(value_head)
+        self.engine = NetEngine(action_dim, num_classes, num_frames, extra_capacity, dtype, max_batch, device, deterministic,
+                                value_head=self.value_head)
         self._build_tree()
         _init_like_reference(self.engine)
         # models.resnet18(pretrained=True) (:11): the ImageNet weights come from a file (config key PRETRAINED_WEIGHTS, or the
@@ -226,6 +232,8 @@ class HabitatDQNMultiAction(nn.Module):
         else:  # :33-34
             self.features = nn.Sequential(*list(self.resnet.children())[:-1])
             self.top = _conv(P, "top", True)
+        if self.value_head:  # behind the reference's modules: state_dict() lists the reference's 250 keys first, then value.*
+            self.value = _conv(P, "value", True)
         object.__setattr__(self, "_trainable_params", [cache[s.name] for s in self._trainable_slots])
         del self._cache
         self._packed_grad = None      # packed weights incl. the data-gradient operands, for differentiable forwards
@@ -255,6 +263,12 @@ class HabitatDQNMultiAction(nn.Module):
         super()._load_from_state_dict(*a, **k)
 
     def load_state_dict(self, state_dict, strict=True):
+        if self.value_head and not all(k in state_dict for k in VALUE_KEYS):
+            # a DQN (or reference) checkpoint into a value-head model, the warm start: the value head keeps what it holds
+            _say_once("value head: the state_dict has no value.weight / value.bias, the value head keeps its initialisation")
+            state_dict = OrderedDict(state_dict)
+            for k in VALUE_KEYS:
+                state_dict.setdefault(k, self.engine.view(k).detach().clone())
         r = super().load_state_dict(state_dict, strict=strict)
         self.engine.mark_dirty()
         return r
@@ -298,6 +312,21 @@ class HabitatDQNMultiAction(nn.Module):
             q = eng.forward(inp, src_kind, b)
         return q.view((-1, self.num_classes, self.action_dim))
 
+    def state_values(self, frames):
+        """V(s) f32 [B, num_classes] of the value head, from the same forward pass that gives `forward(frames)` (no gradient)."""
+        if not self.value_head:
+            raise RuntimeError("state_values: the model was built without value_head=True")
+        if frames.shape[0] > self.engine.max_batch:
+            return torch.cat([self.state_values(frames[i:i + self.engine.max_batch]) for i in range(0, frames.shape[0], self.engine.max_batch)], 0)
+        was_training = self.training
+        self.training = False  # (this module's flag alone: the plain forward, 'basic' on its running statistics, nothing written)
+        try:
+            with torch.no_grad():
+                q = self.forward(frames)
+        finally:
+            self.training = was_training
+        return self.engine.state_values(q.shape[0])
+
 
 def build_model(config, max_batch=None):
     """train_q_network.py:36-47 (config.device selects the GPU; dtype from config.COMPUTE_DTYPE)."""
@@ -308,7 +337,8 @@ def build_model(config, max_batch=None):
                                  dtype=getattr(config, "COMPUTE_DTYPE", None), device=config.device,
                                  max_batch=max_batch or max(64, 2 * getattr(config, "BATCH_SIZE", 16)),
                                  pretrained_weights=(getattr(config, "PRETRAINED_WEIGHTS", "") or None),
-                                 deterministic=(True if getattr(config, "DETERMINISTIC", False) else None))
+                                 deterministic=(True if getattr(config, "DETERMINISTIC", False) else None),
+                                 value_head=float(getattr(config, "IQL_EXPECTILE", 0.0) or 0.0) > 0)
 
 
 def load_model_number(config, number, model_loc=None):

@@ -278,6 +278,25 @@ def td_loss_mc(q_before, q_after_online, q_after_target, act, rew, term, valid=N
     return loss, dq, dq32, penalty, err, stats
 
 
+def td_loss_iql(q_before, q_after_online, q_target_before, act, rew, term, valid=None, *, expectile, weights=None, with_err=False,
+                discount=None, n_cat=5, n_act=3, gamma=0.99, inv_count=None, clip_rect=True, out_dtype=torch.float32, loss_kind="l2",
+                deterministic=False, linear=False, with_stats=True):
+    """The implicit Q-learning loss (vdqn_td_loss_iql): rows of ldq >= n_cat * n_act + n_cat columns, Q(c, a) at c * n_act + a and V(c)
+    at n_cat * n_act + c.  q_before / q_after_online: the online network at s / s'; q_target_before: the TARGET network at s.  V(s) is
+    fitted to Q_target(s, act) by expectile regression, Q(s, act) to rew + gamma (1 - term) V(s').  weights, discount: optional f32 [B].
+    Returns (loss[1], dq[B, ldq] out_dtype, dq_f32, stats[2] = {V loss, mean Q_target(s, act) - V(s)} or None, err[B] or None)."""
+    lib = _lib.load()
+    a, loss, dq, dq32 = _td_args(q_before, q_after_online, q_target_before, act, rew, term, valid, n_cat, n_act, gamma, inv_count, clip_rect,
+                                 linear, out_dtype, loss_kind, deterministic)
+    if discount is not None and (discount.dtype != torch.float32 or discount.numel() != q_before.shape[0] or not discount.is_contiguous()):
+        raise ValueError(f"td_loss_iql: discount must be a contiguous f32 [{q_before.shape[0]}] device tensor")
+    err = torch.empty(q_before.shape[0], dtype=torch.float32, device=loss.device) if with_err else None
+    stats = torch.zeros(2, dtype=torch.float32, device=loss.device) if with_stats else None
+    _lib.check(lib.vdqn_td_loss_iql(C.byref(a), _ptr(weights), _ptr(err), _ptr(discount), float(expectile), _ptr(stats), _stream()),
+               "vdqn_td_loss_iql")
+    return loss, dq, dq32, stats, err
+
+
 def mc_returns(next_row, rew, term, *, gamma, rounds, out=None, workspace=None):
     """vdqn_mc_returns: the Monte-Carlo return table G f32 [N, n_cat] over the first 2^rounds rows of every row's chain (next_row int32
     [N]; rew / term f32 [N, n_cat], all on the device, none written).  workspace: a device byte tensor of at least

@@ -22,7 +22,7 @@ from .augment import COLOR_KEYS, Augmenter, jz
 from .dataset import QLearningRealDataset, SyntheticTupleDataset
 from .dist import BucketAllReduce, agree_all, broadcast_replica_state
 from .engine import TDStepper
-from .model import build_model
+from .model import VALUE_KEYS, build_model
 from .optim import lr_at, schedule_active
 from .shards import (FRAME_BYTES, Batch, DeviceFrameStore, HostFrameStream, RankShardedFrameStore, ShardDataset, collate_batches,
                      is_shard_dir)
@@ -52,13 +52,13 @@ def optimizer_state_dict(stepper: TDStepper) -> dict:
     state = {}
     if stepper.adam_step > 0:
         for s in net.slots.values():
-            if s.kind != 0:
+            if s.kind != 0 or s.name in VALUE_KEYS:  # (the value head's moments: value_head_state)
                 continue
             sl = slice(s.offset, s.offset + s.numel)
             state[s.param_id] = {"step": stepper.adam_step,
                                  "exp_avg": stepper.exp_avg[sl].view(s.shape).clone(),
                                  "exp_avg_sq": stepper.exp_avg_sq[sl].view(s.shape).clone()}
-    n_params = sum(1 for s in net.slots.values() if s.kind in (0, 1))
+    n_params = sum(1 for s in net.slots.values() if s.kind in (0, 1) and s.name not in VALUE_KEYS)
     # (GRAD_CLIP_NORM / WEIGHT_DECAY / LR_*: `lr` is the rate of the last update, `weight_decay` the AdamW factor, and `initial_lr`
     # — the key torch's schedulers add — is there only while a schedule is active: a default-config checkpoint keeps its exact keys)
     group = {"lr": stepper.lr, "betas": tuple(stepper.betas), "eps": stepper.eps, "weight_decay": getattr(stepper, "weight_decay", 0) or 0,
@@ -71,7 +71,7 @@ def optimizer_state_dict(stepper: TDStepper) -> dict:
 
 def load_optimizer_state_dict(stepper: TDStepper, sd: dict) -> None:
     net = stepper.net
-    by_id = {s.param_id: s for s in net.slots.values() if s.kind == 0}
+    by_id = {s.param_id: s for s in net.slots.values() if s.kind == 0 and s.name not in VALUE_KEYS}
     step = 0
     with torch.no_grad():
         for pid, st in sd["state"].items():
@@ -85,13 +85,55 @@ def load_optimizer_state_dict(stepper: TDStepper, sd: dict) -> None:
     stepper.lr, stepper.betas, stepper.eps = g["lr"], tuple(g["betas"]), g["eps"]
 
 
+def reference_state_dict(model) -> "OrderedDict[str, torch.Tensor]":
+    """model.state_dict() without the value head's tensors: the reference's keys in the reference's shapes and order."""
+    sd = model.state_dict()  # (without a value head: the dict as it is)
+    for k in VALUE_KEYS:
+        sd.pop(k, None)
+    getattr(sd, "_metadata", {}).pop("value", None)
+    return sd
+
+
+def value_head_state(stepper: TDStepper) -> dict:
+    """IQL_EXPECTILE: the value head's parameters and Adam moments, what `model_state_dict` and `optimizer_state_dict` leave out so
+    that the reference's class and its Adam load those two as they always did:
+    {"state_dict": {"value.weight", "value.bias"}, "optimizer_state": {name: {step, exp_avg, exp_avg_sq}}} (no moments before the
+    first update, as in torch)."""
+    net = stepper.net
+    out = {"state_dict": OrderedDict(), "optimizer_state": {}}
+    for name in VALUE_KEYS:
+        s = net.slots[name]
+        sl = slice(s.offset, s.offset + s.numel)
+        out["state_dict"][name] = net.params[sl].view(s.shape).clone()
+        if stepper.adam_step > 0:
+            out["optimizer_state"][name] = {"step": stepper.adam_step, "exp_avg": stepper.exp_avg[sl].view(s.shape).clone(),
+                                            "exp_avg_sq": stepper.exp_avg_sq[sl].view(s.shape).clone()}
+    return out
+
+
+def load_value_head_state(stepper: TDStepper, state: dict) -> None:
+    """A `value_head_state` into the engine's parameters and the stepper's moments (behind load_optimizer_state_dict, which sets
+    the step count)."""
+    net = stepper.net
+    with torch.no_grad():
+        for name in VALUE_KEYS:
+            s = net.slots[name]
+            sl = slice(s.offset, s.offset + s.numel)
+            net.params[sl].copy_(state["state_dict"][name].to(torch.float32).reshape(-1))
+            st = state.get("optimizer_state", {}).get(name)
+            if st is not None:
+                stepper.exp_avg[sl].copy_(st["exp_avg"].reshape(-1))
+                stepper.exp_avg_sq[sl].copy_(st["exp_avg_sq"].reshape(-1))
+    net.mark_dirty()
+
+
 def target_state_dict(stepper: TDStepper, model) -> "OrderedDict[str, torch.Tensor]":
     """TARGET_TAU > 0: the Polyak-averaged target weights as a state_dict with the model's own keys, names and shapes — every
     parameter from `stepper.target_params` through the engine's slot table, every BatchNorm buffer as the online network holds it
     (statistics are copied, not averaged) — so the reference's class loads it as the smoothed network."""
     net = stepper.net
     out = OrderedDict()
-    for name, value in model.state_dict().items():
+    for name, value in reference_state_dict(model).items():  # (the target's V rows are never read: reference keys only)
         s = net.slots.get(name)
         if s is not None and s.kind in (0, 1):
             out[name] = stepper.target_params[s.offset:s.offset + s.numel].view(s.shape).clone()
@@ -105,7 +147,7 @@ def load_target_state_dict(stepper: TDStepper, sd) -> None:
     net = stepper.net
     with torch.no_grad():
         for s in net.slots.values():
-            if s.kind in (0, 1):
+            if s.kind in (0, 1) and s.name not in VALUE_KEYS:  # (value.* are not in it: sync_target's copy stays, and is never read)
                 stepper.target_params[s.offset:s.offset + s.numel].copy_(sd[s.name].to(torch.float32).reshape(-1))
     with torch.cuda.device(net.device):
         net.pack_weights(stepper.packed_target, with_dgrad=False, params=stepper.target_params)
@@ -116,8 +158,10 @@ def save_checkpoint(path, sample_number, model, stepper, replay_state=None, targ
     three, which stay as they are (load_model_number and the reference class read the file as before).  target_state_dict
     (TARGET_TAU > 0): the averaged target weights in the model's names and shapes, likewise under a key of its own."""
     ckpt = {"sample_number": sample_number,
-            "model_state_dict": model.state_dict(),
+            "model_state_dict": reference_state_dict(model),
             "optimizer_state_dict": optimizer_state_dict(stepper)}
+    if getattr(stepper.net, "value_head", False):  # IQL_EXPECTILE: the value head beside the reference's three keys, not inside them
+        ckpt["value_head"] = value_head_state(stepper)
     if replay_state is not None:
         ckpt["replay_state"] = replay_state
     if target_state_dict is not None:
@@ -227,6 +271,32 @@ def check_mc(config) -> None:
         if key == "CQL_CALIBRATED" and not float(getattr(config, "CQL_ALPHA", 0.0)) > 0:
             raise ValueError("CQL_CALIBRATED needs CQL_ALPHA > 0: it calibrates the conservative penalty, and there is none")
         check_full_store(config, key, "indexes its return table by the rows of the resident store")
+
+
+def check_iql(config) -> None:
+    """IQL_EXPECTILE: raise ValueError naming the key (before any device work) for a value outside {0} and [0.5, 1) and, when it is
+    on, for every configuration implicit Q-learning does not cover."""
+    import math
+    tau = getattr(config, "IQL_EXPECTILE", 0.0)
+    if isinstance(tau, bool) or not isinstance(tau, (int, float)) or not math.isfinite(tau) or not (tau == 0 or 0.5 <= tau < 1):
+        raise ValueError(f"IQL_EXPECTILE must be 0 (off) or a number in [0.5, 1), not {tau!r}")
+    if tau == 0:
+        return
+    if getattr(config, "TRAIN_ON_GROUND_TRUTH", False):
+        raise ValueError("IQL_EXPECTILE needs the TD branch: TRAIN_ON_GROUND_TRUTH regresses Q(s, a) on given targets and bootstraps nothing")
+    if getattr(config, "LINEAR", False):
+        raise ValueError("IQL_EXPECTILE does not cover LINEAR: y = r + (Qa - 0.1) is the undiscounted Double-DQN target and has no V(s') form")
+    for key in ("VALUE_LEARNING", "ONE_ACTION"):
+        if getattr(config, key, False):
+            raise ValueError(f"IQL_EXPECTILE needs more than one action: {key} builds a network with one action column, whose "
+                             "Q(s, a) is the state value already")
+    if float(getattr(config, "CQL_ALPHA", 0.0)) > 0:
+        raise ValueError("IQL_EXPECTILE with CQL_ALPHA > 0 is deliberately out of scope: the IQL loss launch has no conservative "
+                         "penalty (implicit Q-learning avoids out-of-data actions instead of penalising them); use one or the other")
+    for key in ("CQL_CALIBRATED", "MC_RETURN_FLOOR"):
+        if getattr(config, key, False):
+            raise ValueError(f"IQL_EXPECTILE with {key} is deliberately out of scope: the IQL loss launch takes no Monte-Carlo "
+                             "return table; use one or the other")
 
 
 def check_nstep(config, world_size: int = 1) -> None:
@@ -340,6 +410,7 @@ def check_run(config, world_size: int = 1) -> None:
     check_validation(config)
     check_nstep(config, world_size)
     check_mc(config)
+    check_iql(config)
     if schedule_active(getattr(config, "LR_WARMUP_STEPS", 0), getattr(config, "LR_SCHEDULE", "constant")):
         float(config.LEARNING_RATE)  # (no check above looks at it: what is no number is refused here, not when the schedule is built)
     if getattr(config, "PRIORITIZED_REPLAY", False):
@@ -448,6 +519,7 @@ def build_helpers(config, dataset, store, model, comm, rank, world_size, log):
     n_step = int(getattr(config, "N_STEP", 1))
     mc_floor, cql_calibrated = bool(getattr(config, "MC_RETURN_FLOOR", False)), bool(getattr(config, "CQL_CALIBRATED", False))
     cql_alpha, target_tau = float(getattr(config, "CQL_ALPHA", 0.0)), float(getattr(config, "TARGET_TAU", 0.0))
+    iql_expectile = float(getattr(config, "IQL_EXPECTILE", 0.0) or 0.0)
     clip_norm, weight_decay = float(getattr(config, "GRAD_CLIP_NORM", 0.0)), float(getattr(config, "WEIGHT_DECAY", 0.0))
     aug_pad, aug_flip = getattr(config, "AUG_SHIFT_PAD", 0), getattr(config, "AUG_FLIP", False)
     aug_actions, aug_color = getattr(config, "AUG_FLIP_ACTIONS", [1, 2]), tuple(getattr(config, k, 0.0) for k in COLOR_KEYS)
@@ -471,7 +543,8 @@ def build_helpers(config, dataset, store, model, comm, rank, world_size, log):
                         allreduce_loss=(comm.launch_loss if comm else None), allreduce_wait=(comm.wait_last if comm else None),
                         allreduce_errors=((lambda: comm.launch_errors(replay.err_all)) if comm and replay else None),
                         grad_clip_norm=clip_norm, weight_decay=weight_decay, lr_fn=lr_fn, cql_alpha=cql_alpha,
-                        target_tau=target_tau, mc_floor=mc_floor, cql_calibrated=cql_calibrated)
+                        target_tau=target_tau, mc_floor=mc_floor, cql_calibrated=cql_calibrated,
+                        iql_expectile=iql_expectile)
     walker = returns = next_row = None
     if n_step > 1 or mc_floor or cql_calibrated:
         from .nstep import successors
@@ -500,6 +573,9 @@ def build_helpers(config, dataset, store, model, comm, rank, world_size, log):
     if target_tau > 0:
         log(f"soft target updates: target <- target + {target_tau:g} * (online - target) inside every Adam launch, the target weights "
             "folded from the average in front of every update; TARGET_UPDATE_INTERVAL is unused")
+    if iql_expectile > 0:
+        log(f"implicit Q-learning: a value head V(s) fitted to Q_target(s, a_data) at expectile {iql_expectile:g}, Q(s, a_data) regressed on "
+            "r + GAMMA (1 - t) V(s') in the loss launch; the target pass runs over s; validation is unchanged")
     if cql_alpha > 0:
         log(f"conservative Q-learning: {cql_alpha:g} * (logsumexp_a Q(s, .) - Q(s, a_data)) added to the TD loss in the loss launch")
     if clip_norm > 0 or weight_decay > 0 or lr_fn is not None:
@@ -531,9 +607,17 @@ def restore_state(config, model, stepper, replay, resume_from, rank, world_size,
         model_loc = f"{config.folder}/models/sample{resume_from}.torch"
         snapshot = torch.load(model_loc, map_location=config.device)
         log(f"Loading model from: {model_loc}")
-        model.load_state_dict(snapshot["model_state_dict"])
+        has_head = getattr(stepper.net, "value_head", False) and "value_head" in snapshot
+        model.load_state_dict(OrderedDict(snapshot["model_state_dict"], **snapshot["value_head"]["state_dict"]) if has_head
+                              else snapshot["model_state_dict"])
         load_optimizer_state_dict(stepper, snapshot["optimizer_state_dict"])
         resumed_target = snapshot.get("target_state_dict")
+        if getattr(stepper.net, "value_head", False):
+            if has_head:
+                load_value_head_state(stepper, snapshot["value_head"])
+                log("implicit Q-learning: the value head and its Adam moments restored from the checkpoint")
+            else:
+                log("implicit Q-learning: the checkpoint has no value_head, the value head starts from its initialisation")
         if replay is not None:
             if "replay_state" in snapshot:
                 replay.load_state_dict(snapshot["replay_state"])
@@ -579,6 +663,8 @@ def late_scalars(stepper, returns):
         late.append(LateScalar("cql_penalty/train", stepper.cql_penalty, scaled=True))
     if returns is not None:
         late += [LateScalar("mc_floor_share/train", stepper.mc_stats[0:1], scaled=True), LateScalar("q_minus_return/train", stepper.mc_stats[1:2], scaled=True)]
+    if getattr(stepper, "iql_expectile", 0.0) > 0:  # the V loss alone, and the mean advantage of the data action
+        late += [LateScalar("iql_v_loss/train", stepper.iql_stats[0:1], scaled=True), LateScalar("iql_advantage/train", stepper.iql_stats[1:2], scaled=True)]
     return late
 
 
