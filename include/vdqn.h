@@ -255,6 +255,33 @@ int vdqn_td_loss_mc(const vdqn_td_args* a, const float* weight /* NULL ok */, fl
 int vdqn_td_loss_iql(const vdqn_td_args* a, const float* weight /* NULL = 1 */, float* err_out /* NULL ok */,
                      const float* sample_gamma /* NULL = a->gamma */, float expectile, float* stats /* f32[2], pre-zeroed, NULL ok */,
                      void* stream);
+/* Gaussian distributional Q-learning in one launch (video_dqn_amd/csrc/dist.hip; the reference's config keys DISTRIBUTIONAL,
+ * KL_BACKWARDS, LOG_SIGMA): a row of ldq columns holds the mean of the return at column M(c, a) = c * n_act + a (the Q column) and a
+ * spread parameter rho at column S(c, a) = n_cat * n_act + c * n_act + a, so 2 * n_cat * n_act <= ldq.  flags bit 0 = KL_BACKWARDS,
+ * bit 1 = LOG_SIGMA.  With a* = act[b], smin2 = sigma_min^2, w_b = weight[b] (NULL = 1), vm_bc = valid or 1, gamma_b = sample_gamma[b]
+ * (NULL = a->gamma):
+ *   var(rho) = e(rho) + smin2;  LOG_SIGMA: e = exp(2 clamp(rho, -8, 4)), de/drho = 2 e inside the clamp and exactly 0 outside;
+ *              otherwise e = softplus(rho)^2 (rho > 20: softplus = rho), de/drho = 2 softplus(rho) sigmoid(rho)
+ *   a' = first arg-max of q_after_online[b][M(c, .)];  mt = q_after_target[b][M(c, a')];  vt = var(q_after_target[b][S(c, a')])
+ *   m  = the y of vdqn_td_loss in its order: qa = mt * (1 - term); y = rew + gamma_b * qa; rect clip
+ *   g  = gamma_b * (1 - term);  v = max((g * g) * vt, smin2);  mu = q_before[b][M(c, a*)];  s2 = var(q_before[b][S(c, a*)]);  d = mu - m
+ *   bit 0 clear: L = KL(N(m, v) || N(mu, s2)) = 0.5 (log(s2 / v) + (v + d^2) / s2 - 1),  dL/dmu = d / s2,  dL/ds2 = 0.5 (s2 - v - d^2) / s2^2
+ *   bit 0 set:   L = KL(N(mu, s2) || N(m, v)) = 0.5 (log(v / s2) + (s2 + d^2) / v - 1),  dL/dmu = d / v,   dL/ds2 = 0.5 (s2 - v) / (v s2)
+ *   loss += inv_count * sum w_b vm_bc L       dq[b][M(c, a*)] = dL/dmu w_b vm_bc inv_count
+ *   dq[b][S(c, a*)] = dL/ds2 de/drho w_b vm_bc inv_count      every other column 0      (no gradient through m, v, a')
+ *   err_out[b] = sum_c |d_bc| vm_bc / n_cat                   (NULL ok; the bits vdqn_td_loss_weighted writes for the same mean columns)
+ *   stats[0] += inv_count * sum vm_bc sqrt(s2)                stats[1] += inv_count * sum vm_bc d^2 / s2     (f32[2], pre-zeroed, NULL ok)
+ * `deterministic` sums in one block in a fixed order; q_copy (the mean columns) and dq_f32 as in vdqn_td_loss.  A row whose action
+ * is outside [0, n_act) writes zeros.  Fails by name, before any launch, for a null required pointer, bad dims,
+ * 2 * n_cat * n_act > ldq, batch * ldq >= 2^31, linear != 0, loss_kind != 0 (a KL has no Huber form), unknown flag bits and a
+ * sigma_min that is not finite or outside [1e-4, 10]. */
+int vdqn_td_loss_dist(const vdqn_td_args* a, const float* weight /* NULL = 1 */, float* err_out /* NULL ok */,
+                      const float* sample_gamma /* NULL = a->gamma */, int32_t flags, float sigma_min,
+                      float* stats /* f32[2], pre-zeroed, NULL ok */, void* stream);
+/* The two moments of every (category, action) from rows in vdqn_td_loss_dist's layout: out (f32 [batch][n_cat][n_act][2], 8-byte
+ * aligned) [..][0] = the mean, [..][1] = var(rho), by the same device function as the loss.  Only bit 1 of flags is read. */
+int vdqn_dist_moments(const float* q_rows, float* out, int32_t batch, int32_t n_cat, int32_t n_act, int32_t ldq, int32_t flags,
+                      float sigma_min, void* stream);
 /* Held-out validation metrics of the same loss, forward only: the `eval_losses` list the reference reserves and never fills
  * (train_q_network.py:183-186) and its `# checkpoint and eval` (:240).  One launch adds eight sums per category into
  * acc (device f64 [n_cat][8], 8-byte aligned, ACCUMULATED into: the caller zeroes it once per validation pass).  With d, y and l(d)
@@ -426,6 +453,15 @@ int vdqn_net_create(const vdqn_net_config* cfg, vdqn_net** out);
  * action_dim * num_classes + num_classes <= 64; value_head outside {0, 1} fails. */
 int vdqn_net_create_v(const vdqn_net_config* cfg, int32_t value_head, vdqn_net** out);
 int vdqn_net_value_head(const vdqn_net* net); /* 1 when the net was created with the value head, else 0 */
+/* vdqn_net_create_v with a spread head behind the Q head (Gaussian distributional Q-learning, vdqn_net_td_forward_dist).
+ * spread_head = 0 is vdqn_net_create_v(cfg, value_head, out).  spread_head = 1: the Q layer computes 2 * action_dim * num_classes
+ * columns, the mean Q(c, a) at c * action_dim + a and the spread parameter rho(c, a) action_dim * num_classes columns behind it; the
+ * extra rows are the parameters `spread.weight` [action_dim * num_classes, in] and `spread.bias` [action_dim * num_classes],
+ * registered directly behind `<top>.weight` and `<top>.bias` with param_ids after the reference's, as `value.*` are.  Every entry
+ * that reads Q keeps reading the first action_dim * num_classes columns and leaves the spread columns of dq at 0.  Fails by name
+ * for value_head and spread_head together (out of scope), 2 * action_dim * num_classes > 64 and a flag outside {0, 1}. */
+int vdqn_net_create_d(const vdqn_net_config* cfg, int32_t value_head, int32_t spread_head, vdqn_net** out);
+int vdqn_net_spread_head(const vdqn_net* net); /* 1 when the net was created with the spread head, else 0 */
 /* The engine runs weight gradients and the target-network forward on a second, internal HIP stream (joined back
  * into the caller's stream before their results are consumed).  on = 0 serialises everything on the caller's
  * stream (used for per-kernel roofline timing, where each kernel must have the chip to itself).  Default: on
@@ -587,6 +623,12 @@ int vdqn_net_td_forward_mc(vdqn_net* net, const vdqn_step_args* a, float cql_alp
  * aug_color, aug_zoom, packed_frames and the engine's `deterministic` behave as in vdqn_net_td_forward.  Fails by name, before
  * any launch, for a net without the value head, train_on_ground_truth, linear and an expectile outside [0.5, 1). */
 int vdqn_net_td_forward_iql(vdqn_net* net, const vdqn_step_args* a, float expectile, float* iql_stats, void* stream);
+/* vdqn_net_td_forward for Gaussian distributional Q-learning on a net with the spread head (vdqn_net_create_d): the same update —
+ * the online pass over [s; s'], the target pass over s' — with vdqn_td_loss_dist as the loss launch on the three Q tensors;
+ * dist_stats (device f32[2], NULL ok) is cleared beside `loss`.  sample_weight, sample_err, sample_gamma, aug_*, packed_frames and the
+ * engine's `deterministic` behave as in vdqn_net_td_forward.  Fails by name, before any launch, for a net without the spread head,
+ * train_on_ground_truth, linear, loss_kind != 0, unknown flag bits and a sigma_min outside [1e-4, 10]. */
+int vdqn_net_td_forward_dist(vdqn_net* net, const vdqn_step_args* a, int32_t flags, float sigma_min, float* dist_stats, void* stream);
 /* One held-out batch of a validation pass (the reference's unfilled `eval_losses`, train_q_network.py:183-186, and `# checkpoint
  * and eval`, :240): the online network over [before; after] (2 * batch samples), the target network over after on the side stream,
  * then vdqn_td_eval on the two f32 Q tensors (ldq 64) into acc (device f64 [num_classes][8], accumulated into).  Forward only, both

@@ -77,7 +77,20 @@ evaluated; 0.7 is the usual setting, 0.5 fits the mean; the target pass runs ove
 logs iql_v_loss/train and iql_advantage/train, the mean of Q_target(s, a_data) - V(s); the TD branch with three action columns and
 without LINEAR; not together with CQL_ALPHA, CQL_CALIBRATED or MC_RETURN_FLOOR; composes with N_STEP, PRIORITIZED_REPLAY, AUG_*
 and TARGET_TAU; checkpoints keep the reference's keys and shapes and carry the head under a key of their own, `value_head`;
-validation is unchanged, the one-step Double-DQN metrics on the Q columns).
+validation is unchanged, the one-step Double-DQN metrics on the Q columns), DISTRIBUTIONAL / KL_BACKWARDS / LOG_SIGMA (the
+reference's keys, defaults.py:34-36, all False = off) and DIST_SIGMA_MIN (0.1; in [1e-4, 10]): Gaussian distributional Q-learning —
+the network gets a spread head, one more row of its Q layer per Q column stored as spread.weight / spread.bias, so that every
+(category, action) carries a mean (the Q column, as ever) and a variance sigma^2 + DIST_SIGMA_MIN^2 with sigma = softplus(rho), or
+exp(rho) clamped to rho in [-8, 4] under LOG_SIGMA; the loss is the KL divergence between that Gaussian at the data action and the
+Double-DQN backup's, N(r + GAMMA (1 - t) mean', max((GAMMA (1 - t))^2 var', DIST_SIGMA_MIN^2)) from the target network at the online
+arg-max of the means — KL(backup || prediction), or KL(prediction || backup) under KL_BACKWARDS; an update keeps its three forward
+passes and one backward, only the loss launch differs; avg_q_loss/train is the KL objective, dist_sigma/train the mean predicted
+sigma at the data action and dist_z2/train the mean squared standardised error (1 when calibrated); model.distribution(frames)
+returns (B, C, A, 2) = mean and variance, what the reference's visualize_value.py indexes; KL_BACKWARDS or LOG_SIGMA without
+DISTRIBUTIONAL is refused (no effect); the TD branch without LINEAR and with LOSS_KIND l2; not together with CQL_ALPHA,
+CQL_CALIBRATED, MC_RETURN_FLOOR or IQL_EXPECTILE (deliberately out of scope); composes with N_STEP, PRIORITIZED_REPLAY, AUG_*,
+TARGET_TAU, ONE_ACTION, both architectures and N ranks; checkpoints keep the reference's keys and shapes and carry the head, its
+Adam moments and under TARGET_TAU its target rows under a key of their own, `spread_head`; validation is unchanged).
 """
 from __future__ import annotations
 
@@ -225,6 +238,7 @@ def get_cfg_defaults() -> CfgNode:
     c.MC_RETURN_FLOOR = False     # True: y <- max(y, G), G the Monte-Carlo return of the sampled row along its chain (a table built on the GPU at start)
     c.CQL_CALIBRATED = False      # True: Cal-QL — the CQL penalty's logsumexp over max(Q, G); needs CQL_ALPHA > 0
     c.IQL_EXPECTILE = 0.0         # in [0.5, 1): implicit Q-learning — a value head fitted to Q_target(s, a_data) at this expectile, the bootstrap from V(s'); 0 = off
+    c.DIST_SIGMA_MIN = 0.1        # DISTRIBUTIONAL: the floor of the predicted and of the backed-up standard deviation, in [1e-4, 10]
     c.N_STEP = 1                  # 2 .. 16: n-step returns along each sampled row's chain in the logged data, folded on the GPU; 1 = off
     return c
 

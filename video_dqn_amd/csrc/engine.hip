@@ -400,10 +400,16 @@ static vdqn_td_args fill_td_args(const vdqn_net* net, const vdqn_step_args* a, c
 // vdqn_net_td_forward (cql_alpha == 0: the launches and bits it always had), vdqn_net_td_forward_cql (cql_alpha > 0) and
 // vdqn_net_td_forward_mc (mc_return != NULL: the loss launch is vdqn_td_loss_mc; NULL: nothing differs).  iql_expectile > 0
 // (vdqn_net_td_forward_iql alone, on a net with the value head): the target pass runs over the `before` half of the packed frames
-// and the loss launch is vdqn_td_loss_iql; 0: nothing differs.
+// and the loss launch is vdqn_td_loss_iql; 0: nothing differs.  dist != NULL (vdqn_net_td_forward_dist alone, on a net with the
+// spread head): the loss launch is vdqn_td_loss_dist, the target pass stays over s'; NULL: nothing differs.
+struct DistLoss {
+  int32_t flags;
+  float sigma_min;
+  float* stats;
+};
 static int td_forward_impl(vdqn_net* net, const vdqn_step_args* a, float cql_alpha, float* cql_penalty, void* stream,
                            const float* mc_return = nullptr, int32_t mc_flags = 0, float* mc_stats = nullptr, float iql_expectile = 0.f,
-                           float* iql_stats = nullptr) {
+                           float* iql_stats = nullptr, const DistLoss* dist = nullptr) {
   VDQN_CHECK(net && a, "vdqn_net_td_forward: null arg");
   VDQN_CHECK(a->params && a->bnstats && a->packed_online && a->before && a->act && a->acts_online && a->bwd && a->loss, "vdqn_net_td_forward: null buffer");
   const int B = a->batch;
@@ -471,6 +477,10 @@ static int td_forward_impl(vdqn_net* net, const vdqn_step_args* a, float cql_alp
     e = hipMemsetAsync(iql_stats, 0, 8, st);
     VDQN_CHECK(e == hipSuccess, "vdqn_net_td_forward_iql: memset failed: %s", hipGetErrorString(e));
   }
+  if (dist && dist->stats) {
+    e = hipMemsetAsync(dist->stats, 0, 8, st);
+    VDQN_CHECK(e == hipSuccess, "vdqn_net_td_forward_dist: memset failed: %s", hipGetErrorString(e));
+  }
 
   const float* qf_online = reinterpret_cast<const float*>(ao + A.qf);
   if (!gtb) {
@@ -483,7 +493,8 @@ static int td_forward_impl(vdqn_net* net, const vdqn_step_args* a, float cql_alp
     t.dtype = dt;
     t.deterministic = net->cfg.deterministic;
     t.q_copy = a->q_before;  // (the compact copy of Q(s) rides in the loss launch: no 2-D copy between the loss and the first data gradient)
-    if (iql) RC(vdqn_td_loss_iql(&t, a->sample_weight, a->sample_err, a->sample_gamma, iql_expectile, iql_stats, st));
+    if (dist) RC(vdqn_td_loss_dist(&t, a->sample_weight, a->sample_err, a->sample_gamma, dist->flags, dist->sigma_min, dist->stats, st));
+    else if (iql) RC(vdqn_td_loss_iql(&t, a->sample_weight, a->sample_err, a->sample_gamma, iql_expectile, iql_stats, st));
     else if (mc_return) RC(vdqn_td_loss_mc(&t, a->sample_weight, a->sample_err, cql_alpha, cql_alpha > 0.f ? cql_penalty : nullptr, a->sample_gamma, mc_return, mc_flags, mc_stats, st));
     else if (a->sample_gamma) RC(vdqn_td_loss_nstep(&t, a->sample_weight, a->sample_err, cql_alpha, cql_alpha > 0.f ? cql_penalty : nullptr, a->sample_gamma, st));
     else if (cql_alpha > 0.f) RC(vdqn_td_loss_cql(&t, a->sample_weight, a->sample_err, cql_alpha, cql_penalty, st));
@@ -538,6 +549,20 @@ extern "C" int vdqn_net_td_forward_iql(vdqn_net* net, const vdqn_step_args* a, f
   VDQN_CHECK(!a->linear, "vdqn_net_td_forward_iql: linear: y = r + (Qa - 0.1) is the reference's undiscounted Double-DQN target and has no V(s') form");
   VDQN_CHECK(isfinite(expectile) && expectile >= 0.5f && expectile < 1.0f, "vdqn_net_td_forward_iql: expectile %g must be in [0.5, 1)", (double)expectile);
   return td_forward_impl(net, a, 0.f, nullptr, stream, nullptr, 0, nullptr, expectile, iql_stats);
+}
+
+// vdqn_net_td_forward for Gaussian distributional Q-learning (csrc/dist.hip): everything the loss launch would refuse is refused
+// here, before the forward; then td_forward_impl with vdqn_td_loss_dist for the loss launch.
+extern "C" int vdqn_net_td_forward_dist(vdqn_net* net, const vdqn_step_args* a, int32_t flags, float sigma_min, float* dist_stats, void* stream) {
+  VDQN_CHECK(net && a, "vdqn_net_td_forward_dist: null arg");
+  VDQN_CHECK(net->spread_head, "vdqn_net_td_forward_dist: the net has no spread head (create it with vdqn_net_create_d(cfg, 0, 1, ..))");
+  VDQN_CHECK(!a->train_on_ground_truth, "vdqn_net_td_forward_dist: the ground-truth branch regresses Q(s, a) on given targets and bootstraps nothing (train_on_ground_truth)");
+  VDQN_CHECK(!a->linear, "vdqn_net_td_forward_dist: linear: y = r + (Qa - 0.1) is the reference's undiscounted Double-DQN target; a variance has no backup without a discount");
+  VDQN_CHECK(a->loss_kind == 0, "vdqn_net_td_forward_dist: loss_kind %d: the loss is a KL divergence, which has no Huber form (loss_kind must be 0)", a->loss_kind);
+  VDQN_CHECK((flags & ~3) == 0, "vdqn_net_td_forward_dist: flags 0x%x has unknown bits (bit 0 = KL_BACKWARDS, bit 1 = LOG_SIGMA)", (unsigned)flags);
+  VDQN_CHECK(isfinite(sigma_min) && sigma_min >= 1e-4f && sigma_min <= 10.0f, "vdqn_net_td_forward_dist: sigma_min %g must be in [1e-4, 10]", (double)sigma_min);
+  const DistLoss dist = {flags, sigma_min, dist_stats};
+  return td_forward_impl(net, a, 0.f, nullptr, stream, nullptr, 0, nullptr, 0.f, nullptr, &dist);
 }
 
 // One held-out batch of a validation pass (train_q_network.py:183-186 `eval_losses`, :240 `# checkpoint and eval`): the frames

@@ -94,8 +94,10 @@ Layer make_linear(const std::string& name, int out_f, int in_f, int stage, bool 
 void build_layers(vdqn_net* net) {
   const int F = net->cfg.num_frames;
   std::vector<Layer> fwd;  // forward order
-  // the value head (vdqn_net_create_v): num_classes more rows of the Q layer, registered below as value.weight / value.bias
-  const int n_value = net->value_head ? net->cfg.num_classes : 0;
+  // an extra head: more rows of the Q layer, registered below as <head>.weight / <head>.bias.  The value head
+  // (vdqn_net_create_v): num_classes rows, `value`; the spread head (vdqn_net_create_d): one row per Q column, `spread`.
+  const int n_head = net->value_head ? net->cfg.num_classes : (net->spread_head ? net->n_q() : 0);
+  const std::string head = net->value_head ? "value" : "spread";
   {
     Layer L = make_conv("resnet.conv1", "resnet.bn1", 64, 3, 7, 2, 3, 224, 2);
     L.kind = K_CONV1_S2D;
@@ -126,9 +128,9 @@ void build_layers(vdqn_net* net) {
     fwd.push_back(make_conv("features.8", "", 64, 512, 3, 1, 0, 7, 0));
     fwd.push_back(make_linear("top.0", 512, 1600 * F, 0, true));
     fwd.push_back(make_linear("top.2", 256, 512, 0, false));
-    fwd.push_back(make_linear("top.4", net->n_q() + n_value, 256, 0, false));
+    fwd.push_back(make_linear("top.4", net->n_q() + n_head, 256, 0, false));
   } else {  // :32-34: global average pool, then one Linear over the F concatenated 512-vectors
-    fwd.push_back(make_linear("top", net->n_q() + n_value, 512 * F, 0, false));
+    fwd.push_back(make_linear("top", net->n_q() + n_head, 512 * F, 0, false));
   }
 
   // store layers ordered by backward stage (stable), so each stage's gradients are one contiguous range
@@ -166,10 +168,10 @@ void build_layers(vdqn_net* net) {
     for (int i = net->layer_stage_first[st]; i < net->layer_stage_first[st] + net->layer_stage_count[st]; ++i) {
       Layer& L = net->layers[i];
       L.w_off = poff;
-      const bool q_layer = n_value > 0 && (L.name == "top.4" || L.name == "top");  // its last n_value rows are the value head's
-      if (q_layer) {  // <top>.weight {C*A, in} with value.weight {C, in} directly behind it: one contiguous [co, in] operand
-        add_param(net, L.name + ".weight", poff, {L.co - n_value, L.ci}, 0, st);
-        add_param(net, "value.weight", poff + (int64_t)(L.co - n_value) * L.ci, {n_value, L.ci}, 0, st);
+      const bool q_layer = n_head > 0 && (L.name == "top.4" || L.name == "top");  // its last n_head rows are the extra head's
+      if (q_layer) {  // <top>.weight {C*A, in} with <head>.weight {n_head, in} directly behind it: one contiguous [co, in] operand
+        add_param(net, L.name + ".weight", poff, {L.co - n_head, L.ci}, 0, st);
+        add_param(net, head + ".weight", poff + (int64_t)(L.co - n_head) * L.ci, {n_head, L.ci}, 0, st);
       } else if (L.kind == K_LINEAR || L.kind == K_LINEAR_PERM) add_param(net, L.name + ".weight", poff, {L.co, L.ci}, 0, st);
       else add_param(net, L.name + ".weight", poff, {L.co, L.ci, L.r, L.s}, 0, st);
       poff += (int64_t)L.co * L.ci * L.r * L.s;
@@ -190,8 +192,8 @@ void build_layers(vdqn_net* net) {
         soff += L.co;
       } else if (L.has_bias) {
         L.b_off = poff;
-        add_param(net, L.name + ".bias", poff, {q_layer ? L.co - n_value : L.co}, 0, st);
-        if (q_layer) add_param(net, "value.bias", poff + L.co - n_value, {n_value}, 0, st);
+        add_param(net, L.name + ".bias", poff, {q_layer ? L.co - n_head : L.co}, 0, st);
+        if (q_layer) add_param(net, head + ".bias", poff + L.co - n_head, {n_head}, 0, st);
         poff += L.co;
         poff = (poff + 3) / 4 * 4;
       }
@@ -246,9 +248,9 @@ void build_layers(vdqn_net* net) {
       order.push_back("top.weight");
       order.push_back("top.bias");
     }
-    if (n_value > 0) {  // behind the reference's ids: the reference's Adam state keeps its numbering
-      order.push_back("value.weight");
-      order.push_back("value.bias");
+    if (n_head > 0) {  // behind the reference's ids: the reference's Adam state keeps its numbering
+      order.push_back(head + ".weight");
+      order.push_back(head + ".bias");
     }
     for (auto& pi : net->params)
       for (size_t i = 0; i < order.size(); ++i)
@@ -474,7 +476,7 @@ BwdLayout bwd_layout(const vdqn_net* net, int n_samples) {
 // ---------------------------------------------------------------------------------------------------------
 // C ABI
 // ---------------------------------------------------------------------------------------------------------
-static int net_create(const vdqn_net_config* cfg, int value_head, vdqn_net** out);
+static int net_create(const vdqn_net_config* cfg, int value_head, vdqn_net** out, int spread_head = 0);
 extern "C" int vdqn_net_create(const vdqn_net_config* cfg, vdqn_net** out) { return net_create(cfg, 0, out); }
 // vdqn_net_create with num_classes state values V(c) behind the Q columns of the Q layer (implicit Q-learning, csrc/iql.hip)
 extern "C" int vdqn_net_create_v(const vdqn_net_config* cfg, int32_t value_head, vdqn_net** out) {
@@ -488,8 +490,20 @@ extern "C" int vdqn_net_create_v(const vdqn_net_config* cfg, int32_t value_head,
   return net_create(cfg, value_head, out);
 }
 extern "C" int vdqn_net_value_head(const vdqn_net* net) { return net ? net->value_head : 0; }
+// vdqn_net_create_v with one spread per Q column behind the Q columns (Gaussian distributional Q-learning, csrc/dist.hip)
+extern "C" int vdqn_net_create_d(const vdqn_net_config* cfg, int32_t value_head, int32_t spread_head, vdqn_net** out) {
+  VDQN_CHECK(spread_head == 0 || spread_head == 1, "vdqn_net_create_d: spread_head must be 0 or 1, not %d", spread_head);
+  if (!spread_head) return vdqn_net_create_v(cfg, value_head, out);
+  VDQN_CHECK(value_head == 0 || value_head == 1, "vdqn_net_create_d: value_head must be 0 or 1, not %d", value_head);
+  VDQN_CHECK(!value_head, "vdqn_net_create_d: value_head and spread_head together are out of scope (one extra head behind the Q layer)");
+  VDQN_CHECK(cfg && out, "vdqn_net_create_d: null arg");
+  VDQN_CHECK(cfg->action_dim >= 1 && cfg->num_classes >= 1 && 2 * (int64_t)cfg->action_dim * cfg->num_classes <= 64,
+             "vdqn_net_create_d: 2 * action_dim*num_classes must be in 2..64 (the means and one spread per mean share a 64-wide row)");
+  return net_create(cfg, 0, out, 1);
+}
+extern "C" int vdqn_net_spread_head(const vdqn_net* net) { return net ? net->spread_head : 0; }
 
-static int net_create(const vdqn_net_config* cfg, int value_head, vdqn_net** out) {
+static int net_create(const vdqn_net_config* cfg, int value_head, vdqn_net** out, int spread_head) {
   VDQN_CHECK(cfg && out, "vdqn_net_create: null arg");
   VDQN_CHECK(cfg->extra_capacity == 0 || cfg->extra_capacity == 1, "vdqn_net_create: extra_capacity must be 0 or 1");
   VDQN_CHECK(cfg->dtype == VDQN_F32 || cfg->dtype == VDQN_BF16 || cfg->dtype == VDQN_F32X3, "vdqn_net_create: bad dtype %d", cfg->dtype);
@@ -500,6 +514,7 @@ static int net_create(const vdqn_net_config* cfg, int value_head, vdqn_net** out
   vdqn_net* net = new vdqn_net();
   net->cfg = *cfg;
   net->value_head = value_head;
+  net->spread_head = spread_head;
   net->gemm_dtype = cfg->dtype;
   if (cfg->dtype == VDQN_F32X3) net->cfg.dtype = VDQN_F32;  // f32 layout, tensors and pointwise kernels; only the GEMMs differ
   net->esz = cfg->dtype == VDQN_BF16 ? 2 : 4;

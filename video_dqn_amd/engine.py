@@ -48,6 +48,10 @@ def _say_once(text: str) -> None:
         print(text)
 
 
+def head_kept_message(head: str) -> str:
+    return f"{head} head: the state_dict has no {head}.weight / {head}.bias, the {head} head keeps its initialisation"
+
+
 def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
     return None if t is None else t.data_ptr()
 
@@ -77,7 +81,7 @@ class NetEngine:
     """One HabitatDQNMultiAction instance on the device: flat f32 master parameters + BN statistics."""
 
     def __init__(self, action_dim=3, num_classes=5, num_frames=1, extra_capacity=True, dtype="bf16",
-                 max_batch=512, device=None, deterministic=None, value_head=False):
+                 max_batch=512, device=None, deterministic=None, value_head=False, spread_head=False):
         self.lib = _lib.load()
         # device="cpu" gives a storage-only instance (state_dict / checkpoint plumbing); every compute entry
         # point still requires the GPU and raises otherwise — there is no CPU arithmetic in this package.
@@ -99,8 +103,16 @@ class NetEngine:
         # value_head (implicit Q-learning): num_classes state values V(c) behind the Q columns of the Q layer, its extra rows the
         # parameters `value.weight` / `value.bias` (vdqn_net_create_v); False: vdqn_net_create, the same tables and bits
         self.value_head = bool(value_head)
+        # spread_head (Gaussian distributional Q-learning): one spread parameter rho(c, a) per Q column behind the Q columns, the
+        # extra rows the parameters `spread.weight` / `spread.bias` (vdqn_net_create_d)
+        self.spread_head = bool(spread_head)
+        # the extra head behind the Q layer, if any, and its parameters' names: never among the reference's keys
+        self.head = "spread" if self.spread_head else ("value" if self.value_head else None)
+        self.head_keys = (f"{self.head}.weight", f"{self.head}.bias") if self.head else ()
         h = C.c_void_p()
-        if self.value_head:
+        if self.spread_head:
+            _lib.check(self.lib.vdqn_net_create_d(C.byref(self.cfg), int(self.value_head), 1, C.byref(h)), "vdqn_net_create_d")
+        elif self.value_head:
             _lib.check(self.lib.vdqn_net_create_v(C.byref(self.cfg), 1, C.byref(h)), "vdqn_net_create_v")
         else:
             _lib.check(self.lib.vdqn_net_create(C.byref(self.cfg), C.byref(h)), "vdqn_net_create")
@@ -150,11 +162,11 @@ class NetEngine:
         """Copy every tensor the engine owns (by its reference state_dict name) from ``state_dict``."""
         with torch.no_grad():
             for name in self.slots:
-                if name.startswith("value.") and name not in state_dict:
-                    continue  # a DQN checkpoint into a value-head engine (warm start): the initialised value.* stay
+                if name in self.head_keys and name not in state_dict:
+                    continue  # a DQN checkpoint into an engine with an extra head (warm start): the initialised head stays
                 self.view(name).copy_(state_dict[name].to(torch.float32))
-        if self.value_head and not all(n in state_dict for n in ("value.weight", "value.bias")):
-            _say_once("value head: the state_dict has no value.weight / value.bias, the value head keeps its initialisation")
+        if self.head and not all(n in state_dict for n in self.head_keys):
+            _say_once(head_kept_message(self.head))
         self.mark_dirty()
 
     def mark_dirty(self):
@@ -220,6 +232,22 @@ class NetEngine:
         off = self.lib.vdqn_net_act_offset(self.handle, n_samples, b"qf")
         nq = self.num_classes * self.action_dim
         return acts[off:off + n_samples * 64 * 4].view(torch.float32).view(n_samples, 64)[:, nq:nq + self.num_classes].clone()
+
+    def dist_moments(self, n_samples: int, log_sigma: bool, sigma_min: float) -> torch.Tensor:
+        """f32 [n_samples, num_classes, action_dim, 2] = {mean, variance} of the LAST `forward(.., n_samples)` call: vdqn_dist_moments
+        over the f32 Q rows that call left in its workspace (no second pass)."""
+        self._need_gpu()
+        if not self.spread_head:
+            raise _lib.VdqnError("dist_moments: this NetEngine has no spread head (NetEngine(spread_head=True))")
+        acts = self._acts.get(n_samples)
+        if acts is None:
+            raise _lib.VdqnError(f"dist_moments: no forward over {n_samples} samples has run")
+        off = self.lib.vdqn_net_act_offset(self.handle, n_samples, b"qf")
+        out = torch.empty((n_samples, self.num_classes, self.action_dim, 2), dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.vdqn_dist_moments(acts.data_ptr() + off, out.data_ptr(), n_samples, self.num_classes, self.action_dim, 64,
+                                                  2 if log_sigma else 0, float(sigma_min), _stream()), "vdqn_dist_moments")
+        return out
 
     # ---- one model call with its own backward (torch.autograd over the module, model.py) ----------------------------
     def forward_saved(self, frames: torch.Tensor, src_kind: int, n_samples: int, packed: torch.Tensor):
@@ -333,7 +361,8 @@ class TDStepper:
                  target_update_interval: int = 8000, betas=(0.9, 0.999), eps: float = 1e-8, world_size: int = 1,
                  allreduce=None, loss_kind: str = "l2", allreduce_loss=None, allreduce_wait=None, allreduce_errors=None,
                  grad_clip_norm: float = 0.0, weight_decay: float = 0.0, lr_fn=None, cql_alpha: float = 0.0,
-                 target_tau: float = 0.0, mc_floor: bool = False, cql_calibrated: bool = False, iql_expectile: float = 0.0):
+                 target_tau: float = 0.0, mc_floor: bool = False, cql_calibrated: bool = False, iql_expectile: float = 0.0,
+                 distributional: bool = False, kl_backwards: bool = False, log_sigma: bool = False, sigma_min: float = 0.1):
         net._need_gpu()
         self.net, self.B = net, batch
         self.lib = net.lib
@@ -395,6 +424,32 @@ class TDStepper:
                 raise _lib.VdqnError("TDStepper: iql_expectile does not combine with cql_alpha, mc_floor or cql_calibrated (out of scope: "
                                      "the IQL loss launch has neither the penalty nor the return floor)")
         self.iql_expectile = iql_expectile
+        # distributional (Gaussian distributional Q-learning, csrc/dist.hip; needs NetEngine(spread_head=True)): the update is
+        # vdqn_net_td_forward_dist — the same three forward passes, the loss launch vdqn_td_loss_dist: the KL divergence between the
+        # Gaussian of Q(s, a_data) and that of the Double-DQN backup, its direction by kl_backwards, the spread's parametrisation by
+        # log_sigma, its floor sigma_min — and `dist_stats` receives this rank's share of {mean predicted sigma, mean squared
+        # standardised error}.  False: the entries above, launched as ever.
+        for key, val in (("distributional", distributional), ("kl_backwards", kl_backwards), ("log_sigma", log_sigma)):
+            if not isinstance(val, bool):
+                raise _lib.VdqnError(f"TDStepper: {key} must be a bool, not {val!r}")
+        if (kl_backwards or log_sigma) and not distributional:
+            raise _lib.VdqnError("TDStepper: kl_backwards / log_sigma have no effect without distributional")
+        if distributional:
+            sigma_min = float(sigma_min)
+            if not (1e-4 <= sigma_min <= 10.0):
+                raise _lib.VdqnError(f"TDStepper: sigma_min must be in [1e-4, 10], not {sigma_min}")
+            if not getattr(net, "spread_head", False):
+                raise _lib.VdqnError("TDStepper: distributional needs a network with the spread head (NetEngine(spread_head=True))")
+            if train_on_ground_truth or linear:
+                raise _lib.VdqnError("TDStepper: distributional applies to the TD branch without linear (train_on_ground_truth bootstraps "
+                                     "nothing; y = r + (Qa - 0.1) has no discount to back a variance up with)")
+            if loss_kind != "l2":
+                raise _lib.VdqnError(f"TDStepper: distributional with loss_kind {loss_kind!r}: the loss is a KL divergence, which has no Huber form")
+            if cql_alpha > 0 or self.mc_flags or iql_expectile > 0:
+                raise _lib.VdqnError("TDStepper: distributional does not combine with cql_alpha, mc_floor, cql_calibrated or iql_expectile "
+                                     "(out of scope: the distributional loss launch has neither the penalty, the return floor nor a value head)")
+        self.distributional, self.sigma_min = distributional, float(sigma_min)
+        self.dist_flags = (1 if kl_backwards else 0) | (2 if log_sigma else 0)
         # target_tau > 0 (soft / Polyak target updates): `target_params`, an f32 copy of the whole flat `net.params` (the trainable
         # prefix and the frozen resnet.fc tail), follows the online weights as target <- target + tau (params - target) inside every
         # Adam launch (vdqn_adam_polyak), and `packed_target` is folded from it in front of every update; target_update_interval is
@@ -442,6 +497,7 @@ class TDStepper:
             self.cql_penalty = torch.zeros(1, dtype=torch.float32, device=dev)
             self.mc_stats = torch.zeros(2, dtype=torch.float32, device=dev)
             self.iql_stats = torch.zeros(2, dtype=torch.float32, device=dev)
+            self.dist_stats = torch.zeros(2, dtype=torch.float32, device=dev)
             self.q_before = torch.zeros((batch, net.num_classes * net.action_dim), dtype=torch.float32, device=dev)
             self._ones = torch.ones((batch, net.num_classes), dtype=torch.float32, device=dev)
             if self.grad_clip_norm > 0:
@@ -574,7 +630,10 @@ class TDStepper:
             if ahead is not None and ahead[0] == self._frames_key(before, after, src_kind):
                 slot = ahead[1]  # these frames were packed during the previous update (ordered in front of `st` by its last stage)
                 a.packed_frames = self._packed_buffer(slot).data_ptr()
-            if self.iql_expectile > 0:
+            if self.distributional:
+                _lib.check(self.lib.vdqn_net_td_forward_dist(n.handle, C.byref(a), self.dist_flags, self.sigma_min, self.dist_stats.data_ptr(), st),
+                           "vdqn_net_td_forward_dist")
+            elif self.iql_expectile > 0:
                 _lib.check(self.lib.vdqn_net_td_forward_iql(n.handle, C.byref(a), self.iql_expectile, self.iql_stats.data_ptr(), st),
                            "vdqn_net_td_forward_iql")
             elif mc_return is not None:

@@ -32,9 +32,18 @@ from collections import OrderedDict
 import torch
 import torch.nn as nn
 
-from .engine import NetEngine, _say_once
+from .engine import NetEngine, _say_once, head_kept_message
 
 VALUE_KEYS = ("value.weight", "value.bias")  # the value head's parameters: never among the reference's keys
+SPREAD_KEYS = ("spread.weight", "spread.bias")  # the spread head's, likewise
+# checkpoint key of an extra head -> its parameters: what the reference's three keys leave out and a key of its own carries
+HEADS = {"value_head": VALUE_KEYS, "spread_head": SPREAD_KEYS}
+
+
+def head_of(net):
+    """(checkpoint key, parameter names) of the extra head behind `net`'s Q layer, or (None, ()) without one."""
+    name = getattr(net, "head", None)
+    return (f"{name}_head", HEADS[f"{name}_head"]) if name else (None, ())
 
 
 class _QFunction(torch.autograd.Function):
@@ -144,7 +153,8 @@ def load_torchvision_resnet18(engine: NetEngine, sd, source: str = "state_dict")
 
 class HabitatDQNMultiAction(nn.Module):
     def __init__(self, action_dim, num_classes=5, extra_capacity=False, panorama=True, num_frames=None,
-                 dtype=None, device=None, max_batch=64, pretrained_weights=None, deterministic=None, value_head=False):
+                 dtype=None, device=None, max_batch=64, pretrained_weights=None, deterministic=None, value_head=False,
+                 distributional=False, log_sigma=False, sigma_min=0.1):
         super().__init__()
         self.extra_capacity = extra_capacity
         self.num_classes = num_classes
@@ -159,8 +169,12 @@ class HabitatDQNMultiAction(nn.Module):
         # value_head (implicit Q-learning, IQL_EXPECTILE): a child `value` with `weight` [num_classes, in] and `bias` [num_classes],
         # the rows of the Q layer behind the reference's; `forward` still returns the Q values alone, `state_values` the head's
         self.value_head = bool(value_head)
+        # distributional (DISTRIBUTIONAL): a child `spread` with `weight` [num_classes * action_dim, in] and `bias`, one spread
+        # parameter per Q column; `forward` still returns the means alone in (B, C, A), `distribution` mean and variance in
+        # (B, C, A, 2) — what the reference's visualize_value.py:88-93 indexes — under log_sigma (LOG_SIGMA) and sigma_min
+        self.distributional, self.log_sigma, self.sigma_min = bool(distributional), bool(log_sigma), float(sigma_min)
         self.engine = NetEngine(action_dim, num_classes, num_frames, extra_capacity, dtype, max_batch, device, deterministic,
-                                value_head=self.value_head)
+                                value_head=self.value_head, spread_head=self.distributional)
         self._build_tree()
         _init_like_reference(self.engine)
         # models.resnet18(pretrained=True) (:11): the ImageNet weights come from a file (config key PRETRAINED_WEIGHTS, or the
@@ -232,8 +246,8 @@ class HabitatDQNMultiAction(nn.Module):
         else:  # :33-34
             self.features = nn.Sequential(*list(self.resnet.children())[:-1])
             self.top = _conv(P, "top", True)
-        if self.value_head:  # behind the reference's modules: state_dict() lists the reference's 250 keys first, then value.*
-            self.value = _conv(P, "value", True)
+        if eng.head:  # behind the reference's modules: state_dict() lists the reference's 250 keys first, then value.* / spread.*
+            setattr(self, eng.head, _conv(P, eng.head, True))
         object.__setattr__(self, "_trainable_params", [cache[s.name] for s in self._trainable_slots])
         del self._cache
         self._packed_grad = None      # packed weights incl. the data-gradient operands, for differentiable forwards
@@ -263,11 +277,12 @@ class HabitatDQNMultiAction(nn.Module):
         super()._load_from_state_dict(*a, **k)
 
     def load_state_dict(self, state_dict, strict=True):
-        if self.value_head and not all(k in state_dict for k in VALUE_KEYS):
-            # a DQN (or reference) checkpoint into a value-head model, the warm start: the value head keeps what it holds
-            _say_once("value head: the state_dict has no value.weight / value.bias, the value head keeps its initialisation")
+        keys = self.engine.head_keys
+        if keys and not all(k in state_dict for k in keys):
+            # a DQN (or reference) checkpoint into a model with an extra head, the warm start: the head keeps what it holds
+            _say_once(head_kept_message(self.engine.head))
             state_dict = OrderedDict(state_dict)
-            for k in VALUE_KEYS:
+            for k in keys:
                 state_dict.setdefault(k, self.engine.view(k).detach().clone())
         r = super().load_state_dict(state_dict, strict=strict)
         self.engine.mark_dirty()
@@ -327,6 +342,22 @@ class HabitatDQNMultiAction(nn.Module):
             self.training = was_training
         return self.engine.state_values(q.shape[0])
 
+    def distribution(self, frames):
+        """f32 [B, num_classes, action_dim, 2]: [..., 0] the mean, the bits of `forward(frames)`, and [..., 1] the variance of the
+        return of every (category, action), from one forward pass (no gradient)."""
+        if not self.distributional:
+            raise RuntimeError("distribution: the model was built without distributional=True")
+        if frames.shape[0] > self.engine.max_batch:
+            return torch.cat([self.distribution(frames[i:i + self.engine.max_batch]) for i in range(0, frames.shape[0], self.engine.max_batch)], 0)
+        was_training = self.training
+        self.training = False  # (this module's flag alone: the plain forward, 'basic' on its running statistics, nothing written)
+        try:
+            with torch.no_grad():
+                q = self.forward(frames)
+        finally:
+            self.training = was_training
+        return self.engine.dist_moments(q.shape[0], self.log_sigma, self.sigma_min)
+
 
 def build_model(config, max_batch=None):
     """train_q_network.py:36-47 (config.device selects the GPU; dtype from config.COMPUTE_DTYPE)."""
@@ -338,7 +369,10 @@ def build_model(config, max_batch=None):
                                  max_batch=max_batch or max(64, 2 * getattr(config, "BATCH_SIZE", 16)),
                                  pretrained_weights=(getattr(config, "PRETRAINED_WEIGHTS", "") or None),
                                  deterministic=(True if getattr(config, "DETERMINISTIC", False) else None),
-                                 value_head=float(getattr(config, "IQL_EXPECTILE", 0.0) or 0.0) > 0)
+                                 value_head=float(getattr(config, "IQL_EXPECTILE", 0.0) or 0.0) > 0,
+                                 distributional=bool(getattr(config, "DISTRIBUTIONAL", False)),
+                                 log_sigma=bool(getattr(config, "LOG_SIGMA", False)),
+                                 sigma_min=float(getattr(config, "DIST_SIGMA_MIN", 0.1)))
 
 
 def load_model_number(config, number, model_loc=None):
@@ -348,5 +382,8 @@ def load_model_number(config, number, model_loc=None):
         model_loc = f"{config.folder}/models/sample{number}.torch"
     snapshot = torch.load(model_loc, map_location=config.device)
     print(f"Loading model from: {model_loc}")
-    model.load_state_dict(snapshot["model_state_dict"])
+    sd = snapshot["model_state_dict"]
+    if model.distributional and "spread_head" in snapshot:  # DISTRIBUTIONAL: the head travels beside the reference's keys
+        sd = OrderedDict(sd, **snapshot["spread_head"]["state_dict"])
+    model.load_state_dict(sd)
     return model

@@ -297,6 +297,50 @@ def td_loss_iql(q_before, q_after_online, q_target_before, act, rew, term, valid
     return loss, dq, dq32, stats, err
 
 
+def dist_flags(kl_backwards=False, log_sigma=False) -> int:
+    """The `flags` word of vdqn_td_loss_dist / vdqn_dist_moments: bit 0 = KL_BACKWARDS, bit 1 = LOG_SIGMA."""
+    return (1 if kl_backwards else 0) | (2 if log_sigma else 0)
+
+
+def td_loss_dist(q_before, q_after_online, q_after_target, act, rew, term, valid=None, *, kl_backwards=False, log_sigma=False, sigma_min=0.1,
+                 weights=None, with_err=False, discount=None, n_cat=5, n_act=3, gamma=0.99, inv_count=None, clip_rect=True,
+                 out_dtype=torch.float32, loss_kind="l2", deterministic=False, linear=False, with_stats=True, with_dq32=True, with_q_copy=False,
+                 flags=None):
+    """The Gaussian distributional loss (vdqn_td_loss_dist): rows of ldq >= 2 * n_cat * n_act columns, the mean of (c, a) at c * n_act + a
+    and its spread parameter n_cat * n_act columns behind.  q_before / q_after_online: the online network at s / s'; q_after_target: the
+    target network at s'.  The loss is the KL divergence between N(mean, var)(s, act) and the Double-DQN backup's Gaussian, in the
+    direction kl_backwards chooses.  weights, discount: optional f32 [B].  flags: the raw word in place of the two booleans.
+    Returns (loss[1], dq[B, ldq] out_dtype, dq_f32 or None, stats[2] = {mean predicted sigma, mean squared standardised error} or None,
+    err[B] or None, q_copy[B, n_cat * n_act] or None)."""
+    lib = _lib.load()
+    a, loss, dq, dq32 = _td_args(q_before, q_after_online, q_after_target, act, rew, term, valid, n_cat, n_act, gamma, inv_count, clip_rect,
+                                 linear, out_dtype, loss_kind, deterministic)
+    B = q_before.shape[0]
+    if discount is not None and (discount.dtype != torch.float32 or discount.numel() != B or not discount.is_contiguous()):
+        raise ValueError(f"td_loss_dist: discount must be a contiguous f32 [{B}] device tensor")
+    if not with_dq32:
+        dq32, a.dq_f32 = None, None
+    q_copy = torch.empty((B, n_cat * n_act), dtype=torch.float32, device=loss.device) if with_q_copy else None
+    a.q_copy = _ptr(q_copy)
+    err = torch.empty(B, dtype=torch.float32, device=loss.device) if with_err else None
+    stats = torch.zeros(2, dtype=torch.float32, device=loss.device) if with_stats else None
+    _lib.check(lib.vdqn_td_loss_dist(C.byref(a), _ptr(weights), _ptr(err), _ptr(discount),
+                                     dist_flags(kl_backwards, log_sigma) if flags is None else int(flags), float(sigma_min), _ptr(stats),
+                                     _stream()), "vdqn_td_loss_dist")
+    return loss, dq, dq32, stats, err, q_copy
+
+
+def dist_moments(q_rows, *, n_cat=5, n_act=3, log_sigma=False, sigma_min=0.1, flags=None):
+    """vdqn_dist_moments: f32 [B, n_cat, n_act, 2] = {mean, variance} of every (category, action) from f32 rows [B, ldq] in
+    td_loss_dist's layout."""
+    lib = _lib.load()
+    B, ldq = q_rows.shape
+    out = torch.empty((B, n_cat, n_act, 2), dtype=torch.float32, device=q_rows.device)
+    _lib.check(lib.vdqn_dist_moments(_ptr(q_rows), _ptr(out), B, n_cat, n_act, ldq, dist_flags(False, log_sigma) if flags is None else int(flags),
+                                     float(sigma_min), _stream()), "vdqn_dist_moments")
+    return out
+
+
 def mc_returns(next_row, rew, term, *, gamma, rounds, out=None, workspace=None):
     """vdqn_mc_returns: the Monte-Carlo return table G f32 [N, n_cat] over the first 2^rounds rows of every row's chain (next_row int32
     [N]; rew / term f32 [N, n_cat], all on the device, none written).  workspace: a device byte tensor of at least

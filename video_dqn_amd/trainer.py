@@ -22,7 +22,7 @@ from .augment import COLOR_KEYS, Augmenter, jz
 from .dataset import QLearningRealDataset, SyntheticTupleDataset
 from .dist import BucketAllReduce, agree_all, broadcast_replica_state
 from .engine import TDStepper
-from .model import VALUE_KEYS, build_model
+from .model import build_model, head_of
 from .optim import lr_at, schedule_active
 from .shards import (FRAME_BYTES, Batch, DeviceFrameStore, HostFrameStream, RankShardedFrameStore, ShardDataset, collate_batches,
                      is_shard_dir)
@@ -52,13 +52,13 @@ def optimizer_state_dict(stepper: TDStepper) -> dict:
     state = {}
     if stepper.adam_step > 0:
         for s in net.slots.values():
-            if s.kind != 0 or s.name in VALUE_KEYS:  # (the value head's moments: value_head_state)
+            if s.kind != 0 or s.name in head_of(net)[1]:  # (an extra head's moments: head_state)
                 continue
             sl = slice(s.offset, s.offset + s.numel)
             state[s.param_id] = {"step": stepper.adam_step,
                                  "exp_avg": stepper.exp_avg[sl].view(s.shape).clone(),
                                  "exp_avg_sq": stepper.exp_avg_sq[sl].view(s.shape).clone()}
-    n_params = sum(1 for s in net.slots.values() if s.kind in (0, 1) and s.name not in VALUE_KEYS)
+    n_params = sum(1 for s in net.slots.values() if s.kind in (0, 1) and s.name not in head_of(net)[1])
     # (GRAD_CLIP_NORM / WEIGHT_DECAY / LR_*: `lr` is the rate of the last update, `weight_decay` the AdamW factor, and `initial_lr`
     # — the key torch's schedulers add — is there only while a schedule is active: a default-config checkpoint keeps its exact keys)
     group = {"lr": stepper.lr, "betas": tuple(stepper.betas), "eps": stepper.eps, "weight_decay": getattr(stepper, "weight_decay", 0) or 0,
@@ -71,7 +71,7 @@ def optimizer_state_dict(stepper: TDStepper) -> dict:
 
 def load_optimizer_state_dict(stepper: TDStepper, sd: dict) -> None:
     net = stepper.net
-    by_id = {s.param_id: s for s in net.slots.values() if s.kind == 0 and s.name not in VALUE_KEYS}
+    by_id = {s.param_id: s for s in net.slots.values() if s.kind == 0 and s.name not in head_of(net)[1]}
     step = 0
     with torch.no_grad():
         for pid, st in sd["state"].items():
@@ -86,37 +86,43 @@ def load_optimizer_state_dict(stepper: TDStepper, sd: dict) -> None:
 
 
 def reference_state_dict(model) -> "OrderedDict[str, torch.Tensor]":
-    """model.state_dict() without the value head's tensors: the reference's keys in the reference's shapes and order."""
-    sd = model.state_dict()  # (without a value head: the dict as it is)
-    for k in VALUE_KEYS:
+    """model.state_dict() without an extra head's tensors (value.*, spread.*): the reference's keys in the reference's shapes and
+    order."""
+    sd = model.state_dict()  # (without an extra head: the dict as it is)
+    for k in head_of(model.engine)[1]:
         sd.pop(k, None)
-    getattr(sd, "_metadata", {}).pop("value", None)
+    getattr(sd, "_metadata", {}).pop(getattr(model.engine, "head", None), None)
     return sd
 
 
-def value_head_state(stepper: TDStepper) -> dict:
-    """IQL_EXPECTILE: the value head's parameters and Adam moments, what `model_state_dict` and `optimizer_state_dict` leave out so
-    that the reference's class and its Adam load those two as they always did:
-    {"state_dict": {"value.weight", "value.bias"}, "optimizer_state": {name: {step, exp_avg, exp_avg_sq}}} (no moments before the
-    first update, as in torch)."""
+def head_state(stepper: TDStepper, with_target: bool = False) -> dict:
+    """IQL_EXPECTILE / DISTRIBUTIONAL: the extra head's parameters and Adam moments, what `model_state_dict` and
+    `optimizer_state_dict` leave out so that the reference's class and its Adam load those two as they always did:
+    {"state_dict": {"<head>.weight", "<head>.bias"}, "optimizer_state": {name: {step, exp_avg, exp_avg_sq}}} (no moments before the
+    first update, as in torch).  with_target (the spread head under TARGET_TAU > 0, whose target rows the loss reads): also
+    "target_state_dict", the head's rows of the averaged target weights."""
     net = stepper.net
     out = {"state_dict": OrderedDict(), "optimizer_state": {}}
-    for name in VALUE_KEYS:
+    if with_target:
+        out["target_state_dict"] = OrderedDict()
+    for name in head_of(net)[1]:
         s = net.slots[name]
         sl = slice(s.offset, s.offset + s.numel)
         out["state_dict"][name] = net.params[sl].view(s.shape).clone()
         if stepper.adam_step > 0:
             out["optimizer_state"][name] = {"step": stepper.adam_step, "exp_avg": stepper.exp_avg[sl].view(s.shape).clone(),
                                             "exp_avg_sq": stepper.exp_avg_sq[sl].view(s.shape).clone()}
+        if with_target:
+            out["target_state_dict"][name] = stepper.target_params[sl].view(s.shape).clone()
     return out
 
 
-def load_value_head_state(stepper: TDStepper, state: dict) -> None:
-    """A `value_head_state` into the engine's parameters and the stepper's moments (behind load_optimizer_state_dict, which sets
-    the step count)."""
+def load_head_state(stepper: TDStepper, state: dict) -> None:
+    """A `head_state` into the engine's parameters and the stepper's moments (behind load_optimizer_state_dict, which sets the step
+    count).  Its "target_state_dict", when there, goes into `stepper.target_params` through load_target_state_dict."""
     net = stepper.net
     with torch.no_grad():
-        for name in VALUE_KEYS:
+        for name in head_of(net)[1]:
             s = net.slots[name]
             sl = slice(s.offset, s.offset + s.numel)
             net.params[sl].copy_(state["state_dict"][name].to(torch.float32).reshape(-1))
@@ -127,13 +133,16 @@ def load_value_head_state(stepper: TDStepper, state: dict) -> None:
     net.mark_dirty()
 
 
+value_head_state, load_value_head_state = head_state, load_head_state  # (the names the value head came with)
+
+
 def target_state_dict(stepper: TDStepper, model) -> "OrderedDict[str, torch.Tensor]":
     """TARGET_TAU > 0: the Polyak-averaged target weights as a state_dict with the model's own keys, names and shapes — every
     parameter from `stepper.target_params` through the engine's slot table, every BatchNorm buffer as the online network holds it
     (statistics are copied, not averaged) — so the reference's class loads it as the smoothed network."""
     net = stepper.net
     out = OrderedDict()
-    for name, value in reference_state_dict(model).items():  # (the target's V rows are never read: reference keys only)
+    for name, value in reference_state_dict(model).items():  # (reference keys only: an extra head's target rows travel in head_state)
         s = net.slots.get(name)
         if s is not None and s.kind in (0, 1):
             out[name] = stepper.target_params[s.offset:s.offset + s.numel].view(s.shape).clone()
@@ -142,13 +151,17 @@ def target_state_dict(stepper: TDStepper, model) -> "OrderedDict[str, torch.Tens
     return out
 
 
-def load_target_state_dict(stepper: TDStepper, sd) -> None:
-    """The parameters of a `target_state_dict` into `stepper.target_params`, then `packed_target` folded from them again."""
+def load_target_state_dict(stepper: TDStepper, sd, head_sd=None) -> None:
+    """The parameters of a `target_state_dict` into `stepper.target_params`, then `packed_target` folded from them again.  head_sd:
+    the extra head's target rows (head_state's "target_state_dict"); without it sync_target's copy of them stays — never read for
+    value.*, the online spread.* for a checkpoint written without them."""
     net = stepper.net
     with torch.no_grad():
         for s in net.slots.values():
-            if s.kind in (0, 1) and s.name not in VALUE_KEYS:  # (value.* are not in it: sync_target's copy stays, and is never read)
+            if s.kind in (0, 1) and s.name not in head_of(net)[1]:
                 stepper.target_params[s.offset:s.offset + s.numel].copy_(sd[s.name].to(torch.float32).reshape(-1))
+            elif head_sd is not None and s.name in head_sd:
+                stepper.target_params[s.offset:s.offset + s.numel].copy_(head_sd[s.name].to(torch.float32).reshape(-1))
     with torch.cuda.device(net.device):
         net.pack_weights(stepper.packed_target, with_dgrad=False, params=stepper.target_params)
 
@@ -160,8 +173,9 @@ def save_checkpoint(path, sample_number, model, stepper, replay_state=None, targ
     ckpt = {"sample_number": sample_number,
             "model_state_dict": reference_state_dict(model),
             "optimizer_state_dict": optimizer_state_dict(stepper)}
-    if getattr(stepper.net, "value_head", False):  # IQL_EXPECTILE: the value head beside the reference's three keys, not inside them
-        ckpt["value_head"] = value_head_state(stepper)
+    head_key = head_of(stepper.net)[0]
+    if head_key:  # IQL_EXPECTILE / DISTRIBUTIONAL: the extra head beside the reference's three keys, not inside them
+        ckpt[head_key] = head_state(stepper, with_target=(head_key == "spread_head" and target_state_dict is not None))
     if replay_state is not None:
         ckpt["replay_state"] = replay_state
     if target_state_dict is not None:
@@ -299,6 +313,41 @@ def check_iql(config) -> None:
                              "return table; use one or the other")
 
 
+def check_dist(config) -> None:
+    """DISTRIBUTIONAL, KL_BACKWARDS, LOG_SIGMA, DIST_SIGMA_MIN: raise ValueError naming the key (before any device work) for a value
+    that is no bool, for a modifier without DISTRIBUTIONAL, for a floor outside [1e-4, 10] and, when the key is on, for every
+    configuration Gaussian distributional Q-learning does not cover."""
+    import math
+    for key in ("DISTRIBUTIONAL", "KL_BACKWARDS", "LOG_SIGMA"):
+        if not isinstance(getattr(config, key, False), bool):
+            raise ValueError(f"{key} must be True or False, not {getattr(config, key)!r}")
+    smin = getattr(config, "DIST_SIGMA_MIN", 0.1)
+    if isinstance(smin, bool) or not isinstance(smin, (int, float)) or not math.isfinite(smin) or not (1e-4 <= smin <= 10):
+        raise ValueError(f"DIST_SIGMA_MIN must be a number in [1e-4, 10], not {smin!r}")
+    if not getattr(config, "DISTRIBUTIONAL", False):
+        for key in ("KL_BACKWARDS", "LOG_SIGMA"):
+            if getattr(config, key, False):
+                raise ValueError(f"{key} has no effect without DISTRIBUTIONAL: it chooses the direction of the KL divergence / the "
+                                 "parametrisation of the spread of the distributional loss; set DISTRIBUTIONAL: True or leave it False")
+        return
+    if getattr(config, "TRAIN_ON_GROUND_TRUTH", False):
+        raise ValueError("DISTRIBUTIONAL needs the TD branch: TRAIN_ON_GROUND_TRUTH regresses Q(s, a) on given targets and bootstraps nothing")
+    if getattr(config, "LINEAR", False):
+        raise ValueError("DISTRIBUTIONAL does not cover LINEAR: y = r + (Qa - 0.1) has no discount to back a variance up with")
+    if str(getattr(config, "LOSS_KIND", "l2")) != "l2":
+        raise ValueError(f"DISTRIBUTIONAL with LOSS_KIND: {config.LOSS_KIND} — the loss is a KL divergence between two Gaussians, which has no Huber form")
+    if float(getattr(config, "CQL_ALPHA", 0.0)) > 0:
+        raise ValueError("DISTRIBUTIONAL with CQL_ALPHA > 0 is deliberately out of scope: the distributional loss launch has no "
+                         "conservative penalty; use one or the other")
+    for key in ("CQL_CALIBRATED", "MC_RETURN_FLOOR"):
+        if getattr(config, key, False):
+            raise ValueError(f"DISTRIBUTIONAL with {key} is deliberately out of scope: the distributional loss launch takes no "
+                             "Monte-Carlo return table; use one or the other")
+    if float(getattr(config, "IQL_EXPECTILE", 0.0) or 0.0) > 0:
+        raise ValueError("DISTRIBUTIONAL with IQL_EXPECTILE > 0 is deliberately out of scope: one extra head sits behind the Q layer, "
+                         "the value head or the spread head; use one or the other")
+
+
 def check_nstep(config, world_size: int = 1) -> None:
     """N_STEP: raise ValueError naming the key (before any device work) for a value that is not an integer in 1 .. 16 and, when it is
     above 1, for every configuration the chain walk does not cover: the ground-truth branch, LINEAR, generated tuples, a
@@ -411,6 +460,7 @@ def check_run(config, world_size: int = 1) -> None:
     check_nstep(config, world_size)
     check_mc(config)
     check_iql(config)
+    check_dist(config)
     if schedule_active(getattr(config, "LR_WARMUP_STEPS", 0), getattr(config, "LR_SCHEDULE", "constant")):
         float(config.LEARNING_RATE)  # (no check above looks at it: what is no number is refused here, not when the schedule is built)
     if getattr(config, "PRIORITIZED_REPLAY", False):
@@ -520,6 +570,7 @@ def build_helpers(config, dataset, store, model, comm, rank, world_size, log):
     mc_floor, cql_calibrated = bool(getattr(config, "MC_RETURN_FLOOR", False)), bool(getattr(config, "CQL_CALIBRATED", False))
     cql_alpha, target_tau = float(getattr(config, "CQL_ALPHA", 0.0)), float(getattr(config, "TARGET_TAU", 0.0))
     iql_expectile = float(getattr(config, "IQL_EXPECTILE", 0.0) or 0.0)
+    distributional = bool(getattr(config, "DISTRIBUTIONAL", False))
     clip_norm, weight_decay = float(getattr(config, "GRAD_CLIP_NORM", 0.0)), float(getattr(config, "WEIGHT_DECAY", 0.0))
     aug_pad, aug_flip = getattr(config, "AUG_SHIFT_PAD", 0), getattr(config, "AUG_FLIP", False)
     aug_actions, aug_color = getattr(config, "AUG_FLIP_ACTIONS", [1, 2]), tuple(getattr(config, k, 0.0) for k in COLOR_KEYS)
@@ -544,7 +595,9 @@ def build_helpers(config, dataset, store, model, comm, rank, world_size, log):
                         allreduce_errors=((lambda: comm.launch_errors(replay.err_all)) if comm and replay else None),
                         grad_clip_norm=clip_norm, weight_decay=weight_decay, lr_fn=lr_fn, cql_alpha=cql_alpha,
                         target_tau=target_tau, mc_floor=mc_floor, cql_calibrated=cql_calibrated,
-                        iql_expectile=iql_expectile)
+                        iql_expectile=iql_expectile, distributional=distributional,
+                        kl_backwards=bool(getattr(config, "KL_BACKWARDS", False)), log_sigma=bool(getattr(config, "LOG_SIGMA", False)),
+                        sigma_min=float(getattr(config, "DIST_SIGMA_MIN", 0.1)))
     walker = returns = next_row = None
     if n_step > 1 or mc_floor or cql_calibrated:
         from .nstep import successors
@@ -576,6 +629,10 @@ def build_helpers(config, dataset, store, model, comm, rank, world_size, log):
     if iql_expectile > 0:
         log(f"implicit Q-learning: a value head V(s) fitted to Q_target(s, a_data) at expectile {iql_expectile:g}, Q(s, a_data) regressed on "
             "r + GAMMA (1 - t) V(s') in the loss launch; the target pass runs over s; validation is unchanged")
+    if distributional:
+        log("distributional Q-learning: a Gaussian over the return per (category, action), a spread head behind the Q layer; the loss is KL("
+            + ("prediction || backup" if stepper.dist_flags & 1 else "backup || prediction") + ") against the Double-DQN backup's Gaussian, sigma "
+            + ("= exp(rho)" if stepper.dist_flags & 2 else "= softplus(rho)") + f" with the floor {stepper.sigma_min:g}; validation is unchanged")
     if cql_alpha > 0:
         log(f"conservative Q-learning: {cql_alpha:g} * (logsumexp_a Q(s, .) - Q(s, a_data)) added to the TD loss in the loss launch")
     if clip_norm > 0 or weight_decay > 0 or lr_fn is not None:
@@ -600,24 +657,31 @@ def build_helpers(config, dataset, store, model, comm, rank, world_size, log):
     return stepper, replay, walker, returns, augmenter
 
 
+HEAD_WORDS = {"value_head": ("implicit Q-learning", "value"), "spread_head": ("distributional Q-learning", "spread")}
+
+
 def restore_state(config, model, stepper, replay, resume_from, rank, world_size, log) -> None:
     """Resume (:192-198), bootstrap (:200-206), the replica broadcast, the :208 target sync and, behind it, the resumed soft target."""
     resumed_target = None  # TARGET_TAU: the checkpoint's averaged target weights, loaded behind the :208 sync below
+    resumed_head_target = None  # ... and the spread head's rows of them (read by the distributional loss), from the head's own key
     if resume_from > -1:  # :192-198
         model_loc = f"{config.folder}/models/sample{resume_from}.torch"
         snapshot = torch.load(model_loc, map_location=config.device)
         log(f"Loading model from: {model_loc}")
-        has_head = getattr(stepper.net, "value_head", False) and "value_head" in snapshot
-        model.load_state_dict(OrderedDict(snapshot["model_state_dict"], **snapshot["value_head"]["state_dict"]) if has_head
+        head_key = head_of(stepper.net)[0]
+        has_head = head_key is not None and head_key in snapshot
+        model.load_state_dict(OrderedDict(snapshot["model_state_dict"], **snapshot[head_key]["state_dict"]) if has_head
                               else snapshot["model_state_dict"])
         load_optimizer_state_dict(stepper, snapshot["optimizer_state_dict"])
         resumed_target = snapshot.get("target_state_dict")
-        if getattr(stepper.net, "value_head", False):
+        if head_key:
+            what, head = HEAD_WORDS[head_key]
             if has_head:
-                load_value_head_state(stepper, snapshot["value_head"])
-                log("implicit Q-learning: the value head and its Adam moments restored from the checkpoint")
+                load_head_state(stepper, snapshot[head_key])
+                resumed_head_target = snapshot[head_key].get("target_state_dict")
+                log(f"{what}: the {head} head and its Adam moments restored from the checkpoint")
             else:
-                log("implicit Q-learning: the checkpoint has no value_head, the value head starts from its initialisation")
+                log(f"{what}: the checkpoint has no {head_key}, the {head} head starts from its initialisation")
         if replay is not None:
             if "replay_state" in snapshot:
                 replay.load_state_dict(snapshot["replay_state"])
@@ -648,7 +712,7 @@ def restore_state(config, model, stepper, replay, resume_from, rank, world_size,
     stepper.sync_target()  # :208
     if stepper.target_tau > 0 and resume_from > -1:  # the averaged target of the interrupted run, in place of the copy :208 has just made
         if resumed_target is not None:
-            load_target_state_dict(stepper, resumed_target)
+            load_target_state_dict(stepper, resumed_target, resumed_head_target)
             log("soft target updates: target weights restored from the checkpoint")
         else:
             log("soft target updates: the checkpoint has no target_state_dict, the target starts from the online weights")
@@ -665,6 +729,8 @@ def late_scalars(stepper, returns):
         late += [LateScalar("mc_floor_share/train", stepper.mc_stats[0:1], scaled=True), LateScalar("q_minus_return/train", stepper.mc_stats[1:2], scaled=True)]
     if getattr(stepper, "iql_expectile", 0.0) > 0:  # the V loss alone, and the mean advantage of the data action
         late += [LateScalar("iql_v_loss/train", stepper.iql_stats[0:1], scaled=True), LateScalar("iql_advantage/train", stepper.iql_stats[1:2], scaled=True)]
+    if getattr(stepper, "distributional", False):  # the mean predicted sigma at the data action, and the mean squared standardised error
+        late += [LateScalar("dist_sigma/train", stepper.dist_stats[0:1], scaled=True), LateScalar("dist_z2/train", stepper.dist_stats[1:2], scaled=True)]
     return late
 
 
