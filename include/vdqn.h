@@ -282,6 +282,40 @@ int vdqn_td_loss_dist(const vdqn_td_args* a, const float* weight /* NULL = 1 */,
  * aligned) [..][0] = the mean, [..][1] = var(rho), by the same device function as the loss.  Only bit 1 of flags is read. */
 int vdqn_dist_moments(const float* q_rows, float* out, int32_t batch, int32_t n_cat, int32_t n_act, int32_t ldq, int32_t flags,
                       float sigma_min, void* stream);
+/* Discrete batch-constrained Q-learning in one launch (BCQ, Fujimoto et al. 2019; video_dqn_amd/csrc/bcq.hip): a row of ldq columns
+ * holds Q(c, a) at column c * n_act + a and the behaviour logit i(a) at column n_cat * n_act + a (one set per sample: the logged
+ * action is shared by all categories), so n_cat * n_act + n_act <= ldq.  With a* = act[b], w_b = weight[b] (NULL = 1), vm_bc = valid
+ * or 1, gamma_b = sample_gamma[b] (NULL = a->gamma), i = q_before[b][n_cat*n_act + .] (the logits at s) and
+ * i' = q_after_online[b][n_cat*n_act + .] (the ONLINE logits at s'):
+ *   allowed at s':  m' = max_a i'_a;  lt = (float)log((double)threshold) (threshold 0: -inf);  a is allowed iff (i'_a - m') > lt in f32
+ *                   (the arg-max of i' always is, as threshold < 1: the set is never empty, and no exponential is taken)
+ *   a' = first maximum of q_after_online[b][c*n_act + a] over the allowed a;  Qa = q_after_target[b][c*n_act + a']
+ *   y, d as vdqn_td_loss in its order: Qa *= (1 - term); y = rew + gamma_b * Qa; rect clip; d = Qb - y;  l(d), dl(d) by loss_kind
+ *   behaviour loss, per sample (not per category, no valid mask): m = max_a i_a;  S = sum_a expf(i_a - m)
+ *     ce_b = logf(S) + (m - i_{a*});  reg_b = (sum_a i_a^2) / n_act;  L_B = bc_weight * (ce_b + logit_reg * reg_b)
+ *     dL_B/di_a = bc_weight * (expf(i_a - m) / S - [a == a*] + logit_reg * 2 i_a / n_act)
+ *   loss += inv_count * sum_bc w_b vm_bc l(d_bc) + n_cat * inv_count * sum_b w_b L_B      (the TD terms are means over B*C with
+ *           inv_count = 1 / (n_cat * global batch); the behaviour terms are means over B, hence the factor n_cat * inv_count)
+ *   dq[b][c*n_act + a*] = dl(d) w_b vm_bc inv_count      dq[b][n_cat*n_act + a] = dL_B/di_a w_b n_cat inv_count      every other column 0
+ *   (no gradient through i', a' or y)             err_out[b] = sum_c |d_bc| vm_bc / n_cat   (priorities follow the TD error alone)
+ *   stats[0] += n_cat * inv_count * sum_b ce_b                              (the unweighted mean cross-entropy)
+ *   stats[1] += inv_count * sum_bc vm_bc [a' != the free arg-max]           (the share of targets the constraint changes)
+ *   stats[2] += n_cat * inv_count * sum_b [first arg-max of i == a*]        (behaviour accuracy)
+ * With threshold 0 every action is allowed: the taken-action columns of dq and err_out are then vdqn_td_loss_weighted's bits
+ * (vdqn_td_loss_nstep's with sample_gamma).  `deterministic` sums in one block in a fixed order; q_copy and dq_f32 as in
+ * vdqn_td_loss.  A row whose action is outside [0, n_act) writes zeros and adds nothing.  Fails by name, before any launch, for a
+ * null required pointer, use_valid without valid, bad dims, n_act < 2, n_cat * n_act + n_act > ldq, batch * ldq >= 2^31, a dtype
+ * other than F32 / BF16, loss_kind outside {0, 1}, linear != 0, a threshold that is not finite or outside [0, 1), a bc_weight that is
+ * not finite or <= 0 and a logit_reg that is not finite or < 0. */
+int vdqn_td_loss_bcq(const vdqn_td_args* a, const float* weight /* NULL = 1 */, float* err_out /* NULL ok */,
+                     const float* sample_gamma /* NULL = a->gamma */, float threshold, float bc_weight, float logit_reg,
+                     float* stats /* f32[3], pre-zeroed, NULL ok */, void* stream);
+/* The constrained read-out of rows in vdqn_td_loss_bcq's layout, by the same allowed-set device function as the loss:
+ * q_out[b][c][a] = q_rows[b][c*n_act + a], or -inf where action a is not allowed by the row's own logits (its arg-max over a is the
+ * BCQ policy); prob_out[b][a] (NULL ok) = the softmax of the logits.  Fails by name for a null q_rows / q_out, bad dims, n_act < 2,
+ * n_cat * n_act + n_act > ldq, batch * ldq >= 2^31 and a threshold that is not finite or outside [0, 1). */
+int vdqn_bcq_constrain(const float* q_rows, float* q_out /* [batch][C][A] */, float* prob_out /* [batch][A], NULL ok */,
+                       int32_t batch, int32_t n_cat, int32_t n_act, int32_t ldq, float threshold, void* stream);
 /* Held-out validation metrics of the same loss, forward only: the `eval_losses` list the reference reserves and never fills
  * (train_q_network.py:183-186) and its `# checkpoint and eval` (:240).  One launch adds eight sums per category into
  * acc (device f64 [n_cat][8], 8-byte aligned, ACCUMULATED into: the caller zeroes it once per validation pass).  With d, y and l(d)
@@ -462,6 +496,16 @@ int vdqn_net_value_head(const vdqn_net* net); /* 1 when the net was created with
  * for value_head and spread_head together (out of scope), 2 * action_dim * num_classes > 64 and a flag outside {0, 1}. */
 int vdqn_net_create_d(const vdqn_net_config* cfg, int32_t value_head, int32_t spread_head, vdqn_net** out);
 int vdqn_net_spread_head(const vdqn_net* net); /* 1 when the net was created with the spread head, else 0 */
+/* vdqn_net_create_d with a policy head behind the Q head (discrete batch-constrained Q-learning, vdqn_net_td_forward_bcq).
+ * policy_head = 0 is vdqn_net_create_d(cfg, value_head, spread_head, out): the same tables and bits.  policy_head = 1: the Q layer
+ * computes action_dim * num_classes + action_dim columns, Q(c, a) at c * action_dim + a as ever and the behaviour logit i(a) at
+ * action_dim * num_classes + a; the extra rows are the parameters `policy.weight` [action_dim, in] and `policy.bias` [action_dim],
+ * registered directly behind `<top>.weight` and `<top>.bias` with param_ids after the reference's, as `value.*` and `spread.*` are.
+ * Every entry that reads Q keeps reading the first action_dim * num_classes columns and leaves the logit columns of dq at 0.
+ * Fails by name for policy_head together with value_head or spread_head (out of scope), action_dim < 2,
+ * action_dim * num_classes + action_dim > 64 and a flag outside {0, 1}. */
+int vdqn_net_create_p(const vdqn_net_config* cfg, int32_t value_head, int32_t spread_head, int32_t policy_head, vdqn_net** out);
+int vdqn_net_policy_head(const vdqn_net* net); /* 1 when the net was created with the policy head, else 0 */
 /* The engine runs weight gradients and the target-network forward on a second, internal HIP stream (joined back
  * into the caller's stream before their results are consumed).  on = 0 serialises everything on the caller's
  * stream (used for per-kernel roofline timing, where each kernel must have the chip to itself).  Default: on
@@ -629,6 +673,14 @@ int vdqn_net_td_forward_iql(vdqn_net* net, const vdqn_step_args* a, float expect
  * engine's `deterministic` behave as in vdqn_net_td_forward.  Fails by name, before any launch, for a net without the spread head,
  * train_on_ground_truth, linear, loss_kind != 0, unknown flag bits and a sigma_min outside [1e-4, 10]. */
 int vdqn_net_td_forward_dist(vdqn_net* net, const vdqn_step_args* a, int32_t flags, float sigma_min, float* dist_stats, void* stream);
+/* vdqn_net_td_forward for discrete batch-constrained Q-learning on a net with the policy head (vdqn_net_create_p): the same update —
+ * the online pass over [s; s'], the target pass over s' — with vdqn_td_loss_bcq as the loss launch on the three Q tensors (the
+ * logits it reads are the online pass's, at s and at s'); bcq_stats (device f32[3], NULL ok) is cleared beside `loss`.
+ * sample_weight, sample_err, sample_gamma, aug_*, packed_frames and the engine's `deterministic` behave as in vdqn_net_td_forward.
+ * Fails by name, before any launch, for a net without the policy head, train_on_ground_truth, linear, a threshold outside [0, 1), a
+ * bc_weight that is not finite or <= 0 and a logit_reg that is not finite or < 0. */
+int vdqn_net_td_forward_bcq(vdqn_net* net, const vdqn_step_args* a, float threshold, float bc_weight, float logit_reg, float* bcq_stats,
+                            void* stream);
 /* One held-out batch of a validation pass (the reference's unfilled `eval_losses`, train_q_network.py:183-186, and `# checkpoint
  * and eval`, :240): the online network over [before; after] (2 * batch samples), the target network over after on the side stream,
  * then vdqn_td_eval on the two f32 Q tensors (ldq 64) into acc (device f64 [num_classes][8], accumulated into).  Forward only, both

@@ -172,6 +172,11 @@ _SIGS = {
     "vdqn_net_create_d": (C.c_int, [C.POINTER(NetConfig), c_i32, c_i32, C.POINTER(c_vp)]),
     "vdqn_net_spread_head": (C.c_int, [c_vp]),
     "vdqn_net_td_forward_dist": (C.c_int, [c_vp, C.POINTER(StepArgs), c_i32, c_f32, c_vp, c_vp]),
+    "vdqn_td_loss_bcq": (C.c_int, [C.POINTER(TdArgs), c_vp, c_vp, c_vp, c_f32, c_f32, c_f32, c_vp, c_vp]),
+    "vdqn_bcq_constrain": (C.c_int, [c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_f32, c_vp]),
+    "vdqn_net_create_p": (C.c_int, [C.POINTER(NetConfig), c_i32, c_i32, c_i32, C.POINTER(c_vp)]),
+    "vdqn_net_policy_head": (C.c_int, [c_vp]),
+    "vdqn_net_td_forward_bcq": (C.c_int, [c_vp, C.POINTER(StepArgs), c_f32, c_f32, c_f32, c_vp, c_vp]),
 }
 COMM_UID_BYTES = 128
 EXPORTS = tuple(_SIGS)

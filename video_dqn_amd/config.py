@@ -90,7 +90,21 @@ returns (B, C, A, 2) = mean and variance, what the reference's visualize_value.p
 DISTRIBUTIONAL is refused (no effect); the TD branch without LINEAR and with LOSS_KIND l2; not together with CQL_ALPHA,
 CQL_CALIBRATED, MC_RETURN_FLOOR or IQL_EXPECTILE (deliberately out of scope); composes with N_STEP, PRIORITIZED_REPLAY, AUG_*,
 TARGET_TAU, ONE_ACTION, both architectures and N ranks; checkpoints keep the reference's keys and shapes and carry the head, its
-Adam moments and under TARGET_TAU its target rows under a key of their own, `spread_head`; validation is unchanged).
+Adam moments and under TARGET_TAU its target rows under a key of their own, `spread_head`; validation is unchanged),
+BCQ_THRESHOLD (-1.0 = off; tau in [0, 1), 0.3 in the paper), BCQ_BC_WEIGHT (1.0; > 0) and BCQ_LOGIT_REG (0.01; >= 0): discrete
+batch-constrained Q-learning (BCQ, Fujimoto et al. 2019) — the network gets a policy head, one more row of its Q layer per action
+stored as policy.weight / policy.bias, whose logits i(a) are fitted to the logged action by cross-entropy (weight BCQ_BC_WEIGHT,
+plus BCQ_LOGIT_REG times the mean squared logit), and the Double-DQN target's arg-max at s' runs only over the actions with
+pi_b(a | s') / max_a' pi_b(a' | s') > tau under the online head; 0.0 trains the head and constrains nothing, values near 1 clone the
+behaviour with a learned value; an update keeps its three forward passes and one backward, only the loss launch differs;
+bcq_bc_loss/train is the mean cross-entropy, bcq_constrained_share/train the share of targets whose action the constraint changed
+and bcq_accuracy/train how often the head's arg-max is the logged action; model.behaviour(frames) returns the probabilities,
+model.constrained_q(frames, tau) the Q values with the disallowed actions at -inf; BCQ_BC_WEIGHT or BCQ_LOGIT_REG away from their
+defaults without BCQ_THRESHOLD is refused (no effect); the TD branch without LINEAR, VALUE_LEARNING and ONE_ACTION; not together
+with CQL_ALPHA, CQL_CALIBRATED, MC_RETURN_FLOOR, IQL_EXPECTILE or DISTRIBUTIONAL (deliberately out of scope); composes with N_STEP,
+PRIORITIZED_REPLAY, AUG_* (AUG_FLIP exchanges the action labels before the loss, so the behaviour target follows it), TARGET_TAU,
+LOSS_KIND huber, both architectures and N ranks; checkpoints keep the reference's keys and shapes and carry the head and its Adam
+moments under a key of their own, `policy_head`; validation is unchanged).
 """
 from __future__ import annotations
 
@@ -239,6 +253,9 @@ def get_cfg_defaults() -> CfgNode:
     c.CQL_CALIBRATED = False      # True: Cal-QL — the CQL penalty's logsumexp over max(Q, G); needs CQL_ALPHA > 0
     c.IQL_EXPECTILE = 0.0         # in [0.5, 1): implicit Q-learning — a value head fitted to Q_target(s, a_data) at this expectile, the bootstrap from V(s'); 0 = off
     c.DIST_SIGMA_MIN = 0.1        # DISTRIBUTIONAL: the floor of the predicted and of the backed-up standard deviation, in [1e-4, 10]
+    c.BCQ_THRESHOLD = -1.0        # in [0, 1): discrete BCQ — the target's arg-max only over actions with pi_b(a|s') / max pi_b > this, pi_b a policy head fitted to the logged actions; 0 = head on, nothing constrained; -1 = off
+    c.BCQ_BC_WEIGHT = 1.0         # BCQ_THRESHOLD: the weight of the behaviour head's cross-entropy in the loss, > 0
+    c.BCQ_LOGIT_REG = 0.01        # BCQ_THRESHOLD: the weight of the mean squared behaviour logit (Fujimoto's regulariser), >= 0
     c.N_STEP = 1                  # 2 .. 16: n-step returns along each sampled row's chain in the logged data, folded on the GPU; 1 = off
     return c
 

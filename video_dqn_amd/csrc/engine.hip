@@ -401,15 +401,20 @@ static vdqn_td_args fill_td_args(const vdqn_net* net, const vdqn_step_args* a, c
 // vdqn_net_td_forward_mc (mc_return != NULL: the loss launch is vdqn_td_loss_mc; NULL: nothing differs).  iql_expectile > 0
 // (vdqn_net_td_forward_iql alone, on a net with the value head): the target pass runs over the `before` half of the packed frames
 // and the loss launch is vdqn_td_loss_iql; 0: nothing differs.  dist != NULL (vdqn_net_td_forward_dist alone, on a net with the
-// spread head): the loss launch is vdqn_td_loss_dist, the target pass stays over s'; NULL: nothing differs.
+// spread head): the loss launch is vdqn_td_loss_dist, the target pass stays over s'; NULL: nothing differs.  bcq != NULL
+// (vdqn_net_td_forward_bcq alone, on a net with the policy head): the loss launch is vdqn_td_loss_bcq; NULL: nothing differs.
 struct DistLoss {
   int32_t flags;
   float sigma_min;
   float* stats;
 };
+struct BcqLoss {
+  float threshold, bc_weight, logit_reg;
+  float* stats;
+};
 static int td_forward_impl(vdqn_net* net, const vdqn_step_args* a, float cql_alpha, float* cql_penalty, void* stream,
                            const float* mc_return = nullptr, int32_t mc_flags = 0, float* mc_stats = nullptr, float iql_expectile = 0.f,
-                           float* iql_stats = nullptr, const DistLoss* dist = nullptr) {
+                           float* iql_stats = nullptr, const DistLoss* dist = nullptr, const BcqLoss* bcq = nullptr) {
   VDQN_CHECK(net && a, "vdqn_net_td_forward: null arg");
   VDQN_CHECK(a->params && a->bnstats && a->packed_online && a->before && a->act && a->acts_online && a->bwd && a->loss, "vdqn_net_td_forward: null buffer");
   const int B = a->batch;
@@ -481,6 +486,10 @@ static int td_forward_impl(vdqn_net* net, const vdqn_step_args* a, float cql_alp
     e = hipMemsetAsync(dist->stats, 0, 8, st);
     VDQN_CHECK(e == hipSuccess, "vdqn_net_td_forward_dist: memset failed: %s", hipGetErrorString(e));
   }
+  if (bcq && bcq->stats) {
+    e = hipMemsetAsync(bcq->stats, 0, 12, st);
+    VDQN_CHECK(e == hipSuccess, "vdqn_net_td_forward_bcq: memset failed: %s", hipGetErrorString(e));
+  }
 
   const float* qf_online = reinterpret_cast<const float*>(ao + A.qf);
   if (!gtb) {
@@ -493,7 +502,8 @@ static int td_forward_impl(vdqn_net* net, const vdqn_step_args* a, float cql_alp
     t.dtype = dt;
     t.deterministic = net->cfg.deterministic;
     t.q_copy = a->q_before;  // (the compact copy of Q(s) rides in the loss launch: no 2-D copy between the loss and the first data gradient)
-    if (dist) RC(vdqn_td_loss_dist(&t, a->sample_weight, a->sample_err, a->sample_gamma, dist->flags, dist->sigma_min, dist->stats, st));
+    if (bcq) RC(vdqn_td_loss_bcq(&t, a->sample_weight, a->sample_err, a->sample_gamma, bcq->threshold, bcq->bc_weight, bcq->logit_reg, bcq->stats, st));
+    else if (dist) RC(vdqn_td_loss_dist(&t, a->sample_weight, a->sample_err, a->sample_gamma, dist->flags, dist->sigma_min, dist->stats, st));
     else if (iql) RC(vdqn_td_loss_iql(&t, a->sample_weight, a->sample_err, a->sample_gamma, iql_expectile, iql_stats, st));
     else if (mc_return) RC(vdqn_td_loss_mc(&t, a->sample_weight, a->sample_err, cql_alpha, cql_alpha > 0.f ? cql_penalty : nullptr, a->sample_gamma, mc_return, mc_flags, mc_stats, st));
     else if (a->sample_gamma) RC(vdqn_td_loss_nstep(&t, a->sample_weight, a->sample_err, cql_alpha, cql_alpha > 0.f ? cql_penalty : nullptr, a->sample_gamma, st));
@@ -563,6 +573,22 @@ extern "C" int vdqn_net_td_forward_dist(vdqn_net* net, const vdqn_step_args* a, 
   VDQN_CHECK(isfinite(sigma_min) && sigma_min >= 1e-4f && sigma_min <= 10.0f, "vdqn_net_td_forward_dist: sigma_min %g must be in [1e-4, 10]", (double)sigma_min);
   const DistLoss dist = {flags, sigma_min, dist_stats};
   return td_forward_impl(net, a, 0.f, nullptr, stream, nullptr, 0, nullptr, 0.f, nullptr, &dist);
+}
+
+// vdqn_net_td_forward for discrete batch-constrained Q-learning (csrc/bcq.hip): everything the loss launch would refuse is refused
+// here, before the forward; then td_forward_impl with vdqn_td_loss_bcq for the loss launch.
+extern "C" int vdqn_net_td_forward_bcq(vdqn_net* net, const vdqn_step_args* a, float threshold, float bc_weight, float logit_reg, float* bcq_stats,
+                                       void* stream) {
+  VDQN_CHECK(net && a, "vdqn_net_td_forward_bcq: null arg");
+  VDQN_CHECK(net->policy_head, "vdqn_net_td_forward_bcq: the net has no policy head (create it with vdqn_net_create_p(cfg, 0, 0, 1, ..))");
+  VDQN_CHECK(!a->train_on_ground_truth, "vdqn_net_td_forward_bcq: the ground-truth branch regresses Q(s, a) on given targets and bootstraps nothing (train_on_ground_truth)");
+  VDQN_CHECK(!a->linear, "vdqn_net_td_forward_bcq: linear: y = r + (Qa - 0.1) is the reference's undiscounted Double-DQN target; the constrained target is not defined for it");
+  VDQN_CHECK(a->loss_kind == 0 || a->loss_kind == 1, "vdqn_net_td_forward_bcq: loss_kind %d (0 = half squared error, 1 = Huber)", a->loss_kind);
+  VDQN_CHECK(isfinite(threshold) && threshold >= 0.0f && threshold < 1.0f, "vdqn_net_td_forward_bcq: threshold %g must be in [0, 1)", (double)threshold);
+  VDQN_CHECK(isfinite(bc_weight) && bc_weight > 0.0f, "vdqn_net_td_forward_bcq: bc_weight %g must be finite and > 0", (double)bc_weight);
+  VDQN_CHECK(isfinite(logit_reg) && logit_reg >= 0.0f, "vdqn_net_td_forward_bcq: logit_reg %g must be finite and >= 0", (double)logit_reg);
+  const BcqLoss bcq = {threshold, bc_weight, logit_reg, bcq_stats};
+  return td_forward_impl(net, a, 0.f, nullptr, stream, nullptr, 0, nullptr, 0.f, nullptr, nullptr, &bcq);
 }
 
 // One held-out batch of a validation pass (train_q_network.py:183-186 `eval_losses`, :240 `# checkpoint and eval`): the frames

@@ -91,6 +91,7 @@ struct vdqn_net {
   vdqn_net_config cfg;  // cfg.dtype is the STORAGE dtype: VDQN_F32 for a VDQN_F32X3 engine (every pointwise entry takes that)
   int value_head = 0;   // 1: the Q layer also computes num_classes state values V(c) behind its Q columns (vdqn_net_create_v)
   int spread_head = 0;  // 1: the Q layer also computes one spread rho(c, a) per Q column, at column n_q() + c * action_dim + a (vdqn_net_create_d)
+  int policy_head = 0;  // 1: the Q layer also computes one behaviour logit i(a) per action, at column n_q() + a (vdqn_net_create_p)
   int gemm_dtype;       // dtype of the GEMM calls (convolutions, linear layers, weight gradients, stem): the requested one
   int esz;  // bytes per activation element
   std::vector<Layer> layers;

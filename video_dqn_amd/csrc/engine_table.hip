@@ -95,9 +95,19 @@ void build_layers(vdqn_net* net) {
   const int F = net->cfg.num_frames;
   std::vector<Layer> fwd;  // forward order
   // an extra head: more rows of the Q layer, registered below as <head>.weight / <head>.bias.  The value head
-  // (vdqn_net_create_v): num_classes rows, `value`; the spread head (vdqn_net_create_d): one row per Q column, `spread`.
-  const int n_head = net->value_head ? net->cfg.num_classes : (net->spread_head ? net->n_q() : 0);
-  const std::string head = net->value_head ? "value" : "spread";
+  // (vdqn_net_create_v): num_classes rows, `value`; the spread head (vdqn_net_create_d): one row per Q column, `spread`; the
+  // policy head (vdqn_net_create_p): one behaviour logit per action, `policy`.  At most one of them is set.
+  const struct {
+    int on, rows;
+    const char* name;
+  } heads[] = {{net->value_head, net->cfg.num_classes, "value"}, {net->spread_head, net->n_q(), "spread"}, {net->policy_head, net->cfg.action_dim, "policy"}};
+  int n_head = 0;
+  std::string head;
+  for (const auto& h : heads)
+    if (h.on) {
+      n_head = h.rows;
+      head = h.name;
+    }
   {
     Layer L = make_conv("resnet.conv1", "resnet.bn1", 64, 3, 7, 2, 3, 224, 2);
     L.kind = K_CONV1_S2D;
@@ -476,7 +486,7 @@ BwdLayout bwd_layout(const vdqn_net* net, int n_samples) {
 // ---------------------------------------------------------------------------------------------------------
 // C ABI
 // ---------------------------------------------------------------------------------------------------------
-static int net_create(const vdqn_net_config* cfg, int value_head, vdqn_net** out, int spread_head = 0);
+static int net_create(const vdqn_net_config* cfg, int value_head, vdqn_net** out, int spread_head = 0, int policy_head = 0);
 extern "C" int vdqn_net_create(const vdqn_net_config* cfg, vdqn_net** out) { return net_create(cfg, 0, out); }
 // vdqn_net_create with num_classes state values V(c) behind the Q columns of the Q layer (implicit Q-learning, csrc/iql.hip)
 extern "C" int vdqn_net_create_v(const vdqn_net_config* cfg, int32_t value_head, vdqn_net** out) {
@@ -502,8 +512,22 @@ extern "C" int vdqn_net_create_d(const vdqn_net_config* cfg, int32_t value_head,
   return net_create(cfg, 0, out, 1);
 }
 extern "C" int vdqn_net_spread_head(const vdqn_net* net) { return net ? net->spread_head : 0; }
+// vdqn_net_create_d with one behaviour logit per action behind the Q columns (discrete batch-constrained Q-learning, csrc/bcq.hip)
+extern "C" int vdqn_net_create_p(const vdqn_net_config* cfg, int32_t value_head, int32_t spread_head, int32_t policy_head, vdqn_net** out) {
+  VDQN_CHECK(policy_head == 0 || policy_head == 1, "vdqn_net_create_p: policy_head must be 0 or 1, not %d", policy_head);
+  if (!policy_head) return vdqn_net_create_d(cfg, value_head, spread_head, out);
+  VDQN_CHECK((value_head == 0 || value_head == 1) && (spread_head == 0 || spread_head == 1),
+             "vdqn_net_create_p: value_head and spread_head must be 0 or 1, not %d and %d", value_head, spread_head);
+  VDQN_CHECK(!value_head && !spread_head, "vdqn_net_create_p: policy_head together with value_head or spread_head is out of scope (one extra head behind the Q layer)");
+  VDQN_CHECK(cfg && out, "vdqn_net_create_p: null arg");
+  VDQN_CHECK(cfg->action_dim >= 2, "vdqn_net_create_p: action_dim is %d: with one action there is nothing to constrain (policy_head needs action_dim >= 2)", cfg->action_dim);
+  VDQN_CHECK(cfg->num_classes >= 1 && (int64_t)cfg->action_dim * cfg->num_classes + cfg->action_dim <= 64,
+             "vdqn_net_create_p: action_dim*num_classes + action_dim must be in 1..64 (the Q columns and one behaviour logit per action share a 64-wide row)");
+  return net_create(cfg, 0, out, 0, 1);
+}
+extern "C" int vdqn_net_policy_head(const vdqn_net* net) { return net ? net->policy_head : 0; }
 
-static int net_create(const vdqn_net_config* cfg, int value_head, vdqn_net** out, int spread_head) {
+static int net_create(const vdqn_net_config* cfg, int value_head, vdqn_net** out, int spread_head, int policy_head) {
   VDQN_CHECK(cfg && out, "vdqn_net_create: null arg");
   VDQN_CHECK(cfg->extra_capacity == 0 || cfg->extra_capacity == 1, "vdqn_net_create: extra_capacity must be 0 or 1");
   VDQN_CHECK(cfg->dtype == VDQN_F32 || cfg->dtype == VDQN_BF16 || cfg->dtype == VDQN_F32X3, "vdqn_net_create: bad dtype %d", cfg->dtype);
@@ -515,6 +539,7 @@ static int net_create(const vdqn_net_config* cfg, int value_head, vdqn_net** out
   net->cfg = *cfg;
   net->value_head = value_head;
   net->spread_head = spread_head;
+  net->policy_head = policy_head;
   net->gemm_dtype = cfg->dtype;
   if (cfg->dtype == VDQN_F32X3) net->cfg.dtype = VDQN_F32;  // f32 layout, tensors and pointwise kernels; only the GEMMs differ
   net->esz = cfg->dtype == VDQN_BF16 ? 2 : 4;

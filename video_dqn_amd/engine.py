@@ -10,6 +10,7 @@ from __future__ import annotations
 
 import contextlib
 import ctypes as C
+import math
 import os
 from collections import OrderedDict
 from dataclasses import dataclass
@@ -81,7 +82,7 @@ class NetEngine:
     """One HabitatDQNMultiAction instance on the device: flat f32 master parameters + BN statistics."""
 
     def __init__(self, action_dim=3, num_classes=5, num_frames=1, extra_capacity=True, dtype="bf16",
-                 max_batch=512, device=None, deterministic=None, value_head=False, spread_head=False):
+                 max_batch=512, device=None, deterministic=None, value_head=False, spread_head=False, policy_head=False):
         self.lib = _lib.load()
         # device="cpu" gives a storage-only instance (state_dict / checkpoint plumbing); every compute entry
         # point still requires the GPU and raises otherwise — there is no CPU arithmetic in this package.
@@ -107,10 +108,15 @@ class NetEngine:
         # extra rows the parameters `spread.weight` / `spread.bias` (vdqn_net_create_d)
         self.spread_head = bool(spread_head)
         # the extra head behind the Q layer, if any, and its parameters' names: never among the reference's keys
-        self.head = "spread" if self.spread_head else ("value" if self.value_head else None)
+        # policy_head (discrete batch-constrained Q-learning): one behaviour logit i(a) per action behind the Q columns, the extra
+        # rows the parameters `policy.weight` / `policy.bias` (vdqn_net_create_p)
+        self.policy_head = bool(policy_head)
+        self.head = "policy" if self.policy_head else ("spread" if self.spread_head else ("value" if self.value_head else None))
         self.head_keys = (f"{self.head}.weight", f"{self.head}.bias") if self.head else ()
         h = C.c_void_p()
-        if self.spread_head:
+        if self.policy_head:
+            _lib.check(self.lib.vdqn_net_create_p(C.byref(self.cfg), int(self.value_head), int(self.spread_head), 1, C.byref(h)), "vdqn_net_create_p")
+        elif self.spread_head:
             _lib.check(self.lib.vdqn_net_create_d(C.byref(self.cfg), int(self.value_head), 1, C.byref(h)), "vdqn_net_create_d")
         elif self.value_head:
             _lib.check(self.lib.vdqn_net_create_v(C.byref(self.cfg), 1, C.byref(h)), "vdqn_net_create_v")
@@ -249,6 +255,24 @@ class NetEngine:
                                                   2 if log_sigma else 0, float(sigma_min), _stream()), "vdqn_dist_moments")
         return out
 
+    def bcq_constrain(self, n_samples: int, threshold: float):
+        """(q f32 [n_samples, num_classes, action_dim] with the actions the behaviour head disallows at -inf, prob f32 [n_samples,
+        action_dim] = the behaviour probabilities) of the LAST `forward(.., n_samples)` call: vdqn_bcq_constrain over the f32 Q rows
+        that call left in its workspace (no second pass)."""
+        self._need_gpu()
+        if not self.policy_head:
+            raise _lib.VdqnError("bcq_constrain: this NetEngine has no policy head (NetEngine(policy_head=True))")
+        acts = self._acts.get(n_samples)
+        if acts is None:
+            raise _lib.VdqnError(f"bcq_constrain: no forward over {n_samples} samples has run")
+        off = self.lib.vdqn_net_act_offset(self.handle, n_samples, b"qf")
+        q = torch.empty((n_samples, self.num_classes, self.action_dim), dtype=torch.float32, device=self.device)
+        prob = torch.empty((n_samples, self.action_dim), dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.vdqn_bcq_constrain(acts.data_ptr() + off, q.data_ptr(), prob.data_ptr(), n_samples, self.num_classes,
+                                                   self.action_dim, 64, float(threshold), _stream()), "vdqn_bcq_constrain")
+        return q, prob
+
     # ---- one model call with its own backward (torch.autograd over the module, model.py) ----------------------------
     def forward_saved(self, frames: torch.Tensor, src_kind: int, n_samples: int, packed: torch.Tensor):
         """`vdqn_net_forward` into a workspace of its own that the caller keeps for `backward_from_dq`: -> (q, acts).
@@ -362,7 +386,8 @@ class TDStepper:
                  allreduce=None, loss_kind: str = "l2", allreduce_loss=None, allreduce_wait=None, allreduce_errors=None,
                  grad_clip_norm: float = 0.0, weight_decay: float = 0.0, lr_fn=None, cql_alpha: float = 0.0,
                  target_tau: float = 0.0, mc_floor: bool = False, cql_calibrated: bool = False, iql_expectile: float = 0.0,
-                 distributional: bool = False, kl_backwards: bool = False, log_sigma: bool = False, sigma_min: float = 0.1):
+                 distributional: bool = False, kl_backwards: bool = False, log_sigma: bool = False, sigma_min: float = 0.1,
+                 bcq_threshold: float = -1.0, bcq_bc_weight: float = 1.0, bcq_logit_reg: float = 0.01):
         net._need_gpu()
         self.net, self.B = net, batch
         self.lib = net.lib
@@ -450,6 +475,31 @@ class TDStepper:
                                      "(out of scope: the distributional loss launch has neither the penalty, the return floor nor a value head)")
         self.distributional, self.sigma_min = distributional, float(sigma_min)
         self.dist_flags = (1 if kl_backwards else 0) | (2 if log_sigma else 0)
+        # bcq_threshold in [0, 1) (discrete batch-constrained Q-learning, csrc/bcq.hip; needs NetEngine(policy_head=True)): the update
+        # is vdqn_net_td_forward_bcq — the same three forward passes, the loss launch vdqn_td_loss_bcq: the Double-DQN arg-max at s'
+        # only over the actions whose behaviour probability is above bcq_threshold times the largest, plus bcq_bc_weight times the
+        # cross-entropy of the behaviour logits at the logged action (and bcq_logit_reg times their mean square) — and `bcq_stats`
+        # receives this rank's share of {mean cross-entropy, share of targets the constraint changes, behaviour accuracy}.
+        # -1 (off): the entries above, launched as ever.
+        bcq_threshold, bcq_bc_weight, bcq_logit_reg = float(bcq_threshold), float(bcq_bc_weight), float(bcq_logit_reg)
+        self.bcq = bcq_threshold != -1.0
+        if not (bcq_threshold == -1.0 or 0.0 <= bcq_threshold < 1.0):
+            raise _lib.VdqnError(f"TDStepper: bcq_threshold must be -1 (off) or in [0, 1), not {bcq_threshold}")
+        if not (math.isfinite(bcq_bc_weight) and bcq_bc_weight > 0):
+            raise _lib.VdqnError(f"TDStepper: bcq_bc_weight must be finite and > 0, not {bcq_bc_weight}")
+        if not (math.isfinite(bcq_logit_reg) and bcq_logit_reg >= 0):
+            raise _lib.VdqnError(f"TDStepper: bcq_logit_reg must be finite and >= 0, not {bcq_logit_reg}")
+        if self.bcq:
+            if not getattr(net, "policy_head", False):
+                raise _lib.VdqnError("TDStepper: bcq_threshold needs a network with the policy head (NetEngine(policy_head=True))")
+            if train_on_ground_truth or linear:
+                raise _lib.VdqnError("TDStepper: bcq_threshold applies to the TD branch without linear (train_on_ground_truth bootstraps "
+                                     "nothing; the constrained target is not defined for y = r + (Qa - 0.1))")
+            if cql_alpha > 0 or self.mc_flags or iql_expectile > 0 or distributional:
+                raise _lib.VdqnError("TDStepper: bcq_threshold does not combine with cql_alpha, mc_floor, cql_calibrated, iql_expectile or "
+                                     "distributional (out of scope: one extra head sits behind the Q layer, and the BCQ loss launch has "
+                                     "neither the penalty nor the return floor)")
+        self.bcq_threshold, self.bcq_bc_weight, self.bcq_logit_reg = bcq_threshold, bcq_bc_weight, bcq_logit_reg
         # target_tau > 0 (soft / Polyak target updates): `target_params`, an f32 copy of the whole flat `net.params` (the trainable
         # prefix and the frozen resnet.fc tail), follows the online weights as target <- target + tau (params - target) inside every
         # Adam launch (vdqn_adam_polyak), and `packed_target` is folded from it in front of every update; target_update_interval is
@@ -498,6 +548,7 @@ class TDStepper:
             self.mc_stats = torch.zeros(2, dtype=torch.float32, device=dev)
             self.iql_stats = torch.zeros(2, dtype=torch.float32, device=dev)
             self.dist_stats = torch.zeros(2, dtype=torch.float32, device=dev)
+            self.bcq_stats = torch.zeros(3, dtype=torch.float32, device=dev)
             self.q_before = torch.zeros((batch, net.num_classes * net.action_dim), dtype=torch.float32, device=dev)
             self._ones = torch.ones((batch, net.num_classes), dtype=torch.float32, device=dev)
             if self.grad_clip_norm > 0:
@@ -630,7 +681,10 @@ class TDStepper:
             if ahead is not None and ahead[0] == self._frames_key(before, after, src_kind):
                 slot = ahead[1]  # these frames were packed during the previous update (ordered in front of `st` by its last stage)
                 a.packed_frames = self._packed_buffer(slot).data_ptr()
-            if self.distributional:
+            if self.bcq:
+                _lib.check(self.lib.vdqn_net_td_forward_bcq(n.handle, C.byref(a), self.bcq_threshold, self.bcq_bc_weight, self.bcq_logit_reg,
+                                                            self.bcq_stats.data_ptr(), st), "vdqn_net_td_forward_bcq")
+            elif self.distributional:
                 _lib.check(self.lib.vdqn_net_td_forward_dist(n.handle, C.byref(a), self.dist_flags, self.sigma_min, self.dist_stats.data_ptr(), st),
                            "vdqn_net_td_forward_dist")
             elif self.iql_expectile > 0:

@@ -37,7 +37,8 @@ from .engine import NetEngine, _say_once, head_kept_message
 VALUE_KEYS = ("value.weight", "value.bias")  # the value head's parameters: never among the reference's keys
 SPREAD_KEYS = ("spread.weight", "spread.bias")  # the spread head's, likewise
 # checkpoint key of an extra head -> its parameters: what the reference's three keys leave out and a key of its own carries
-HEADS = {"value_head": VALUE_KEYS, "spread_head": SPREAD_KEYS}
+POLICY_KEYS = ("policy.weight", "policy.bias")  # the policy (behaviour) head's, likewise
+HEADS = {"value_head": VALUE_KEYS, "spread_head": SPREAD_KEYS, "policy_head": POLICY_KEYS}
 
 
 def head_of(net):
@@ -154,7 +155,7 @@ def load_torchvision_resnet18(engine: NetEngine, sd, source: str = "state_dict")
 class HabitatDQNMultiAction(nn.Module):
     def __init__(self, action_dim, num_classes=5, extra_capacity=False, panorama=True, num_frames=None,
                  dtype=None, device=None, max_batch=64, pretrained_weights=None, deterministic=None, value_head=False,
-                 distributional=False, log_sigma=False, sigma_min=0.1):
+                 distributional=False, log_sigma=False, sigma_min=0.1, policy_head=False):
         super().__init__()
         self.extra_capacity = extra_capacity
         self.num_classes = num_classes
@@ -173,8 +174,12 @@ class HabitatDQNMultiAction(nn.Module):
         # parameter per Q column; `forward` still returns the means alone in (B, C, A), `distribution` mean and variance in
         # (B, C, A, 2) — what the reference's visualize_value.py:88-93 indexes — under log_sigma (LOG_SIGMA) and sigma_min
         self.distributional, self.log_sigma, self.sigma_min = bool(distributional), bool(log_sigma), float(sigma_min)
+        # policy_head (BCQ_THRESHOLD): a child `policy` with `weight` [action_dim, in] and `bias` [action_dim], the behaviour logits;
+        # `forward` still returns the Q values alone, `behaviour` the head's probabilities and `constrained_q` the Q values with
+        # the actions the head finds implausible at -inf
+        self.policy_head = bool(policy_head)
         self.engine = NetEngine(action_dim, num_classes, num_frames, extra_capacity, dtype, max_batch, device, deterministic,
-                                value_head=self.value_head, spread_head=self.distributional)
+                                value_head=self.value_head, spread_head=self.distributional, policy_head=self.policy_head)
         self._build_tree()
         _init_like_reference(self.engine)
         # models.resnet18(pretrained=True) (:11): the ImageNet weights come from a file (config key PRETRAINED_WEIGHTS, or the
@@ -246,7 +251,7 @@ class HabitatDQNMultiAction(nn.Module):
         else:  # :33-34
             self.features = nn.Sequential(*list(self.resnet.children())[:-1])
             self.top = _conv(P, "top", True)
-        if eng.head:  # behind the reference's modules: state_dict() lists the reference's 250 keys first, then value.* / spread.*
+        if eng.head:  # behind the reference's modules: state_dict() lists the reference's 250 keys first, then value.* / spread.* / policy.*
             setattr(self, eng.head, _conv(P, eng.head, True))
         object.__setattr__(self, "_trainable_params", [cache[s.name] for s in self._trainable_slots])
         del self._cache
@@ -358,6 +363,31 @@ class HabitatDQNMultiAction(nn.Module):
             self.training = was_training
         return self.engine.dist_moments(q.shape[0], self.log_sigma, self.sigma_min)
 
+    def _bcq_readout(self, frames, threshold):
+        if not self.policy_head:
+            raise RuntimeError("constrained_q / behaviour: the model was built without policy_head=True")
+        if frames.shape[0] > self.engine.max_batch:
+            parts = [self._bcq_readout(frames[i:i + self.engine.max_batch], threshold) for i in range(0, frames.shape[0], self.engine.max_batch)]
+            return torch.cat([p[0] for p in parts], 0), torch.cat([p[1] for p in parts], 0)
+        was_training = self.training
+        self.training = False  # (this module's flag alone: the plain forward, 'basic' on its running statistics, nothing written)
+        try:
+            with torch.no_grad():
+                q = self.forward(frames)
+        finally:
+            self.training = was_training
+        return self.engine.bcq_constrain(q.shape[0], threshold)
+
+    def constrained_q(self, frames, threshold):
+        """f32 [B, num_classes, action_dim]: the bits of `forward(frames)`, with -inf at every action whose behaviour probability is
+        not above `threshold` (in [0, 1)) times the largest one of its sample; from one forward pass (no gradient).  Its
+        `argmax(-1)` is the BCQ policy."""
+        return self._bcq_readout(frames, threshold)[0]
+
+    def behaviour(self, frames):
+        """f32 [B, action_dim]: the behaviour head's probabilities pi_b(a | s), from one forward pass (no gradient)."""
+        return self._bcq_readout(frames, 0.0)[1]
+
 
 def build_model(config, max_batch=None):
     """train_q_network.py:36-47 (config.device selects the GPU; dtype from config.COMPUTE_DTYPE)."""
@@ -372,7 +402,8 @@ def build_model(config, max_batch=None):
                                  value_head=float(getattr(config, "IQL_EXPECTILE", 0.0) or 0.0) > 0,
                                  distributional=bool(getattr(config, "DISTRIBUTIONAL", False)),
                                  log_sigma=bool(getattr(config, "LOG_SIGMA", False)),
-                                 sigma_min=float(getattr(config, "DIST_SIGMA_MIN", 0.1)))
+                                 sigma_min=float(getattr(config, "DIST_SIGMA_MIN", 0.1)),
+                                 policy_head=float(getattr(config, "BCQ_THRESHOLD", -1.0)) >= 0)
 
 
 def load_model_number(config, number, model_loc=None):

@@ -341,6 +341,43 @@ def dist_moments(q_rows, *, n_cat=5, n_act=3, log_sigma=False, sigma_min=0.1, fl
     return out
 
 
+def td_loss_bcq(q_before, q_after_online, q_after_target, act, rew, term, valid=None, *, threshold=0.3, bc_weight=1.0, logit_reg=0.01,
+                weights=None, with_err=False, discount=None, n_cat=5, n_act=3, gamma=0.99, inv_count=None, clip_rect=True,
+                out_dtype=torch.float32, loss_kind="l2", deterministic=False, linear=False, with_stats=True, with_dq32=True, with_q_copy=False):
+    """The discrete BCQ loss (vdqn_td_loss_bcq): rows of ldq >= n_cat * n_act + n_act columns, Q(c, a) at c * n_act + a and the behaviour
+    logit of action a at n_cat * n_act + a.  q_before / q_after_online: the online network at s / s'; q_after_target: the target network
+    at s'.  The Double-DQN target's arg-max runs over the actions whose online logit at s' is within log(threshold) of the largest; the
+    logits at s are fitted to `act` by cross-entropy.  weights, discount: optional f32 [B].
+    Returns (loss[1], dq[B, ldq] out_dtype, dq_f32 or None, stats[3] = {mean cross-entropy, share of targets the constraint changes,
+    behaviour accuracy} or None, err[B] or None, q_copy[B, n_cat * n_act] or None)."""
+    lib = _lib.load()
+    a, loss, dq, dq32 = _td_args(q_before, q_after_online, q_after_target, act, rew, term, valid, n_cat, n_act, gamma, inv_count, clip_rect,
+                                 linear, out_dtype, loss_kind, deterministic)
+    B = q_before.shape[0]
+    if discount is not None and (discount.dtype != torch.float32 or discount.numel() != B or not discount.is_contiguous()):
+        raise ValueError(f"td_loss_bcq: discount must be a contiguous f32 [{B}] device tensor")
+    if not with_dq32:
+        dq32, a.dq_f32 = None, None
+    q_copy = torch.empty((B, n_cat * n_act), dtype=torch.float32, device=loss.device) if with_q_copy else None
+    a.q_copy = _ptr(q_copy)
+    err = torch.empty(B, dtype=torch.float32, device=loss.device) if with_err else None
+    stats = torch.zeros(3, dtype=torch.float32, device=loss.device) if with_stats else None
+    _lib.check(lib.vdqn_td_loss_bcq(C.byref(a), _ptr(weights), _ptr(err), _ptr(discount), float(threshold), float(bc_weight), float(logit_reg),
+                                    _ptr(stats), _stream()), "vdqn_td_loss_bcq")
+    return loss, dq, dq32, stats, err, q_copy
+
+
+def bcq_constrain(q_rows, threshold, *, n_cat=5, n_act=3, with_prob=True):
+    """vdqn_bcq_constrain: (q f32 [B, n_cat, n_act] with the disallowed actions at -inf, prob f32 [B, n_act] or None) from f32 rows
+    [B, ldq] in td_loss_bcq's layout."""
+    lib = _lib.load()
+    B, ldq = q_rows.shape
+    q = torch.empty((B, n_cat, n_act), dtype=torch.float32, device=q_rows.device)
+    prob = torch.empty((B, n_act), dtype=torch.float32, device=q_rows.device) if with_prob else None
+    _lib.check(lib.vdqn_bcq_constrain(_ptr(q_rows), _ptr(q), _ptr(prob), B, n_cat, n_act, ldq, float(threshold), _stream()), "vdqn_bcq_constrain")
+    return q, prob
+
+
 def mc_returns(next_row, rew, term, *, gamma, rounds, out=None, workspace=None):
     """vdqn_mc_returns: the Monte-Carlo return table G f32 [N, n_cat] over the first 2^rounds rows of every row's chain (next_row int32
     [N]; rew / term f32 [N, n_cat], all on the device, none written).  workspace: a device byte tensor of at least

@@ -348,6 +348,53 @@ def check_dist(config) -> None:
                          "the value head or the spread head; use one or the other")
 
 
+def check_bcq(config) -> None:
+    """BCQ_THRESHOLD, BCQ_BC_WEIGHT, BCQ_LOGIT_REG: raise ValueError naming the key (before any device work) for a threshold outside
+    {-1} and [0, 1), a weight that is not finite and > 0, a regulariser that is not finite and >= 0, either of the two away from
+    its default while BCQ is off and, when it is on, for every configuration discrete BCQ does not cover."""
+    import math
+
+    def number(key, default):
+        v = getattr(config, key, default)
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v):
+            raise ValueError(f"{key} must be a finite number, not {v!r}")
+        return float(v)
+    tau, bc_weight, logit_reg = number("BCQ_THRESHOLD", -1.0), number("BCQ_BC_WEIGHT", 1.0), number("BCQ_LOGIT_REG", 0.01)
+    if not (tau == -1.0 or 0.0 <= tau < 1.0):
+        raise ValueError(f"BCQ_THRESHOLD must be -1 (off) or in [0, 1), not {tau!r}: an action is allowed when pi_b(a|s') / max pi_b > BCQ_THRESHOLD")
+    if not bc_weight > 0:
+        raise ValueError(f"BCQ_BC_WEIGHT must be > 0, not {bc_weight!r}")
+    if not logit_reg >= 0:
+        raise ValueError(f"BCQ_LOGIT_REG must be >= 0, not {logit_reg!r}")
+    if tau < 0:
+        for key, val, default in (("BCQ_BC_WEIGHT", bc_weight, 1.0), ("BCQ_LOGIT_REG", logit_reg, 0.01)):
+            if val != default:
+                raise ValueError(f"{key} has no effect without BCQ_THRESHOLD: it weighs a term of the behaviour head's loss; set "
+                                 f"BCQ_THRESHOLD in [0, 1) or leave {key} at {default}")
+        return
+    if getattr(config, "TRAIN_ON_GROUND_TRUTH", False):
+        raise ValueError("BCQ_THRESHOLD needs the TD branch: TRAIN_ON_GROUND_TRUTH regresses Q(s, a) on given targets and bootstraps nothing")
+    if getattr(config, "LINEAR", False):
+        raise ValueError("BCQ_THRESHOLD does not cover LINEAR: the constrained target is not defined for y = r + (Qa - 0.1)")
+    for key in ("VALUE_LEARNING", "ONE_ACTION"):
+        if getattr(config, key, False):
+            raise ValueError(f"BCQ_THRESHOLD needs more than one action: {key} builds a network with one action column, and with "
+                             "one action there is nothing to constrain")
+    if float(getattr(config, "CQL_ALPHA", 0.0)) > 0:
+        raise ValueError("BCQ_THRESHOLD with CQL_ALPHA > 0 is deliberately out of scope: the BCQ loss launch has no conservative "
+                         "penalty; use one or the other")
+    for key in ("CQL_CALIBRATED", "MC_RETURN_FLOOR"):
+        if getattr(config, key, False):
+            raise ValueError(f"BCQ_THRESHOLD with {key} is deliberately out of scope: the BCQ loss launch takes no Monte-Carlo return "
+                             "table; use one or the other")
+    if float(getattr(config, "IQL_EXPECTILE", 0.0) or 0.0) > 0:
+        raise ValueError("BCQ_THRESHOLD with IQL_EXPECTILE > 0 is deliberately out of scope: one extra head sits behind the Q layer, "
+                         "the value head or the policy head; use one or the other")
+    if getattr(config, "DISTRIBUTIONAL", False):
+        raise ValueError("BCQ_THRESHOLD with DISTRIBUTIONAL is deliberately out of scope: one extra head sits behind the Q layer, "
+                         "the spread head or the policy head; use one or the other")
+
+
 def check_nstep(config, world_size: int = 1) -> None:
     """N_STEP: raise ValueError naming the key (before any device work) for a value that is not an integer in 1 .. 16 and, when it is
     above 1, for every configuration the chain walk does not cover: the ground-truth branch, LINEAR, generated tuples, a
@@ -461,6 +508,7 @@ def check_run(config, world_size: int = 1) -> None:
     check_mc(config)
     check_iql(config)
     check_dist(config)
+    check_bcq(config)
     if schedule_active(getattr(config, "LR_WARMUP_STEPS", 0), getattr(config, "LR_SCHEDULE", "constant")):
         float(config.LEARNING_RATE)  # (no check above looks at it: what is no number is refused here, not when the schedule is built)
     if getattr(config, "PRIORITIZED_REPLAY", False):
@@ -571,6 +619,7 @@ def build_helpers(config, dataset, store, model, comm, rank, world_size, log):
     cql_alpha, target_tau = float(getattr(config, "CQL_ALPHA", 0.0)), float(getattr(config, "TARGET_TAU", 0.0))
     iql_expectile = float(getattr(config, "IQL_EXPECTILE", 0.0) or 0.0)
     distributional = bool(getattr(config, "DISTRIBUTIONAL", False))
+    bcq_threshold = float(getattr(config, "BCQ_THRESHOLD", -1.0))
     clip_norm, weight_decay = float(getattr(config, "GRAD_CLIP_NORM", 0.0)), float(getattr(config, "WEIGHT_DECAY", 0.0))
     aug_pad, aug_flip = getattr(config, "AUG_SHIFT_PAD", 0), getattr(config, "AUG_FLIP", False)
     aug_actions, aug_color = getattr(config, "AUG_FLIP_ACTIONS", [1, 2]), tuple(getattr(config, k, 0.0) for k in COLOR_KEYS)
@@ -597,7 +646,8 @@ def build_helpers(config, dataset, store, model, comm, rank, world_size, log):
                         target_tau=target_tau, mc_floor=mc_floor, cql_calibrated=cql_calibrated,
                         iql_expectile=iql_expectile, distributional=distributional,
                         kl_backwards=bool(getattr(config, "KL_BACKWARDS", False)), log_sigma=bool(getattr(config, "LOG_SIGMA", False)),
-                        sigma_min=float(getattr(config, "DIST_SIGMA_MIN", 0.1)))
+                        sigma_min=float(getattr(config, "DIST_SIGMA_MIN", 0.1)), bcq_threshold=bcq_threshold,
+                        bcq_bc_weight=float(getattr(config, "BCQ_BC_WEIGHT", 1.0)), bcq_logit_reg=float(getattr(config, "BCQ_LOGIT_REG", 0.01)))
     walker = returns = next_row = None
     if n_step > 1 or mc_floor or cql_calibrated:
         from .nstep import successors
@@ -633,6 +683,10 @@ def build_helpers(config, dataset, store, model, comm, rank, world_size, log):
         log("distributional Q-learning: a Gaussian over the return per (category, action), a spread head behind the Q layer; the loss is KL("
             + ("prediction || backup" if stepper.dist_flags & 1 else "backup || prediction") + ") against the Double-DQN backup's Gaussian, sigma "
             + ("= exp(rho)" if stepper.dist_flags & 2 else "= softplus(rho)") + f" with the floor {stepper.sigma_min:g}; validation is unchanged")
+    if bcq_threshold >= 0:
+        log(f"batch-constrained Q-learning: a policy head behind the Q layer fitted to the logged actions (weight {stepper.bcq_bc_weight:g}, "
+            f"logit regulariser {stepper.bcq_logit_reg:g}); the target's arg-max at s' runs over the actions with pi_b / max pi_b > "
+            f"{bcq_threshold:g} under the online head; validation is unchanged")
     if cql_alpha > 0:
         log(f"conservative Q-learning: {cql_alpha:g} * (logsumexp_a Q(s, .) - Q(s, a_data)) added to the TD loss in the loss launch")
     if clip_norm > 0 or weight_decay > 0 or lr_fn is not None:
@@ -657,7 +711,8 @@ def build_helpers(config, dataset, store, model, comm, rank, world_size, log):
     return stepper, replay, walker, returns, augmenter
 
 
-HEAD_WORDS = {"value_head": ("implicit Q-learning", "value"), "spread_head": ("distributional Q-learning", "spread")}
+HEAD_WORDS = {"value_head": ("implicit Q-learning", "value"), "spread_head": ("distributional Q-learning", "spread"),
+              "policy_head": ("batch-constrained Q-learning", "policy")}
 
 
 def restore_state(config, model, stepper, replay, resume_from, rank, world_size, log) -> None:
@@ -731,6 +786,10 @@ def late_scalars(stepper, returns):
         late += [LateScalar("iql_v_loss/train", stepper.iql_stats[0:1], scaled=True), LateScalar("iql_advantage/train", stepper.iql_stats[1:2], scaled=True)]
     if getattr(stepper, "distributional", False):  # the mean predicted sigma at the data action, and the mean squared standardised error
         late += [LateScalar("dist_sigma/train", stepper.dist_stats[0:1], scaled=True), LateScalar("dist_z2/train", stepper.dist_stats[1:2], scaled=True)]
+    if getattr(stepper, "bcq", False):  # the behaviour head's cross-entropy, the share of targets the constraint changed, its accuracy
+        late += [LateScalar("bcq_bc_loss/train", stepper.bcq_stats[0:1], scaled=True),
+                 LateScalar("bcq_constrained_share/train", stepper.bcq_stats[1:2], scaled=True),
+                 LateScalar("bcq_accuracy/train", stepper.bcq_stats[2:3], scaled=True)]
     return late
 
 
