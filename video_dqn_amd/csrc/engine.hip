@@ -397,24 +397,51 @@ static vdqn_td_args fill_td_args(const vdqn_net* net, const vdqn_step_args* a, c
   return t;
 }
 
-// vdqn_net_td_forward (cql_alpha == 0: the launches and bits it always had), vdqn_net_td_forward_cql (cql_alpha > 0) and
-// vdqn_net_td_forward_mc (mc_return != NULL: the loss launch is vdqn_td_loss_mc; NULL: nothing differs).  iql_expectile > 0
-// (vdqn_net_td_forward_iql alone, on a net with the value head): the target pass runs over the `before` half of the packed frames
-// and the loss launch is vdqn_td_loss_iql; 0: nothing differs.  dist != NULL (vdqn_net_td_forward_dist alone, on a net with the
-// spread head): the loss launch is vdqn_td_loss_dist, the target pass stays over s'; NULL: nothing differs.  bcq != NULL
-// (vdqn_net_td_forward_bcq alone, on a net with the policy head): the loss launch is vdqn_td_loss_bcq; NULL: nothing differs.
-struct DistLoss {
-  int32_t flags;
-  float sigma_min;
+// What one TD update's loss is, filled by the exported vdqn_net_td_forward* entry that was called.  `algo` picks the loss launch
+// and indexes kAlgos; the TD family (plain, weighted, n-step, CQL, Monte-Carlo floor / Cal-QL) reads the four fields marked so, each
+// head algorithm its own scalars.  `stats` (n_stats floats, NULL ok) and cql_penalty (cql_alpha > 0) are cleared before the launch.
+namespace {
+enum LossAlgo { ALGO_TD = 0, ALGO_IQL, ALGO_DIST, ALGO_BCQ };
+struct LossSpec {
+  LossAlgo algo;
   float* stats;
+  int n_stats;
+  float cql_alpha; float* cql_penalty; const float* mc_return; int32_t mc_flags;  // the TD family
+  float iql_expectile;
+  int32_t dist_flags; float dist_sigma_min;
+  float bcq_threshold, bcq_bc_weight, bcq_logit_reg;
 };
-struct BcqLoss {
-  float threshold, bc_weight, logit_reg;
-  float* stats;
+// One row per LossAlgo; the TD family's is that of vdqn_net_td_forward_mc, its one entry with statistics and row refusals.
+struct AlgoRow {
+  const char* entry;
+  Head head;                     // the head the net must carry
+  const char *no_gt, *no_linear;  // why train_on_ground_truth and linear are refused
+  int n_stats;
+  bool target_over_before;  // the target pass reads s, not s'
 };
-static int td_forward_impl(vdqn_net* net, const vdqn_step_args* a, float cql_alpha, float* cql_penalty, void* stream,
-                           const float* mc_return = nullptr, int32_t mc_flags = 0, float* mc_stats = nullptr, float iql_expectile = 0.f,
-                           float* iql_stats = nullptr, const DistLoss* dist = nullptr, const BcqLoss* bcq = nullptr) {
+const char kNoBootstrap[] = "the ground-truth branch regresses Q(s, a) on given targets and bootstraps nothing (train_on_ground_truth)";
+const AlgoRow kAlgos[] = {
+    {"vdqn_net_td_forward_mc", HEAD_NONE, "mc_return is given, but the ground-truth branch has no target to floor and no penalty to calibrate (train_on_ground_truth)",
+     "mc_return is given with linear: y = r + (Qa - 0.1) has no discount, and a discounted return bounds nothing of it", 2, false},
+    {"vdqn_net_td_forward_iql", HEAD_VALUE, kNoBootstrap,
+     "linear: y = r + (Qa - 0.1) is the reference's undiscounted Double-DQN target and has no V(s') form", 2, true},
+    {"vdqn_net_td_forward_dist", HEAD_SPREAD, kNoBootstrap,
+     "linear: y = r + (Qa - 0.1) is the reference's undiscounted Double-DQN target; a variance has no backup without a discount", 2, false},
+    {"vdqn_net_td_forward_bcq", HEAD_POLICY, kNoBootstrap,
+     "linear: y = r + (Qa - 0.1) is the reference's undiscounted Double-DQN target; the constrained target is not defined for it", 3, false},
+};
+LossSpec loss_spec(LossAlgo algo, float* stats) { return {algo, stats, kAlgos[algo].n_stats}; }  // (the rest zero)
+// the refusals every row shares: the net lacks the row's head, the ground-truth branch, linear
+int refuse_by_row(const AlgoRow& r, const vdqn_net* net, const vdqn_step_args* a) {
+  static const char* const head_word[] = {"", "value", "spread", "policy"};
+  static const char* const head_create[] = {"", "vdqn_net_create_v(cfg, 1, ..)", "vdqn_net_create_d(cfg, 0, 1, ..)", "vdqn_net_create_p(cfg, 0, 0, 1, ..)"};
+  VDQN_CHECK(r.head == HEAD_NONE || net->head == r.head, "%s: the net has no %s head (create it with %s)", r.entry, head_word[r.head], head_create[r.head]);
+  VDQN_CHECK(!a->train_on_ground_truth, "%s: %s", r.entry, r.no_gt);
+  VDQN_CHECK(!a->linear, "%s: %s", r.entry, r.no_linear);
+  return VDQN_OK;
+}
+
+int td_forward_impl(vdqn_net* net, const vdqn_step_args* a, const LossSpec& spec, void* stream) {
   VDQN_CHECK(net && a, "vdqn_net_td_forward: null arg");
   VDQN_CHECK(a->params && a->bnstats && a->packed_online && a->before && a->act && a->acts_online && a->bwd && a->loss, "vdqn_net_td_forward: null buffer");
   const int B = a->batch;
@@ -435,7 +462,7 @@ static int td_forward_impl(vdqn_net* net, const vdqn_step_args* a, float cql_alp
   VDQN_CHECK(!a->sample_gamma || !a->linear, "vdqn_net_td_forward: sample_gamma is given with linear: y = r + (Qa - 0.1) has no discount and no n-step form");
   hipStream_t st = (hipStream_t)stream;
   const int F = net->cfg.num_frames, dt = net->cfg.dtype;
-  const bool iql = iql_expectile > 0.f;
+  const AlgoRow& row = kAlgos[spec.algo];
   const int ns_online = step_layout_samples(net, a);
   const ActLayout A = act_layout(net, ns_online);
   const BwdLayout W = bwd_layout(net, B);
@@ -455,7 +482,7 @@ static int td_forward_impl(vdqn_net* net, const vdqn_step_args* a, float cql_alp
   if (tst != st) join(net, net->side, st);  // packed input ready for the online pass
   if (!gtb) {
     const ActLayout T = act_layout(net, B);
-    const unsigned char* tin_target = iql ? tin : tin + (int64_t)B * F * frame_bytes(net);  // implicit Q-learning: Q_target(s), not Q_target(s')
+    const unsigned char* tin_target = row.target_over_before ? tin : tin + (int64_t)B * F * frame_bytes(net);
     RC(forward_impl(net, (const unsigned char*)a->packed_target, tin_target, B, (unsigned char*)a->acts_target, T, tst, false, 0));  // (no backward: no arg-max bytes)
   }
   if (net->basic())  // two model calls (before, after), each with its own batch statistics; running stats updated in place
@@ -470,25 +497,13 @@ static int td_forward_impl(vdqn_net* net, const vdqn_step_args* a, float cql_alp
   VDQN_CHECK(e == hipSuccess, "vdqn_net_td_forward: memset failed: %s", hipGetErrorString(e));
   e = hipMemsetAsync(a->loss, 0, 4, st);
   VDQN_CHECK(e == hipSuccess, "vdqn_net_td_forward: memset failed: %s", hipGetErrorString(e));
-  if (cql_alpha > 0.f && cql_penalty) {
-    e = hipMemsetAsync(cql_penalty, 0, 4, st);
+  if (spec.cql_alpha > 0.f && spec.cql_penalty) {
+    e = hipMemsetAsync(spec.cql_penalty, 0, 4, st);
     VDQN_CHECK(e == hipSuccess, "vdqn_net_td_forward_cql: memset failed: %s", hipGetErrorString(e));
   }
-  if (mc_return && mc_stats) {
-    e = hipMemsetAsync(mc_stats, 0, 8, st);
-    VDQN_CHECK(e == hipSuccess, "vdqn_net_td_forward_mc: memset failed: %s", hipGetErrorString(e));
-  }
-  if (iql && iql_stats) {
-    e = hipMemsetAsync(iql_stats, 0, 8, st);
-    VDQN_CHECK(e == hipSuccess, "vdqn_net_td_forward_iql: memset failed: %s", hipGetErrorString(e));
-  }
-  if (dist && dist->stats) {
-    e = hipMemsetAsync(dist->stats, 0, 8, st);
-    VDQN_CHECK(e == hipSuccess, "vdqn_net_td_forward_dist: memset failed: %s", hipGetErrorString(e));
-  }
-  if (bcq && bcq->stats) {
-    e = hipMemsetAsync(bcq->stats, 0, 12, st);
-    VDQN_CHECK(e == hipSuccess, "vdqn_net_td_forward_bcq: memset failed: %s", hipGetErrorString(e));
+  if (spec.stats) {
+    e = hipMemsetAsync(spec.stats, 0, 4 * (size_t)spec.n_stats, st);
+    VDQN_CHECK(e == hipSuccess, "%s: memset failed: %s", row.entry, hipGetErrorString(e));
   }
 
   const float* qf_online = reinterpret_cast<const float*>(ao + A.qf);
@@ -502,14 +517,21 @@ static int td_forward_impl(vdqn_net* net, const vdqn_step_args* a, float cql_alp
     t.dtype = dt;
     t.deterministic = net->cfg.deterministic;
     t.q_copy = a->q_before;  // (the compact copy of Q(s) rides in the loss launch: no 2-D copy between the loss and the first data gradient)
-    if (bcq) RC(vdqn_td_loss_bcq(&t, a->sample_weight, a->sample_err, a->sample_gamma, bcq->threshold, bcq->bc_weight, bcq->logit_reg, bcq->stats, st));
-    else if (dist) RC(vdqn_td_loss_dist(&t, a->sample_weight, a->sample_err, a->sample_gamma, dist->flags, dist->sigma_min, dist->stats, st));
-    else if (iql) RC(vdqn_td_loss_iql(&t, a->sample_weight, a->sample_err, a->sample_gamma, iql_expectile, iql_stats, st));
-    else if (mc_return) RC(vdqn_td_loss_mc(&t, a->sample_weight, a->sample_err, cql_alpha, cql_alpha > 0.f ? cql_penalty : nullptr, a->sample_gamma, mc_return, mc_flags, mc_stats, st));
-    else if (a->sample_gamma) RC(vdqn_td_loss_nstep(&t, a->sample_weight, a->sample_err, cql_alpha, cql_alpha > 0.f ? cql_penalty : nullptr, a->sample_gamma, st));
-    else if (cql_alpha > 0.f) RC(vdqn_td_loss_cql(&t, a->sample_weight, a->sample_err, cql_alpha, cql_penalty, st));
-    else if (a->sample_weight) RC(vdqn_td_loss_weighted(&t, a->sample_weight, a->sample_err, st));
-    else RC(vdqn_td_loss(&t, st));
+    float* pen = spec.cql_alpha > 0.f ? spec.cql_penalty : nullptr;
+    const float *sw = a->sample_weight, *sg = a->sample_gamma;
+    float* se = a->sample_err;
+    switch (spec.algo) {
+      case ALGO_BCQ: RC(vdqn_td_loss_bcq(&t, sw, se, sg, spec.bcq_threshold, spec.bcq_bc_weight, spec.bcq_logit_reg, spec.stats, st)); break;
+      case ALGO_DIST: RC(vdqn_td_loss_dist(&t, sw, se, sg, spec.dist_flags, spec.dist_sigma_min, spec.stats, st)); break;
+      case ALGO_IQL: RC(vdqn_td_loss_iql(&t, sw, se, sg, spec.iql_expectile, spec.stats, st)); break;
+      case ALGO_TD:
+        if (spec.mc_return) RC(vdqn_td_loss_mc(&t, sw, se, spec.cql_alpha, pen, sg, spec.mc_return, spec.mc_flags, spec.stats, st));
+        else if (sg) RC(vdqn_td_loss_nstep(&t, sw, se, spec.cql_alpha, pen, sg, st));
+        else if (spec.cql_alpha > 0.f) RC(vdqn_td_loss_cql(&t, sw, se, spec.cql_alpha, spec.cql_penalty, st));
+        else if (sw) RC(vdqn_td_loss_weighted(&t, sw, se, st));
+        else RC(vdqn_td_loss(&t, st));
+        break;
+    }
   } else {
     RC(vdqn_gt_loss(qf_online, a->act, a->gt, a->loss, bw + W.dq, nullptr, B, net->cfg.num_classes, net->cfg.action_dim, 64, a->inv_count,
                     a->value_learning, dt, st));
@@ -522,7 +544,9 @@ static int td_forward_impl(vdqn_net* net, const vdqn_step_args* a, float cql_alp
   return VDQN_OK;
 }
 
-extern "C" int vdqn_net_td_forward(vdqn_net* net, const vdqn_step_args* a, void* stream) { return td_forward_impl(net, a, 0.f, nullptr, stream); }
+}  // namespace
+
+extern "C" int vdqn_net_td_forward(vdqn_net* net, const vdqn_step_args* a, void* stream) { return td_forward_impl(net, a, loss_spec(ALGO_TD, nullptr), stream); }
 
 extern "C" int vdqn_net_td_forward_cql(vdqn_net* net, const vdqn_step_args* a, float cql_alpha, float* cql_penalty, void* stream) {
   VDQN_CHECK(net && a, "vdqn_net_td_forward_cql: null arg");
@@ -531,64 +555,64 @@ extern "C" int vdqn_net_td_forward_cql(vdqn_net* net, const vdqn_step_args* a, f
     VDQN_CHECK(!a->train_on_ground_truth, "vdqn_net_td_forward_cql: the ground-truth branch regresses Q(s, a) on given targets and has no conservative penalty (train_on_ground_truth with cql_alpha > 0)");
     VDQN_CHECK(net->cfg.action_dim >= 2, "vdqn_net_td_forward_cql: action_dim is 1: with one action the penalty is identically zero");
   }
-  return td_forward_impl(net, a, cql_alpha, cql_penalty, stream);
+  LossSpec spec = loss_spec(ALGO_TD, nullptr);
+  spec.cql_alpha = cql_alpha; spec.cql_penalty = cql_penalty;
+  return td_forward_impl(net, a, spec, stream);
 }
 
+// Each entry below refuses, before the forward, everything its loss launch would refuse; the order decides which message a call
+// with several faults meets.
 // vdqn_net_td_forward_cql with the Monte-Carlo return of every sampled row (csrc/mcreturn.hip) for the loss launch: per-update
-// inputs, plain arguments, nothing kept in the engine.  Everything the loss launch would refuse is refused here, before the forward.
+// inputs, plain arguments, nothing kept in the engine.
 extern "C" int vdqn_net_td_forward_mc(vdqn_net* net, const vdqn_step_args* a, float cql_alpha, float* cql_penalty, const float* mc_return,
                                       int32_t mc_flags, float* mc_stats, void* stream) {
   if (!mc_return) return vdqn_net_td_forward_cql(net, a, cql_alpha, cql_penalty, stream);
   VDQN_CHECK(net && a, "vdqn_net_td_forward_mc: null arg");
   VDQN_CHECK(isfinite(cql_alpha) && cql_alpha >= 0.f, "vdqn_net_td_forward_mc: cql_alpha %g must be finite and >= 0", (double)cql_alpha);
-  VDQN_CHECK(!a->train_on_ground_truth, "vdqn_net_td_forward_mc: mc_return is given, but the ground-truth branch has no target to floor and no penalty to calibrate (train_on_ground_truth)");
-  VDQN_CHECK(!a->linear, "vdqn_net_td_forward_mc: mc_return is given with linear: y = r + (Qa - 0.1) has no discount, and a discounted return bounds nothing of it");
+  RC(refuse_by_row(kAlgos[ALGO_TD], net, a));
   VDQN_CHECK((mc_flags & ~3) == 0, "vdqn_net_td_forward_mc: mc_flags 0x%x has unknown bits (bit 0 = floor, bit 1 = calibrated)", (unsigned)mc_flags);
   VDQN_CHECK(mc_flags != 0, "vdqn_net_td_forward_mc: mc_flags is 0: at least one of bit 0 (floor) and bit 1 (calibrated) must be set");
   VDQN_CHECK(!(mc_flags & 2) || cql_alpha > 0.f, "vdqn_net_td_forward_mc: mc_flags bit 1 (calibrated) needs cql_alpha > 0");
   if (cql_alpha > 0.f) VDQN_CHECK(net->cfg.action_dim >= 2, "vdqn_net_td_forward_mc: action_dim is 1: with one action the penalty is identically zero");
-  return td_forward_impl(net, a, cql_alpha, cql_penalty, stream, mc_return, mc_flags, mc_stats);
+  LossSpec spec = loss_spec(ALGO_TD, mc_stats);
+  spec.cql_alpha = cql_alpha; spec.cql_penalty = cql_penalty; spec.mc_return = mc_return; spec.mc_flags = mc_flags;
+  return td_forward_impl(net, a, spec, stream);
 }
 
-// vdqn_net_td_forward for implicit Q-learning (csrc/iql.hip): everything the loss launch would refuse is refused here, before the
-// forward; then td_forward_impl with the target pass over `before` and vdqn_td_loss_iql for the loss launch.
+// implicit Q-learning (csrc/iql.hip)
 extern "C" int vdqn_net_td_forward_iql(vdqn_net* net, const vdqn_step_args* a, float expectile, float* iql_stats, void* stream) {
   VDQN_CHECK(net && a, "vdqn_net_td_forward_iql: null arg");
-  VDQN_CHECK(net->value_head, "vdqn_net_td_forward_iql: the net has no value head (create it with vdqn_net_create_v(cfg, 1, ..))");
-  VDQN_CHECK(!a->train_on_ground_truth, "vdqn_net_td_forward_iql: the ground-truth branch regresses Q(s, a) on given targets and bootstraps nothing (train_on_ground_truth)");
-  VDQN_CHECK(!a->linear, "vdqn_net_td_forward_iql: linear: y = r + (Qa - 0.1) is the reference's undiscounted Double-DQN target and has no V(s') form");
+  RC(refuse_by_row(kAlgos[ALGO_IQL], net, a));
   VDQN_CHECK(isfinite(expectile) && expectile >= 0.5f && expectile < 1.0f, "vdqn_net_td_forward_iql: expectile %g must be in [0.5, 1)", (double)expectile);
-  return td_forward_impl(net, a, 0.f, nullptr, stream, nullptr, 0, nullptr, expectile, iql_stats);
+  LossSpec spec = loss_spec(ALGO_IQL, iql_stats);
+  spec.iql_expectile = expectile;
+  return td_forward_impl(net, a, spec, stream);
 }
 
-// vdqn_net_td_forward for Gaussian distributional Q-learning (csrc/dist.hip): everything the loss launch would refuse is refused
-// here, before the forward; then td_forward_impl with vdqn_td_loss_dist for the loss launch.
+// Gaussian distributional Q-learning (csrc/dist.hip)
 extern "C" int vdqn_net_td_forward_dist(vdqn_net* net, const vdqn_step_args* a, int32_t flags, float sigma_min, float* dist_stats, void* stream) {
   VDQN_CHECK(net && a, "vdqn_net_td_forward_dist: null arg");
-  VDQN_CHECK(net->spread_head, "vdqn_net_td_forward_dist: the net has no spread head (create it with vdqn_net_create_d(cfg, 0, 1, ..))");
-  VDQN_CHECK(!a->train_on_ground_truth, "vdqn_net_td_forward_dist: the ground-truth branch regresses Q(s, a) on given targets and bootstraps nothing (train_on_ground_truth)");
-  VDQN_CHECK(!a->linear, "vdqn_net_td_forward_dist: linear: y = r + (Qa - 0.1) is the reference's undiscounted Double-DQN target; a variance has no backup without a discount");
+  RC(refuse_by_row(kAlgos[ALGO_DIST], net, a));
   VDQN_CHECK(a->loss_kind == 0, "vdqn_net_td_forward_dist: loss_kind %d: the loss is a KL divergence, which has no Huber form (loss_kind must be 0)", a->loss_kind);
   VDQN_CHECK((flags & ~3) == 0, "vdqn_net_td_forward_dist: flags 0x%x has unknown bits (bit 0 = KL_BACKWARDS, bit 1 = LOG_SIGMA)", (unsigned)flags);
   VDQN_CHECK(isfinite(sigma_min) && sigma_min >= 1e-4f && sigma_min <= 10.0f, "vdqn_net_td_forward_dist: sigma_min %g must be in [1e-4, 10]", (double)sigma_min);
-  const DistLoss dist = {flags, sigma_min, dist_stats};
-  return td_forward_impl(net, a, 0.f, nullptr, stream, nullptr, 0, nullptr, 0.f, nullptr, &dist);
+  LossSpec spec = loss_spec(ALGO_DIST, dist_stats);
+  spec.dist_flags = flags; spec.dist_sigma_min = sigma_min;
+  return td_forward_impl(net, a, spec, stream);
 }
 
-// vdqn_net_td_forward for discrete batch-constrained Q-learning (csrc/bcq.hip): everything the loss launch would refuse is refused
-// here, before the forward; then td_forward_impl with vdqn_td_loss_bcq for the loss launch.
+// discrete batch-constrained Q-learning (csrc/bcq.hip)
 extern "C" int vdqn_net_td_forward_bcq(vdqn_net* net, const vdqn_step_args* a, float threshold, float bc_weight, float logit_reg, float* bcq_stats,
                                        void* stream) {
   VDQN_CHECK(net && a, "vdqn_net_td_forward_bcq: null arg");
-  VDQN_CHECK(net->policy_head, "vdqn_net_td_forward_bcq: the net has no policy head (create it with vdqn_net_create_p(cfg, 0, 0, 1, ..))");
-  VDQN_CHECK(!a->train_on_ground_truth, "vdqn_net_td_forward_bcq: the ground-truth branch regresses Q(s, a) on given targets and bootstraps nothing (train_on_ground_truth)");
-  VDQN_CHECK(!a->linear, "vdqn_net_td_forward_bcq: linear: y = r + (Qa - 0.1) is the reference's undiscounted Double-DQN target; the constrained target is not defined for it");
+  RC(refuse_by_row(kAlgos[ALGO_BCQ], net, a));
   VDQN_CHECK(a->loss_kind == 0 || a->loss_kind == 1, "vdqn_net_td_forward_bcq: loss_kind %d (0 = half squared error, 1 = Huber)", a->loss_kind);
   VDQN_CHECK(isfinite(threshold) && threshold >= 0.0f && threshold < 1.0f, "vdqn_net_td_forward_bcq: threshold %g must be in [0, 1)", (double)threshold);
   VDQN_CHECK(isfinite(bc_weight) && bc_weight > 0.0f, "vdqn_net_td_forward_bcq: bc_weight %g must be finite and > 0", (double)bc_weight);
   VDQN_CHECK(isfinite(logit_reg) && logit_reg >= 0.0f, "vdqn_net_td_forward_bcq: logit_reg %g must be finite and >= 0", (double)logit_reg);
-  const BcqLoss bcq = {threshold, bc_weight, logit_reg, bcq_stats};
-  return td_forward_impl(net, a, 0.f, nullptr, stream, nullptr, 0, nullptr, 0.f, nullptr, nullptr, &bcq);
+  LossSpec spec = loss_spec(ALGO_BCQ, bcq_stats);
+  spec.bcq_threshold = threshold; spec.bcq_bc_weight = bc_weight; spec.bcq_logit_reg = logit_reg;
+  return td_forward_impl(net, a, spec, stream);
 }
 
 // One held-out batch of a validation pass (train_q_network.py:183-186 `eval_losses`, :240 `# checkpoint and eval`): the frames

@@ -85,14 +85,17 @@ struct BwdLayout {
 
 inline int64_t align_up(int64_t v, int64_t a = 256) { return (v + a - 1) / a * a; }
 
+enum Head { HEAD_NONE = 0, HEAD_VALUE, HEAD_SPREAD, HEAD_POLICY };
+
 #pragma GCC visibility pop
 
 struct vdqn_net {
   vdqn_net_config cfg;  // cfg.dtype is the STORAGE dtype: VDQN_F32 for a VDQN_F32X3 engine (every pointwise entry takes that)
-  int value_head = 0;   // 1: the Q layer also computes num_classes state values V(c) behind its Q columns (vdqn_net_create_v)
-  int spread_head = 0;  // 1: the Q layer also computes one spread rho(c, a) per Q column, at column n_q() + c * action_dim + a (vdqn_net_create_d)
-  int policy_head = 0;  // 1: the Q layer also computes one behaviour logit i(a) per action, at column n_q() + a (vdqn_net_create_p)
-  int gemm_dtype;       // dtype of the GEMM calls (convolutions, linear layers, weight gradients, stem): the requested one
+  // The one extra head the Q layer may carry behind its Q columns.  HEAD_VALUE: num_classes state values, V(c) at column n_q() + c
+  // (vdqn_net_create_v); HEAD_SPREAD: one spread rho(c, a) per Q column, at column n_q() + c * action_dim + a (vdqn_net_create_d);
+  // HEAD_POLICY: one behaviour logit i(a) per action, at column n_q() + a (vdqn_net_create_p).
+  Head head = HEAD_NONE;
+  int gemm_dtype;  // dtype of the GEMM calls (convolutions, linear layers, weight gradients, stem): the requested one
   int esz;  // bytes per activation element
   std::vector<Layer> layers;
   std::vector<vdqn_param_info> params;

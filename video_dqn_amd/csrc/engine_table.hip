@@ -94,20 +94,14 @@ Layer make_linear(const std::string& name, int out_f, int in_f, int stage, bool 
 void build_layers(vdqn_net* net) {
   const int F = net->cfg.num_frames;
   std::vector<Layer> fwd;  // forward order
-  // an extra head: more rows of the Q layer, registered below as <head>.weight / <head>.bias.  The value head
-  // (vdqn_net_create_v): num_classes rows, `value`; the spread head (vdqn_net_create_d): one row per Q column, `spread`; the
-  // policy head (vdqn_net_create_p): one behaviour logit per action, `policy`.  At most one of them is set.
+  // the extra head (rows indexed by Head): more rows of the Q layer, registered below as <head>.weight / <head>.bias.  The value
+  // head: num_classes rows; the spread head: one row per Q column; the policy head: one behaviour logit per action.
   const struct {
-    int on, rows;
+    int rows;
     const char* name;
-  } heads[] = {{net->value_head, net->cfg.num_classes, "value"}, {net->spread_head, net->n_q(), "spread"}, {net->policy_head, net->cfg.action_dim, "policy"}};
-  int n_head = 0;
-  std::string head;
-  for (const auto& h : heads)
-    if (h.on) {
-      n_head = h.rows;
-      head = h.name;
-    }
+  } heads[] = {{0, ""}, {net->cfg.num_classes, "value"}, {net->n_q(), "spread"}, {net->cfg.action_dim, "policy"}};
+  const int n_head = heads[net->head].rows;
+  const std::string head = heads[net->head].name;
   {
     Layer L = make_conv("resnet.conv1", "resnet.bn1", 64, 3, 7, 2, 3, 224, 2);
     L.kind = K_CONV1_S2D;
@@ -486,8 +480,8 @@ BwdLayout bwd_layout(const vdqn_net* net, int n_samples) {
 // ---------------------------------------------------------------------------------------------------------
 // C ABI
 // ---------------------------------------------------------------------------------------------------------
-static int net_create(const vdqn_net_config* cfg, int value_head, vdqn_net** out, int spread_head = 0, int policy_head = 0);
-extern "C" int vdqn_net_create(const vdqn_net_config* cfg, vdqn_net** out) { return net_create(cfg, 0, out); }
+static int net_create(const vdqn_net_config* cfg, Head head, vdqn_net** out);
+extern "C" int vdqn_net_create(const vdqn_net_config* cfg, vdqn_net** out) { return net_create(cfg, HEAD_NONE, out); }
 // vdqn_net_create with num_classes state values V(c) behind the Q columns of the Q layer (implicit Q-learning, csrc/iql.hip)
 extern "C" int vdqn_net_create_v(const vdqn_net_config* cfg, int32_t value_head, vdqn_net** out) {
   VDQN_CHECK(value_head == 0 || value_head == 1, "vdqn_net_create_v: value_head must be 0 or 1, not %d", value_head);
@@ -497,9 +491,9 @@ extern "C" int vdqn_net_create_v(const vdqn_net_config* cfg, int32_t value_head,
     VDQN_CHECK(cfg->num_classes >= 1 && (int64_t)cfg->action_dim * cfg->num_classes + cfg->num_classes <= 64,
                "vdqn_net_create_v: action_dim*num_classes + num_classes must be in 1..64 (the Q columns and one V per category share a 64-wide row)");
   }
-  return net_create(cfg, value_head, out);
+  return net_create(cfg, value_head ? HEAD_VALUE : HEAD_NONE, out);
 }
-extern "C" int vdqn_net_value_head(const vdqn_net* net) { return net ? net->value_head : 0; }
+extern "C" int vdqn_net_value_head(const vdqn_net* net) { return net && net->head == HEAD_VALUE; }
 // vdqn_net_create_v with one spread per Q column behind the Q columns (Gaussian distributional Q-learning, csrc/dist.hip)
 extern "C" int vdqn_net_create_d(const vdqn_net_config* cfg, int32_t value_head, int32_t spread_head, vdqn_net** out) {
   VDQN_CHECK(spread_head == 0 || spread_head == 1, "vdqn_net_create_d: spread_head must be 0 or 1, not %d", spread_head);
@@ -509,9 +503,9 @@ extern "C" int vdqn_net_create_d(const vdqn_net_config* cfg, int32_t value_head,
   VDQN_CHECK(cfg && out, "vdqn_net_create_d: null arg");
   VDQN_CHECK(cfg->action_dim >= 1 && cfg->num_classes >= 1 && 2 * (int64_t)cfg->action_dim * cfg->num_classes <= 64,
              "vdqn_net_create_d: 2 * action_dim*num_classes must be in 2..64 (the means and one spread per mean share a 64-wide row)");
-  return net_create(cfg, 0, out, 1);
+  return net_create(cfg, HEAD_SPREAD, out);
 }
-extern "C" int vdqn_net_spread_head(const vdqn_net* net) { return net ? net->spread_head : 0; }
+extern "C" int vdqn_net_spread_head(const vdqn_net* net) { return net && net->head == HEAD_SPREAD; }
 // vdqn_net_create_d with one behaviour logit per action behind the Q columns (discrete batch-constrained Q-learning, csrc/bcq.hip)
 extern "C" int vdqn_net_create_p(const vdqn_net_config* cfg, int32_t value_head, int32_t spread_head, int32_t policy_head, vdqn_net** out) {
   VDQN_CHECK(policy_head == 0 || policy_head == 1, "vdqn_net_create_p: policy_head must be 0 or 1, not %d", policy_head);
@@ -523,11 +517,11 @@ extern "C" int vdqn_net_create_p(const vdqn_net_config* cfg, int32_t value_head,
   VDQN_CHECK(cfg->action_dim >= 2, "vdqn_net_create_p: action_dim is %d: with one action there is nothing to constrain (policy_head needs action_dim >= 2)", cfg->action_dim);
   VDQN_CHECK(cfg->num_classes >= 1 && (int64_t)cfg->action_dim * cfg->num_classes + cfg->action_dim <= 64,
              "vdqn_net_create_p: action_dim*num_classes + action_dim must be in 1..64 (the Q columns and one behaviour logit per action share a 64-wide row)");
-  return net_create(cfg, 0, out, 0, 1);
+  return net_create(cfg, HEAD_POLICY, out);
 }
-extern "C" int vdqn_net_policy_head(const vdqn_net* net) { return net ? net->policy_head : 0; }
+extern "C" int vdqn_net_policy_head(const vdqn_net* net) { return net && net->head == HEAD_POLICY; }
 
-static int net_create(const vdqn_net_config* cfg, int value_head, vdqn_net** out, int spread_head, int policy_head) {
+static int net_create(const vdqn_net_config* cfg, Head head, vdqn_net** out) {
   VDQN_CHECK(cfg && out, "vdqn_net_create: null arg");
   VDQN_CHECK(cfg->extra_capacity == 0 || cfg->extra_capacity == 1, "vdqn_net_create: extra_capacity must be 0 or 1");
   VDQN_CHECK(cfg->dtype == VDQN_F32 || cfg->dtype == VDQN_BF16 || cfg->dtype == VDQN_F32X3, "vdqn_net_create: bad dtype %d", cfg->dtype);
@@ -537,9 +531,7 @@ static int net_create(const vdqn_net_config* cfg, int value_head, vdqn_net** out
   VDQN_CHECK(cfg->deterministic == 0 || cfg->deterministic == 1, "vdqn_net_create: deterministic must be 0 or 1");
   vdqn_net* net = new vdqn_net();
   net->cfg = *cfg;
-  net->value_head = value_head;
-  net->spread_head = spread_head;
-  net->policy_head = policy_head;
+  net->head = head;
   net->gemm_dtype = cfg->dtype;
   if (cfg->dtype == VDQN_F32X3) net->cfg.dtype = VDQN_F32;  // f32 layout, tensors and pointwise kernels; only the GEMMs differ
   net->esz = cfg->dtype == VDQN_BF16 ? 2 : 4;

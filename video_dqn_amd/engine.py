@@ -14,11 +14,13 @@ import math
 import os
 from collections import OrderedDict
 from dataclasses import dataclass
+from types import SimpleNamespace
 from typing import Dict, Optional
 
 import torch
 
 from . import _lib
+from .algos import ALGOS, BCQ, LOSS_SLOTS, MODIFIERS, refuse
 
 LOSS_KINDS = {"l2": 0, "huber": 1}  # vdqn_td_args.loss_kind
 
@@ -101,27 +103,16 @@ class NetEngine:
         self.deterministic = bool(deterministic)
         self.cfg = _lib.NetConfig(action_dim, num_classes, num_frames, int(self.extra_capacity), DTYPES[dtype], max_batch,
                                   int(self.deterministic))
-        # value_head (implicit Q-learning): num_classes state values V(c) behind the Q columns of the Q layer, its extra rows the
-        # parameters `value.weight` / `value.bias` (vdqn_net_create_v); False: vdqn_net_create, the same tables and bits
-        self.value_head = bool(value_head)
-        # spread_head (Gaussian distributional Q-learning): one spread parameter rho(c, a) per Q column behind the Q columns, the
-        # extra rows the parameters `spread.weight` / `spread.bias` (vdqn_net_create_d)
-        self.spread_head = bool(spread_head)
-        # the extra head behind the Q layer, if any, and its parameters' names: never among the reference's keys
-        # policy_head (discrete batch-constrained Q-learning): one behaviour logit i(a) per action behind the Q columns, the extra
-        # rows the parameters `policy.weight` / `policy.bias` (vdqn_net_create_p)
-        self.policy_head = bool(policy_head)
-        self.head = "policy" if self.policy_head else ("spread" if self.spread_head else ("value" if self.value_head else None))
-        self.head_keys = (f"{self.head}.weight", f"{self.head}.bias") if self.head else ()
+        # The one extra head behind the Q layer (algos.py), its extra rows the parameters <head>.weight / <head>.bias, never among the
+        # reference's keys; none: vdqn_net_create, the same tables and bits.  The create entries form a chain, each taking its
+        # predecessors' flags in front of its own: the last flag set picks the entry, and the engine refuses more than one.
+        given = {"value": bool(value_head), "spread": bool(spread_head), "policy": bool(policy_head)}
+        self.value_head, self.spread_head, self.policy_head = given.values()
+        flags = [given[a.head] for a in ALGOS]
+        last = max((i for i, f in enumerate(flags) if f), default=-1)
+        self.head, self.head_keys, create = (None, (), "vdqn_net_create") if last < 0 else (ALGOS[last].head, ALGOS[last].head_keys, ALGOS[last].create)
         h = C.c_void_p()
-        if self.policy_head:
-            _lib.check(self.lib.vdqn_net_create_p(C.byref(self.cfg), int(self.value_head), int(self.spread_head), 1, C.byref(h)), "vdqn_net_create_p")
-        elif self.spread_head:
-            _lib.check(self.lib.vdqn_net_create_d(C.byref(self.cfg), int(self.value_head), 1, C.byref(h)), "vdqn_net_create_d")
-        elif self.value_head:
-            _lib.check(self.lib.vdqn_net_create_v(C.byref(self.cfg), 1, C.byref(h)), "vdqn_net_create_v")
-        else:
-            _lib.check(self.lib.vdqn_net_create(C.byref(self.cfg), C.byref(h)), "vdqn_net_create")
+        _lib.check(getattr(self.lib, create)(C.byref(self.cfg), *map(int, flags[:last + 1]), C.byref(h)), create)
         self.handle = h
         self.max_batch = max_batch
         self.slots: "OrderedDict[str, ParamSlot]" = OrderedDict()
@@ -226,50 +217,39 @@ class NetEngine:
                                                  _ptr(acts), _ptr(q), _stream()), "vdqn_net_forward")
         return q
 
-    def state_values(self, n_samples: int) -> torch.Tensor:
-        """V(s) f32 [n_samples, num_classes] of the LAST `forward(.., n_samples)` call: the value head's columns of the f32 Q rows
-        that call left in its workspace (no second pass)."""
+    def _last_qf(self, what: str, head: str, n_samples: int) -> torch.Tensor:
+        """The f32 Q rows [n_samples][64], as bytes, that the LAST `forward(.., n_samples)` left in its workspace (no second pass)."""
         self._need_gpu()
-        if not self.value_head:
-            raise _lib.VdqnError("state_values: this NetEngine has no value head (NetEngine(value_head=True))")
+        if self.head != head:
+            raise _lib.VdqnError(f"{what}: this NetEngine has no {head} head (NetEngine({head}_head=True))")
         acts = self._acts.get(n_samples)
         if acts is None:
-            raise _lib.VdqnError(f"state_values: no forward over {n_samples} samples has run")
+            raise _lib.VdqnError(f"{what}: no forward over {n_samples} samples has run")
         off = self.lib.vdqn_net_act_offset(self.handle, n_samples, b"qf")
+        return acts[off:off + n_samples * 64 * 4]
+
+    def state_values(self, n_samples: int) -> torch.Tensor:
+        """V(s) f32 [n_samples, num_classes] of the last forward: the value head's columns of its f32 Q rows."""
         nq = self.num_classes * self.action_dim
-        return acts[off:off + n_samples * 64 * 4].view(torch.float32).view(n_samples, 64)[:, nq:nq + self.num_classes].clone()
+        return self._last_qf("state_values", "value", n_samples).view(torch.float32).view(n_samples, 64)[:, nq:nq + self.num_classes].clone()
 
     def dist_moments(self, n_samples: int, log_sigma: bool, sigma_min: float) -> torch.Tensor:
-        """f32 [n_samples, num_classes, action_dim, 2] = {mean, variance} of the LAST `forward(.., n_samples)` call: vdqn_dist_moments
-        over the f32 Q rows that call left in its workspace (no second pass)."""
-        self._need_gpu()
-        if not self.spread_head:
-            raise _lib.VdqnError("dist_moments: this NetEngine has no spread head (NetEngine(spread_head=True))")
-        acts = self._acts.get(n_samples)
-        if acts is None:
-            raise _lib.VdqnError(f"dist_moments: no forward over {n_samples} samples has run")
-        off = self.lib.vdqn_net_act_offset(self.handle, n_samples, b"qf")
+        """f32 [n_samples, num_classes, action_dim, 2] = {mean, variance} of the last forward: vdqn_dist_moments over its f32 Q rows."""
+        qf = self._last_qf("dist_moments", "spread", n_samples)
         out = torch.empty((n_samples, self.num_classes, self.action_dim, 2), dtype=torch.float32, device=self.device)
         with torch.cuda.device(self.device):
-            _lib.check(self.lib.vdqn_dist_moments(acts.data_ptr() + off, out.data_ptr(), n_samples, self.num_classes, self.action_dim, 64,
+            _lib.check(self.lib.vdqn_dist_moments(qf.data_ptr(), out.data_ptr(), n_samples, self.num_classes, self.action_dim, 64,
                                                   2 if log_sigma else 0, float(sigma_min), _stream()), "vdqn_dist_moments")
         return out
 
     def bcq_constrain(self, n_samples: int, threshold: float):
         """(q f32 [n_samples, num_classes, action_dim] with the actions the behaviour head disallows at -inf, prob f32 [n_samples,
-        action_dim] = the behaviour probabilities) of the LAST `forward(.., n_samples)` call: vdqn_bcq_constrain over the f32 Q rows
-        that call left in its workspace (no second pass)."""
-        self._need_gpu()
-        if not self.policy_head:
-            raise _lib.VdqnError("bcq_constrain: this NetEngine has no policy head (NetEngine(policy_head=True))")
-        acts = self._acts.get(n_samples)
-        if acts is None:
-            raise _lib.VdqnError(f"bcq_constrain: no forward over {n_samples} samples has run")
-        off = self.lib.vdqn_net_act_offset(self.handle, n_samples, b"qf")
+        action_dim] = the behaviour probabilities) of the last forward: vdqn_bcq_constrain over its f32 Q rows."""
+        qf = self._last_qf("bcq_constrain", "policy", n_samples)
         q = torch.empty((n_samples, self.num_classes, self.action_dim), dtype=torch.float32, device=self.device)
         prob = torch.empty((n_samples, self.action_dim), dtype=torch.float32, device=self.device)
         with torch.cuda.device(self.device):
-            _lib.check(self.lib.vdqn_bcq_constrain(acts.data_ptr() + off, q.data_ptr(), prob.data_ptr(), n_samples, self.num_classes,
+            _lib.check(self.lib.vdqn_bcq_constrain(qf.data_ptr(), q.data_ptr(), prob.data_ptr(), n_samples, self.num_classes,
                                                    self.action_dim, 64, float(threshold), _stream()), "vdqn_bcq_constrain")
         return q, prob
 
@@ -432,74 +412,39 @@ class TDStepper:
                                  "target to floor; y = r + (Qa - 0.1) has no discount)")
         if cql_calibrated and not cql_alpha > 0:
             raise _lib.VdqnError("TDStepper: cql_calibrated needs cql_alpha > 0 (there is no penalty to calibrate)")
-        # iql_expectile > 0 (implicit Q-learning, csrc/iql.hip; needs NetEngine(value_head=True)): the update is
-        # vdqn_net_td_forward_iql — the target pass over s instead of s', the loss launch vdqn_td_loss_iql, which fits V(s) to the
-        # target network's Q(s, a_data) by expectile regression and bootstraps Q from V(s') — and `iql_stats` receives this rank's
-        # share of {the V loss, the mean of Q_target(s, a_data) - V(s)}.  0: the entries above, launched as ever.
-        iql_expectile = float(iql_expectile)
+        # The head algorithms (algos.py: one row each; at most one is on, `self.algo`): each needs the NetEngine with its head and runs
+        # the update through its own entry.  All off: the entries above, launched as ever.  Their value checks, then the row's refusals.
+        self.iql_expectile = iql_expectile = float(iql_expectile)
         if iql_expectile != 0.0 and not (0.5 <= iql_expectile < 1.0):
             raise _lib.VdqnError(f"TDStepper: iql_expectile must be 0 (off) or in [0.5, 1), not {iql_expectile}")
-        if iql_expectile > 0:
-            if not getattr(net, "value_head", False):
-                raise _lib.VdqnError("TDStepper: iql_expectile needs a network with the value head (NetEngine(value_head=True))")
-            if train_on_ground_truth or linear:
-                raise _lib.VdqnError("TDStepper: iql_expectile applies to the TD branch without linear (train_on_ground_truth bootstraps "
-                                     "nothing; y = r + (Qa - 0.1) has no V(s') form)")
-            if cql_alpha > 0 or self.mc_flags:
-                raise _lib.VdqnError("TDStepper: iql_expectile does not combine with cql_alpha, mc_floor or cql_calibrated (out of scope: "
-                                     "the IQL loss launch has neither the penalty nor the return floor)")
-        self.iql_expectile = iql_expectile
-        # distributional (Gaussian distributional Q-learning, csrc/dist.hip; needs NetEngine(spread_head=True)): the update is
-        # vdqn_net_td_forward_dist — the same three forward passes, the loss launch vdqn_td_loss_dist: the KL divergence between the
-        # Gaussian of Q(s, a_data) and that of the Double-DQN backup, its direction by kl_backwards, the spread's parametrisation by
-        # log_sigma, its floor sigma_min — and `dist_stats` receives this rank's share of {mean predicted sigma, mean squared
-        # standardised error}.  False: the entries above, launched as ever.
         for key, val in (("distributional", distributional), ("kl_backwards", kl_backwards), ("log_sigma", log_sigma)):
             if not isinstance(val, bool):
                 raise _lib.VdqnError(f"TDStepper: {key} must be a bool, not {val!r}")
         if (kl_backwards or log_sigma) and not distributional:
             raise _lib.VdqnError("TDStepper: kl_backwards / log_sigma have no effect without distributional")
-        if distributional:
-            sigma_min = float(sigma_min)
-            if not (1e-4 <= sigma_min <= 10.0):
-                raise _lib.VdqnError(f"TDStepper: sigma_min must be in [1e-4, 10], not {sigma_min}")
-            if not getattr(net, "spread_head", False):
-                raise _lib.VdqnError("TDStepper: distributional needs a network with the spread head (NetEngine(spread_head=True))")
-            if train_on_ground_truth or linear:
-                raise _lib.VdqnError("TDStepper: distributional applies to the TD branch without linear (train_on_ground_truth bootstraps "
-                                     "nothing; y = r + (Qa - 0.1) has no discount to back a variance up with)")
-            if loss_kind != "l2":
-                raise _lib.VdqnError(f"TDStepper: distributional with loss_kind {loss_kind!r}: the loss is a KL divergence, which has no Huber form")
-            if cql_alpha > 0 or self.mc_flags or iql_expectile > 0:
-                raise _lib.VdqnError("TDStepper: distributional does not combine with cql_alpha, mc_floor, cql_calibrated or iql_expectile "
-                                     "(out of scope: the distributional loss launch has neither the penalty, the return floor nor a value head)")
         self.distributional, self.sigma_min = distributional, float(sigma_min)
+        if distributional and not (1e-4 <= self.sigma_min <= 10.0):
+            raise _lib.VdqnError(f"TDStepper: sigma_min must be in [1e-4, 10], not {self.sigma_min}")
         self.dist_flags = (1 if kl_backwards else 0) | (2 if log_sigma else 0)
-        # bcq_threshold in [0, 1) (discrete batch-constrained Q-learning, csrc/bcq.hip; needs NetEngine(policy_head=True)): the update
-        # is vdqn_net_td_forward_bcq — the same three forward passes, the loss launch vdqn_td_loss_bcq: the Double-DQN arg-max at s'
-        # only over the actions whose behaviour probability is above bcq_threshold times the largest, plus bcq_bc_weight times the
-        # cross-entropy of the behaviour logits at the logged action (and bcq_logit_reg times their mean square) — and `bcq_stats`
-        # receives this rank's share of {mean cross-entropy, share of targets the constraint changes, behaviour accuracy}.
-        # -1 (off): the entries above, launched as ever.
         bcq_threshold, bcq_bc_weight, bcq_logit_reg = float(bcq_threshold), float(bcq_bc_weight), float(bcq_logit_reg)
-        self.bcq = bcq_threshold != -1.0
         if not (bcq_threshold == -1.0 or 0.0 <= bcq_threshold < 1.0):
             raise _lib.VdqnError(f"TDStepper: bcq_threshold must be -1 (off) or in [0, 1), not {bcq_threshold}")
         if not (math.isfinite(bcq_bc_weight) and bcq_bc_weight > 0):
             raise _lib.VdqnError(f"TDStepper: bcq_bc_weight must be finite and > 0, not {bcq_bc_weight}")
         if not (math.isfinite(bcq_logit_reg) and bcq_logit_reg >= 0):
             raise _lib.VdqnError(f"TDStepper: bcq_logit_reg must be finite and >= 0, not {bcq_logit_reg}")
-        if self.bcq:
-            if not getattr(net, "policy_head", False):
-                raise _lib.VdqnError("TDStepper: bcq_threshold needs a network with the policy head (NetEngine(policy_head=True))")
-            if train_on_ground_truth or linear:
-                raise _lib.VdqnError("TDStepper: bcq_threshold applies to the TD branch without linear (train_on_ground_truth bootstraps "
-                                     "nothing; the constrained target is not defined for y = r + (Qa - 0.1))")
-            if cql_alpha > 0 or self.mc_flags or iql_expectile > 0 or distributional:
-                raise _lib.VdqnError("TDStepper: bcq_threshold does not combine with cql_alpha, mc_floor, cql_calibrated, iql_expectile or "
-                                     "distributional (out of scope: one extra head sits behind the Q layer, and the BCQ loss launch has "
-                                     "neither the penalty nor the return floor)")
         self.bcq_threshold, self.bcq_bc_weight, self.bcq_logit_reg = bcq_threshold, bcq_bc_weight, bcq_logit_reg
+        facts = SimpleNamespace(TRAIN_ON_GROUND_TRUTH=train_on_ground_truth, LINEAR=linear, LOSS_KIND=loss_kind, CQL_ALPHA=cql_alpha,
+                                CQL_CALIBRATED=cql_calibrated, MC_RETURN_FLOOR=mc_floor, IQL_EXPECTILE=iql_expectile,
+                                DISTRIBUTIONAL=distributional, BCQ_THRESHOLD=bcq_threshold)
+        names = {key: arg for key, arg, *_ in MODIFIERS + tuple(p for a in ALGOS for p in a.params)}
+        self.algo = None
+        for algo in (a for a in ALGOS if a.is_on(facts)):
+            if getattr(net, "head", None) != algo.head:
+                raise _lib.VdqnError(f"TDStepper: {names[algo.key]} needs a network with the {algo.head} head (NetEngine({algo.head}_head=True))")
+            refuse(algo, facts, lambda key: names.get(key, key.lower()), _lib.VdqnError, "TDStepper: ")
+            self.algo = algo
+        self.bcq = self.algo is BCQ
         # target_tau > 0 (soft / Polyak target updates): `target_params`, an f32 copy of the whole flat `net.params` (the trainable
         # prefix and the frozen resnet.fc tail), follows the online weights as target <- target + tau (params - target) inside every
         # Adam launch (vdqn_adam_polyak), and `packed_target` is folded from it in front of every update; target_update_interval is
@@ -544,11 +489,12 @@ class TDStepper:
             self.exp_avg = torch.zeros(nt, dtype=torch.float32, device=dev)
             self.exp_avg_sq = torch.zeros(nt, dtype=torch.float32, device=dev)
             self.loss = torch.zeros(1, dtype=torch.float32, device=dev)
-            self.cql_penalty = torch.zeros(1, dtype=torch.float32, device=dev)
-            self.mc_stats = torch.zeros(2, dtype=torch.float32, device=dev)
-            self.iql_stats = torch.zeros(2, dtype=torch.float32, device=dev)
-            self.dist_stats = torch.zeros(2, dtype=torch.float32, device=dev)
-            self.bcq_stats = torch.zeros(3, dtype=torch.float32, device=dev)
+            # what the loss launch writes beside the loss.  The TD family: cql_penalty in slot 0, mc_stats in slots 1..2; a head
+            # algorithm (never beside them): its statistics from slot 0
+            self.loss_stats = torch.zeros(LOSS_SLOTS, dtype=torch.float32, device=dev)
+            self.cql_penalty, self.mc_stats = self.loss_stats[0:1], self.loss_stats[1:3]
+            for a in ALGOS:
+                setattr(self, a.stats_attr, self.loss_stats[:len(a.stats)])
             self.q_before = torch.zeros((batch, net.num_classes * net.action_dim), dtype=torch.float32, device=dev)
             self._ones = torch.ones((batch, net.num_classes), dtype=torch.float32, device=dev)
             if self.grad_clip_norm > 0:
@@ -681,23 +627,16 @@ class TDStepper:
             if ahead is not None and ahead[0] == self._frames_key(before, after, src_kind):
                 slot = ahead[1]  # these frames were packed during the previous update (ordered in front of `st` by its last stage)
                 a.packed_frames = self._packed_buffer(slot).data_ptr()
-            if self.bcq:
-                _lib.check(self.lib.vdqn_net_td_forward_bcq(n.handle, C.byref(a), self.bcq_threshold, self.bcq_bc_weight, self.bcq_logit_reg,
-                                                            self.bcq_stats.data_ptr(), st), "vdqn_net_td_forward_bcq")
-            elif self.distributional:
-                _lib.check(self.lib.vdqn_net_td_forward_dist(n.handle, C.byref(a), self.dist_flags, self.sigma_min, self.dist_stats.data_ptr(), st),
-                           "vdqn_net_td_forward_dist")
-            elif self.iql_expectile > 0:
-                _lib.check(self.lib.vdqn_net_td_forward_iql(n.handle, C.byref(a), self.iql_expectile, self.iql_stats.data_ptr(), st),
-                           "vdqn_net_td_forward_iql")
+            if self.algo is not None:
+                entry, args = self.algo.entry, (*self.algo.entry_args(self), getattr(self, self.algo.stats_attr).data_ptr())
             elif mc_return is not None:
-                _lib.check(self.lib.vdqn_net_td_forward_mc(n.handle, C.byref(a), self.cql_alpha, self.cql_penalty.data_ptr(), mc_return.data_ptr(),
-                                                           self.mc_flags, self.mc_stats.data_ptr(), st), "vdqn_net_td_forward_mc")
+                entry, args = "vdqn_net_td_forward_mc", (self.cql_alpha, self.cql_penalty.data_ptr(), mc_return.data_ptr(), self.mc_flags,
+                                                         self.mc_stats.data_ptr())
             elif self.cql_alpha > 0:
-                _lib.check(self.lib.vdqn_net_td_forward_cql(n.handle, C.byref(a), self.cql_alpha, self.cql_penalty.data_ptr(), st),
-                           "vdqn_net_td_forward_cql")
+                entry, args = "vdqn_net_td_forward_cql", (self.cql_alpha, self.cql_penalty.data_ptr())
             else:
-                _lib.check(self.lib.vdqn_net_td_forward(n.handle, C.byref(a), st), "vdqn_net_td_forward")
+                entry, args = "vdqn_net_td_forward", ()
+            _lib.check(getattr(self.lib, entry)(n.handle, C.byref(a), *args, st), entry)
             err_ready = None
             if td_error is not None and self.allreduce_errors is not None:  # the loss launch has written this rank's errors on `st`
                 err_ready = torch.cuda.Event()

@@ -32,13 +32,11 @@ from collections import OrderedDict
 import torch
 import torch.nn as nn
 
+from .algos import ALGOS
 from .engine import NetEngine, _say_once, head_kept_message
 
-VALUE_KEYS = ("value.weight", "value.bias")  # the value head's parameters: never among the reference's keys
-SPREAD_KEYS = ("spread.weight", "spread.bias")  # the spread head's, likewise
 # checkpoint key of an extra head -> its parameters: what the reference's three keys leave out and a key of its own carries
-POLICY_KEYS = ("policy.weight", "policy.bias")  # the policy (behaviour) head's, likewise
-HEADS = {"value_head": VALUE_KEYS, "spread_head": SPREAD_KEYS, "policy_head": POLICY_KEYS}
+HEADS = {f"{a.head}_head": a.head_keys for a in ALGOS}
 
 
 def head_of(net):
@@ -399,11 +397,9 @@ def build_model(config, max_batch=None):
                                  max_batch=max_batch or max(64, 2 * getattr(config, "BATCH_SIZE", 16)),
                                  pretrained_weights=(getattr(config, "PRETRAINED_WEIGHTS", "") or None),
                                  deterministic=(True if getattr(config, "DETERMINISTIC", False) else None),
-                                 value_head=float(getattr(config, "IQL_EXPECTILE", 0.0) or 0.0) > 0,
-                                 distributional=bool(getattr(config, "DISTRIBUTIONAL", False)),
                                  log_sigma=bool(getattr(config, "LOG_SIGMA", False)),
                                  sigma_min=float(getattr(config, "DIST_SIGMA_MIN", 0.1)),
-                                 policy_head=float(getattr(config, "BCQ_THRESHOLD", -1.0)) >= 0)
+                                 **{a.model_arg: a.is_on(config) for a in ALGOS})
 
 
 def load_model_number(config, number, model_loc=None):

@@ -18,6 +18,7 @@ import numpy as np
 import torch
 from torch.utils import data
 
+from . import algos
 from .augment import COLOR_KEYS, Augmenter, jz
 from .dataset import QLearningRealDataset, SyntheticTupleDataset
 from .dist import BucketAllReduce, agree_all, broadcast_replica_state
@@ -289,34 +290,18 @@ def check_mc(config) -> None:
 
 def check_iql(config) -> None:
     """IQL_EXPECTILE: raise ValueError naming the key (before any device work) for a value outside {0} and [0.5, 1) and, when it is
-    on, for every configuration implicit Q-learning does not cover."""
+    on, for every configuration implicit Q-learning does not cover (algos.refuse)."""
     import math
     tau = getattr(config, "IQL_EXPECTILE", 0.0)
     if isinstance(tau, bool) or not isinstance(tau, (int, float)) or not math.isfinite(tau) or not (tau == 0 or 0.5 <= tau < 1):
         raise ValueError(f"IQL_EXPECTILE must be 0 (off) or a number in [0.5, 1), not {tau!r}")
-    if tau == 0:
-        return
-    if getattr(config, "TRAIN_ON_GROUND_TRUTH", False):
-        raise ValueError("IQL_EXPECTILE needs the TD branch: TRAIN_ON_GROUND_TRUTH regresses Q(s, a) on given targets and bootstraps nothing")
-    if getattr(config, "LINEAR", False):
-        raise ValueError("IQL_EXPECTILE does not cover LINEAR: y = r + (Qa - 0.1) is the undiscounted Double-DQN target and has no V(s') form")
-    for key in ("VALUE_LEARNING", "ONE_ACTION"):
-        if getattr(config, key, False):
-            raise ValueError(f"IQL_EXPECTILE needs more than one action: {key} builds a network with one action column, whose "
-                             "Q(s, a) is the state value already")
-    if float(getattr(config, "CQL_ALPHA", 0.0)) > 0:
-        raise ValueError("IQL_EXPECTILE with CQL_ALPHA > 0 is deliberately out of scope: the IQL loss launch has no conservative "
-                         "penalty (implicit Q-learning avoids out-of-data actions instead of penalising them); use one or the other")
-    for key in ("CQL_CALIBRATED", "MC_RETURN_FLOOR"):
-        if getattr(config, key, False):
-            raise ValueError(f"IQL_EXPECTILE with {key} is deliberately out of scope: the IQL loss launch takes no Monte-Carlo "
-                             "return table; use one or the other")
+    algos.refuse(algos.IQL, config)
 
 
 def check_dist(config) -> None:
     """DISTRIBUTIONAL, KL_BACKWARDS, LOG_SIGMA, DIST_SIGMA_MIN: raise ValueError naming the key (before any device work) for a value
     that is no bool, for a modifier without DISTRIBUTIONAL, for a floor outside [1e-4, 10] and, when the key is on, for every
-    configuration Gaussian distributional Q-learning does not cover."""
+    configuration Gaussian distributional Q-learning does not cover (algos.refuse)."""
     import math
     for key in ("DISTRIBUTIONAL", "KL_BACKWARDS", "LOG_SIGMA"):
         if not isinstance(getattr(config, key, False), bool):
@@ -324,34 +309,17 @@ def check_dist(config) -> None:
     smin = getattr(config, "DIST_SIGMA_MIN", 0.1)
     if isinstance(smin, bool) or not isinstance(smin, (int, float)) or not math.isfinite(smin) or not (1e-4 <= smin <= 10):
         raise ValueError(f"DIST_SIGMA_MIN must be a number in [1e-4, 10], not {smin!r}")
-    if not getattr(config, "DISTRIBUTIONAL", False):
-        for key in ("KL_BACKWARDS", "LOG_SIGMA"):
-            if getattr(config, key, False):
-                raise ValueError(f"{key} has no effect without DISTRIBUTIONAL: it chooses the direction of the KL divergence / the "
-                                 "parametrisation of the spread of the distributional loss; set DISTRIBUTIONAL: True or leave it False")
-        return
-    if getattr(config, "TRAIN_ON_GROUND_TRUTH", False):
-        raise ValueError("DISTRIBUTIONAL needs the TD branch: TRAIN_ON_GROUND_TRUTH regresses Q(s, a) on given targets and bootstraps nothing")
-    if getattr(config, "LINEAR", False):
-        raise ValueError("DISTRIBUTIONAL does not cover LINEAR: y = r + (Qa - 0.1) has no discount to back a variance up with")
-    if str(getattr(config, "LOSS_KIND", "l2")) != "l2":
-        raise ValueError(f"DISTRIBUTIONAL with LOSS_KIND: {config.LOSS_KIND} — the loss is a KL divergence between two Gaussians, which has no Huber form")
-    if float(getattr(config, "CQL_ALPHA", 0.0)) > 0:
-        raise ValueError("DISTRIBUTIONAL with CQL_ALPHA > 0 is deliberately out of scope: the distributional loss launch has no "
-                         "conservative penalty; use one or the other")
-    for key in ("CQL_CALIBRATED", "MC_RETURN_FLOOR"):
-        if getattr(config, key, False):
-            raise ValueError(f"DISTRIBUTIONAL with {key} is deliberately out of scope: the distributional loss launch takes no "
-                             "Monte-Carlo return table; use one or the other")
-    if float(getattr(config, "IQL_EXPECTILE", 0.0) or 0.0) > 0:
-        raise ValueError("DISTRIBUTIONAL with IQL_EXPECTILE > 0 is deliberately out of scope: one extra head sits behind the Q layer, "
-                         "the value head or the spread head; use one or the other")
+    for key in ("KL_BACKWARDS", "LOG_SIGMA"):
+        if getattr(config, key, False) and not getattr(config, "DISTRIBUTIONAL", False):
+            raise ValueError(f"{key} has no effect without DISTRIBUTIONAL: it chooses the direction of the KL divergence / the "
+                             "parametrisation of the spread of the distributional loss; set DISTRIBUTIONAL: True or leave it False")
+    algos.refuse(algos.DIST, config)
 
 
 def check_bcq(config) -> None:
     """BCQ_THRESHOLD, BCQ_BC_WEIGHT, BCQ_LOGIT_REG: raise ValueError naming the key (before any device work) for a threshold outside
     {-1} and [0, 1), a weight that is not finite and > 0, a regulariser that is not finite and >= 0, either of the two away from
-    its default while BCQ is off and, when it is on, for every configuration discrete BCQ does not cover."""
+    its default while BCQ is off and, when it is on, for every configuration discrete BCQ does not cover (algos.refuse)."""
     import math
 
     def number(key, default):
@@ -366,33 +334,11 @@ def check_bcq(config) -> None:
         raise ValueError(f"BCQ_BC_WEIGHT must be > 0, not {bc_weight!r}")
     if not logit_reg >= 0:
         raise ValueError(f"BCQ_LOGIT_REG must be >= 0, not {logit_reg!r}")
-    if tau < 0:
-        for key, val, default in (("BCQ_BC_WEIGHT", bc_weight, 1.0), ("BCQ_LOGIT_REG", logit_reg, 0.01)):
-            if val != default:
-                raise ValueError(f"{key} has no effect without BCQ_THRESHOLD: it weighs a term of the behaviour head's loss; set "
-                                 f"BCQ_THRESHOLD in [0, 1) or leave {key} at {default}")
-        return
-    if getattr(config, "TRAIN_ON_GROUND_TRUTH", False):
-        raise ValueError("BCQ_THRESHOLD needs the TD branch: TRAIN_ON_GROUND_TRUTH regresses Q(s, a) on given targets and bootstraps nothing")
-    if getattr(config, "LINEAR", False):
-        raise ValueError("BCQ_THRESHOLD does not cover LINEAR: the constrained target is not defined for y = r + (Qa - 0.1)")
-    for key in ("VALUE_LEARNING", "ONE_ACTION"):
-        if getattr(config, key, False):
-            raise ValueError(f"BCQ_THRESHOLD needs more than one action: {key} builds a network with one action column, and with "
-                             "one action there is nothing to constrain")
-    if float(getattr(config, "CQL_ALPHA", 0.0)) > 0:
-        raise ValueError("BCQ_THRESHOLD with CQL_ALPHA > 0 is deliberately out of scope: the BCQ loss launch has no conservative "
-                         "penalty; use one or the other")
-    for key in ("CQL_CALIBRATED", "MC_RETURN_FLOOR"):
-        if getattr(config, key, False):
-            raise ValueError(f"BCQ_THRESHOLD with {key} is deliberately out of scope: the BCQ loss launch takes no Monte-Carlo return "
-                             "table; use one or the other")
-    if float(getattr(config, "IQL_EXPECTILE", 0.0) or 0.0) > 0:
-        raise ValueError("BCQ_THRESHOLD with IQL_EXPECTILE > 0 is deliberately out of scope: one extra head sits behind the Q layer, "
-                         "the value head or the policy head; use one or the other")
-    if getattr(config, "DISTRIBUTIONAL", False):
-        raise ValueError("BCQ_THRESHOLD with DISTRIBUTIONAL is deliberately out of scope: one extra head sits behind the Q layer, "
-                         "the spread head or the policy head; use one or the other")
+    for key, val, default in (("BCQ_BC_WEIGHT", bc_weight, 1.0), ("BCQ_LOGIT_REG", logit_reg, 0.01)):
+        if tau < 0 and val != default:
+            raise ValueError(f"{key} has no effect without BCQ_THRESHOLD: it weighs a term of the behaviour head's loss; set "
+                             f"BCQ_THRESHOLD in [0, 1) or leave {key} at {default}")
+    algos.refuse(algos.BCQ, config)
 
 
 def check_nstep(config, world_size: int = 1) -> None:
@@ -617,9 +563,6 @@ def build_helpers(config, dataset, store, model, comm, rank, world_size, log):
     n_step = int(getattr(config, "N_STEP", 1))
     mc_floor, cql_calibrated = bool(getattr(config, "MC_RETURN_FLOOR", False)), bool(getattr(config, "CQL_CALIBRATED", False))
     cql_alpha, target_tau = float(getattr(config, "CQL_ALPHA", 0.0)), float(getattr(config, "TARGET_TAU", 0.0))
-    iql_expectile = float(getattr(config, "IQL_EXPECTILE", 0.0) or 0.0)
-    distributional = bool(getattr(config, "DISTRIBUTIONAL", False))
-    bcq_threshold = float(getattr(config, "BCQ_THRESHOLD", -1.0))
     clip_norm, weight_decay = float(getattr(config, "GRAD_CLIP_NORM", 0.0)), float(getattr(config, "WEIGHT_DECAY", 0.0))
     aug_pad, aug_flip = getattr(config, "AUG_SHIFT_PAD", 0), getattr(config, "AUG_FLIP", False)
     aug_actions, aug_color = getattr(config, "AUG_FLIP_ACTIONS", [1, 2]), tuple(getattr(config, k, 0.0) for k in COLOR_KEYS)
@@ -644,10 +587,7 @@ def build_helpers(config, dataset, store, model, comm, rank, world_size, log):
                         allreduce_errors=((lambda: comm.launch_errors(replay.err_all)) if comm and replay else None),
                         grad_clip_norm=clip_norm, weight_decay=weight_decay, lr_fn=lr_fn, cql_alpha=cql_alpha,
                         target_tau=target_tau, mc_floor=mc_floor, cql_calibrated=cql_calibrated,
-                        iql_expectile=iql_expectile, distributional=distributional,
-                        kl_backwards=bool(getattr(config, "KL_BACKWARDS", False)), log_sigma=bool(getattr(config, "LOG_SIGMA", False)),
-                        sigma_min=float(getattr(config, "DIST_SIGMA_MIN", 0.1)), bcq_threshold=bcq_threshold,
-                        bcq_bc_weight=float(getattr(config, "BCQ_BC_WEIGHT", 1.0)), bcq_logit_reg=float(getattr(config, "BCQ_LOGIT_REG", 0.01)))
+                        **{arg: v for a in algos.ALGOS for arg, v in a.kwargs(config).items()})
     walker = returns = next_row = None
     if n_step > 1 or mc_floor or cql_calibrated:
         from .nstep import successors
@@ -676,17 +616,8 @@ def build_helpers(config, dataset, store, model, comm, rank, world_size, log):
     if target_tau > 0:
         log(f"soft target updates: target <- target + {target_tau:g} * (online - target) inside every Adam launch, the target weights "
             "folded from the average in front of every update; TARGET_UPDATE_INTERVAL is unused")
-    if iql_expectile > 0:
-        log(f"implicit Q-learning: a value head V(s) fitted to Q_target(s, a_data) at expectile {iql_expectile:g}, Q(s, a_data) regressed on "
-            "r + GAMMA (1 - t) V(s') in the loss launch; the target pass runs over s; validation is unchanged")
-    if distributional:
-        log("distributional Q-learning: a Gaussian over the return per (category, action), a spread head behind the Q layer; the loss is KL("
-            + ("prediction || backup" if stepper.dist_flags & 1 else "backup || prediction") + ") against the Double-DQN backup's Gaussian, sigma "
-            + ("= exp(rho)" if stepper.dist_flags & 2 else "= softplus(rho)") + f" with the floor {stepper.sigma_min:g}; validation is unchanged")
-    if bcq_threshold >= 0:
-        log(f"batch-constrained Q-learning: a policy head behind the Q layer fitted to the logged actions (weight {stepper.bcq_bc_weight:g}, "
-            f"logit regulariser {stepper.bcq_logit_reg:g}); the target's arg-max at s' runs over the actions with pi_b / max pi_b > "
-            f"{bcq_threshold:g} under the online head; validation is unchanged")
+    if stepper.algo is not None:
+        log(f"{stepper.algo.title}: {stepper.algo.log(stepper)}; validation is unchanged")
     if cql_alpha > 0:
         log(f"conservative Q-learning: {cql_alpha:g} * (logsumexp_a Q(s, .) - Q(s, a_data)) added to the TD loss in the loss launch")
     if clip_norm > 0 or weight_decay > 0 or lr_fn is not None:
@@ -711,8 +642,7 @@ def build_helpers(config, dataset, store, model, comm, rank, world_size, log):
     return stepper, replay, walker, returns, augmenter
 
 
-HEAD_WORDS = {"value_head": ("implicit Q-learning", "value"), "spread_head": ("distributional Q-learning", "spread"),
-              "policy_head": ("batch-constrained Q-learning", "policy")}
+HEAD_WORDS = {f"{a.head}_head": (a.title, a.head) for a in algos.ALGOS}
 
 
 def restore_state(config, model, stepper, replay, resume_from, rank, world_size, log) -> None:
@@ -782,14 +712,9 @@ def late_scalars(stepper, returns):
         late.append(LateScalar("cql_penalty/train", stepper.cql_penalty, scaled=True))
     if returns is not None:
         late += [LateScalar("mc_floor_share/train", stepper.mc_stats[0:1], scaled=True), LateScalar("q_minus_return/train", stepper.mc_stats[1:2], scaled=True)]
-    if getattr(stepper, "iql_expectile", 0.0) > 0:  # the V loss alone, and the mean advantage of the data action
-        late += [LateScalar("iql_v_loss/train", stepper.iql_stats[0:1], scaled=True), LateScalar("iql_advantage/train", stepper.iql_stats[1:2], scaled=True)]
-    if getattr(stepper, "distributional", False):  # the mean predicted sigma at the data action, and the mean squared standardised error
-        late += [LateScalar("dist_sigma/train", stepper.dist_stats[0:1], scaled=True), LateScalar("dist_z2/train", stepper.dist_stats[1:2], scaled=True)]
-    if getattr(stepper, "bcq", False):  # the behaviour head's cross-entropy, the share of targets the constraint changed, its accuracy
-        late += [LateScalar("bcq_bc_loss/train", stepper.bcq_stats[0:1], scaled=True),
-                 LateScalar("bcq_constrained_share/train", stepper.bcq_stats[1:2], scaled=True),
-                 LateScalar("bcq_accuracy/train", stepper.bcq_stats[2:3], scaled=True)]
+    algo = getattr(stepper, "algo", None)
+    if algo is not None:
+        late += [LateScalar(f"{name}/train", getattr(stepper, algo.stats_attr)[i:i + 1], scaled=True) for i, name in enumerate(algo.stats)]
     return late
 
 
