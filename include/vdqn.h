@@ -332,6 +332,31 @@ int vdqn_bcq_constrain(const float* q_rows, float* q_out /* [batch][C][A] */, fl
  * Q values are not special-cased; a row whose action is outside [0, n_act) adds nothing.  Fails by name before any launch for a
  * null required pointer, batch / n_cat / n_act < 1, n_cat * n_act > ldq, loss_kind outside {0, 1}, acc not 8-byte aligned. */
 int vdqn_td_eval(const vdqn_td_args* a, double* acc, void* stream);
+/* What a head algorithm adds to the held-out metrics (the same unfilled `eval_losses`, train_q_network.py:183-186,240): one launch
+ * adds eight sums per category and one row of per-sample sums into acc_head (device f64 [n_cat + 1][8], 8-byte aligned,
+ * ACCUMULATED into), beside vdqn_td_eval's table, which it leaves alone.  Rows in the layout of the algorithm's loss entry; every
+ * quantity is that loss launch's own f32 statement of it (the same device functions, contraction off) with the scalar gamma, no
+ * importance weight and no per-sample discount; each term is multiplied by vm = use_valid ? valid[b,c] : 1 last and summed in f64 in
+ * vdqn_td_eval's fixed order (n_cat + 1 blocks, no atomics: two runs agree bit for bit).  A row whose action is outside [0, n_act)
+ * adds nothing.  Row c < n_cat, slots 0 .. 7 (symbols as in the loss entries' comments above):
+ *   vdqn_td_eval_iql   q_after_target holds the TARGET network's rows AT S (as vdqn_td_loss_iql's), q_after_online the online rows at s':
+ *                      vm | L_V = omega u^2 | u = Q_target(s, a*) - V(s) | l(d), d = Q(s, a*) - (rew + gamma (1 - term) V(s')), by loss_kind
+ *                      | |d| | V(s) | y | [u > 0]
+ *   vdqn_td_eval_dist  vm | L, the KL in the direction of flags bit 0, clamped at 0 | sqrt(s2) | d^2 / s2 | 0.5 (log s2 + d^2 / s2): the
+ *                      Gaussian NLL of the backup's mean, constant dropped | [d^2 <= s2] (one-sigma coverage: 0.683 when calibrated)
+ *                      | sqrt(v), the backup's sigma | sqrt(var(rho(c, k*))), k* = first arg-max of the means at s
+ *   vdqn_td_eval_bcq   vm | l(d), d against the constrained target | |d| | y | [a' != the free arg-max] | [kc == a*], kc = first maximum
+ *                      of Q(s, c, .) over the actions the logits AT S allow (the policy vdqn_bcq_constrain's read-out deploys)
+ *                      | [kc != the free first arg-max of Q(s, c, .)] | Q(s, c, kc)
+ * Row n_cat: untouched by _iql and _dist; _bcq adds per sample (unweighted, no valid mask, i = the logits at s):
+ *   1 | ce_b | [first arg-max of i == a*] | reg_b | actions allowed at s | softmax(i)[a*] | actions allowed at s' (online logits) | 0
+ * Each fails by name, before any launch, for what its loss entry refuses of the fields it reads: a null required pointer, use_valid
+ * without valid, bad dims, columns that do not fit ldq, batch * ldq >= 2^31, linear != 0, loss_kind outside {0, 1} (_dist: != 0),
+ * its scalars out of range (expectile outside [0.5, 1); unknown flag bits, sigma_min outside [1e-4, 10]; n_act < 2, threshold outside
+ * [0, 1)) and an acc_head that is not 8-byte aligned.  loss, dq, dq_f32, inv_count, dtype, deterministic, q_copy are ignored. */
+int vdqn_td_eval_iql(const vdqn_td_args* a, float expectile, double* acc_head, void* stream);
+int vdqn_td_eval_dist(const vdqn_td_args* a, int32_t flags, float sigma_min, double* acc_head, void* stream);
+int vdqn_td_eval_bcq(const vdqn_td_args* a, float threshold, double* acc_head, void* stream);
 
 /* Ground-truth branch (train_q_network.py:170-178): l = 0.5 (Qb*mask - gt)^2, mask = !isnan(gt) when
  * value_learning, else l = 0.5 (Qb - gt)^2.  gt is f32 [batch][n_cat] (NaN allowed). */
@@ -694,6 +719,18 @@ int vdqn_net_td_forward_bcq(vdqn_net* net, const vdqn_step_args* a, float thresh
  * sample_gamma (validation is one-step whatever the training target, so runs with different N_STEP are judged alike) and
  * acts_samples != 0. */
 int vdqn_net_td_eval(vdqn_net* net, const vdqn_step_args* a, double* acc, void* stream);
+/* vdqn_net_td_eval under a head algorithm (train_q_network.py:183-186,240): everything that entry does into acc, its refusals
+ * included, then the algorithm's head metrics launch (vdqn_td_eval_iql / _dist / _bcq above) into acc_head (device f64
+ * [num_classes + 1][8], accumulated into) behind it on `stream`.  _dist and _bcq read the two Q tensors the first launch read.  _iql
+ * needs Q_target(s, a_data), and acts_target holds `batch` samples: a second target pass runs over the `before` half of the packed
+ * frames into the same workspace, on the side stream BEHIND the first metrics launch (which reads Q_target(s') there), and the head
+ * launch waits for it; the next entry on `stream` opens by making the side stream wait for `stream`, the head launch included.
+ * One more batch-sample forward per validation batch.  Each fails by name, before any launch, for a net without the algorithm's head,
+ * train_on_ground_truth, linear, its scalars out of range as the update's entry (vdqn_net_td_forward_iql / _dist / _bcq) refuses
+ * them, a NULL or misaligned acc_head, and everything vdqn_net_td_eval refuses.  Added without a change of vdqn_abi_version(). */
+int vdqn_net_td_eval_iql(vdqn_net* net, const vdqn_step_args* a, float expectile, double* acc, double* acc_head, void* stream);
+int vdqn_net_td_eval_dist(vdqn_net* net, const vdqn_step_args* a, int32_t flags, float sigma_min, double* acc, double* acc_head, void* stream);
+int vdqn_net_td_eval_bcq(vdqn_net* net, const vdqn_step_args* a, float threshold, double* acc, double* acc_head, void* stream);
 /* Stage s of the backward pass (0: head + layer4, 1: layer3, 2: layer2, layer1, stem).  With the overlap on, the stage's weight
  * gradients and the kernel that writes its range of `grads` run on the engine's side stream: after the call returns that range is
  * complete on vdqn_net_grad_stream(net), NOT on `stream`, which goes straight on to the next stage's data gradients.  The call

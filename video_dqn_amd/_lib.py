@@ -177,6 +177,12 @@ _SIGS = {
     "vdqn_net_create_p": (C.c_int, [C.POINTER(NetConfig), c_i32, c_i32, c_i32, C.POINTER(c_vp)]),
     "vdqn_net_policy_head": (C.c_int, [c_vp]),
     "vdqn_net_td_forward_bcq": (C.c_int, [c_vp, C.POINTER(StepArgs), c_f32, c_f32, c_f32, c_vp, c_vp]),
+    "vdqn_td_eval_iql": (C.c_int, [C.POINTER(TdArgs), c_f32, c_vp, c_vp]),
+    "vdqn_td_eval_dist": (C.c_int, [C.POINTER(TdArgs), c_i32, c_f32, c_vp, c_vp]),
+    "vdqn_td_eval_bcq": (C.c_int, [C.POINTER(TdArgs), c_f32, c_vp, c_vp]),
+    "vdqn_net_td_eval_iql": (C.c_int, [c_vp, C.POINTER(StepArgs), c_f32, c_vp, c_vp, c_vp]),
+    "vdqn_net_td_eval_dist": (C.c_int, [c_vp, C.POINTER(StepArgs), c_i32, c_f32, c_vp, c_vp, c_vp]),
+    "vdqn_net_td_eval_bcq": (C.c_int, [c_vp, C.POINTER(StepArgs), c_f32, c_vp, c_vp, c_vp]),
 }
 COMM_UID_BYTES = 128
 EXPORTS = tuple(_SIGS)

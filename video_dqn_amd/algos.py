@@ -2,7 +2,7 @@
 
 A head algorithm is a loss launch of its own that reads one extra head behind the Q layer.  Its row says, once, what the config
 checks (trainer.check_*), TDStepper, NetEngine, the model and the trainer's log lines and scalars read: its keys, its head, its
-engine entries, its statistics, and why it refuses what it does not cover.  (csrc/engine.hip kAlgos: the same table on the C side.)"""
+engine entries, its statistics, its held-out metrics, and why it refuses what it does not cover.  (csrc/engine.hip kAlgos: the same table on the C side.)"""
 from dataclasses import dataclass
 from typing import Callable, Optional, Tuple
 
@@ -25,6 +25,9 @@ class Algo:
     entry_args: Callable    # ... and its scalars, from the stepper
     stats_attr: str         # the stepper's view of loss_stats[0 : len(stats)] ...
     stats: Tuple            # ... and what its slots hold: the <name>/train scalars
+    eval_entry: str         # the engine entry of one validation batch: vdqn_net_td_eval plus the head metrics launch ...
+    eval_args: Callable     # ... and its scalars, from the stepper
+    eval_slots: Tuple       # what the eight slots of a category's row of the head table hold (slot 0 the count): the <name>/val scalars
     title: str              # its name in log lines
     log: Callable           # stepper -> the rest of its start-up line
     word: str               # "the <word> loss launch"
@@ -33,6 +36,7 @@ class Algo:
     one_action: str = ""    # (min_actions 2) why one action column is refused
     no_loss_kind: Optional[str] = None  # why LOSS_KIND other than l2 is refused
     cql_note: str = ""      # what its refusal of CQL_ALPHA adds
+    eval_sample_slots: Tuple = ()  # what the slots of the head table's per-sample row hold (slot 0 the count); (): the row stays zero
 
     @property
     def head_keys(self):
@@ -53,6 +57,11 @@ ALGOS = (
          head="value", model_arg="value_head", create="vdqn_net_create_v",
          entry="vdqn_net_td_forward_iql", entry_args=lambda s: (s.iql_expectile,),
          stats_attr="iql_stats", stats=("iql_v_loss", "iql_advantage"),  # the V loss alone, the mean advantage of the data action
+         eval_entry="vdqn_net_td_eval_iql", eval_args=lambda s: (s.iql_expectile,),
+         # the expectile loss, Q_target(s, a_data) - V(s), the loss and |error| of Q(s, a_data) against r + GAMMA (1 - t) V(s'), V(s),
+         # that target, the share of positive advantages
+         eval_slots=("count", "iql_v_loss", "iql_advantage", "iql_q_loss", "iql_td_abs_error", "iql_value", "iql_td_target",
+                     "iql_positive_share"),
          title="implicit Q-learning",
          log=lambda s: f"a value head V(s) fitted to Q_target(s, a_data) at expectile {s.iql_expectile:g}, Q(s, a_data) regressed on "
                        "r + GAMMA (1 - t) V(s') in the loss launch; the target pass runs over s",
@@ -65,6 +74,10 @@ ALGOS = (
          head="spread", model_arg="distributional", create="vdqn_net_create_d",
          entry="vdqn_net_td_forward_dist", entry_args=lambda s: (s.dist_flags, s.sigma_min),
          stats_attr="dist_stats", stats=("dist_sigma", "dist_z2"),  # mean predicted sigma at the data action, mean squared standardised error
+         eval_entry="vdqn_net_td_eval_dist", eval_args=lambda s: (s.dist_flags, s.sigma_min),
+         # the KL, the predicted sigma, the squared standardised error, the Gaussian NLL of the backup's mean (constant dropped), the
+         # one-sigma coverage (0.683 when calibrated), the backup's sigma, the predicted sigma of the greedy action
+         eval_slots=("count", "dist_kl", "dist_sigma", "dist_z2", "dist_nll", "dist_coverage", "dist_backup_sigma", "dist_greedy_sigma"),
          title="distributional Q-learning",
          log=lambda s: "a Gaussian over the return per (category, action), a spread head behind the Q layer; the loss is KL("
                        + ("prediction || backup" if s.dist_flags & 1 else "backup || prediction") + ") against the Double-DQN backup's Gaussian, sigma "
@@ -76,6 +89,14 @@ ALGOS = (
          head="policy", model_arg="policy_head", create="vdqn_net_create_p",
          entry="vdqn_net_td_forward_bcq", entry_args=lambda s: (s.bcq_threshold, s.bcq_bc_weight, s.bcq_logit_reg),
          stats_attr="bcq_stats", stats=("bcq_bc_loss", "bcq_constrained_share", "bcq_accuracy"),  # (share: of targets the constraint changed)
+         eval_entry="vdqn_net_td_eval_bcq", eval_args=lambda s: (s.bcq_threshold,),
+         # the loss and |error| against the constrained target, that target, the share of targets the constraint changes, the agreement
+         # of the constrained policy at s with the data, the share of states where the constraint changes the greedy action, its Q
+         eval_slots=("count", "bcq_q_loss", "bcq_td_abs_error", "bcq_td_target", "bcq_constrained_share", "bcq_policy_agreement",
+                     "bcq_policy_changed", "bcq_q_policy"),
+         # per sample: the cross-entropy, the behaviour accuracy, mean_a i_a^2, the allowed actions at s, pi_b(a_data), the allowed at s'
+         eval_sample_slots=("samples", "bcq_bc_loss", "bcq_accuracy", "bcq_logit_sq", "bcq_allowed_actions", "bcq_data_prob",
+                            "bcq_allowed_actions_next"),
          title="batch-constrained Q-learning",
          log=lambda s: f"a policy head behind the Q layer fitted to the logged actions (weight {s.bcq_bc_weight:g}, "
                        f"logit regulariser {s.bcq_logit_reg:g}); the target's arg-max at s' runs over the actions with pi_b / max pi_b > "
@@ -84,6 +105,7 @@ ALGOS = (
          min_actions=2, one_action="and with one action there is nothing to constrain"),
 )
 IQL, DIST, BCQ = ALGOS
+HEAD_EVAL_SLOTS = 8  # of a row of the head table, f64 [num_classes + 1][8] (csrc/eval.hip)
 LOSS_SLOTS = 4  # of TDStepper.loss_stats: the TD family's cql_penalty and mc_stats side by side, or a head algorithm's statistics
 
 
@@ -115,3 +137,8 @@ def refuse(algo: Algo, config, say=str, error=ValueError, prefix="") -> None:
             a, b = sorted((algo, other), key=ALGOS.index)
             raise error(f"{prefix}{say(b.key)} with {a.on_text.replace(a.key, say(a.key))} is deliberately out of scope: one extra head "
                         f"sits behind the Q layer, the {a.head} head or the {b.head} head; use one or the other")
+
+
+def eval_tags(algo: Algo) -> Tuple:
+    """((scalar tag, key of eval_result()["head"]), ..) of `algo`'s held-out metrics: <slot name>/val, the counts left out."""
+    return tuple((f"{name}/val", name) for name in algo.eval_slots[1:] + algo.eval_sample_slots[1:])

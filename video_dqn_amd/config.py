@@ -77,7 +77,8 @@ evaluated; 0.7 is the usual setting, 0.5 fits the mean; the target pass runs ove
 logs iql_v_loss/train and iql_advantage/train, the mean of Q_target(s, a_data) - V(s); the TD branch with three action columns and
 without LINEAR; not together with CQL_ALPHA, CQL_CALIBRATED or MC_RETURN_FLOOR; composes with N_STEP, PRIORITIZED_REPLAY, AUG_*
 and TARGET_TAU; checkpoints keep the reference's keys and shapes and carry the head under a key of their own, `value_head`;
-validation is unchanged, the one-step Double-DQN metrics on the Q columns), DISTRIBUTIONAL / KL_BACKWARDS / LOG_SIGMA (the
+validation adds iql_v_loss/val, iql_advantage/val, iql_q_loss/val and the rest of the value head's held-out metrics to the one-step
+Double-DQN metrics on the Q columns), DISTRIBUTIONAL / KL_BACKWARDS / LOG_SIGMA (the
 reference's keys, defaults.py:34-36, all False = off) and DIST_SIGMA_MIN (0.1; in [1e-4, 10]): Gaussian distributional Q-learning —
 the network gets a spread head, one more row of its Q layer per Q column stored as spread.weight / spread.bias, so that every
 (category, action) carries a mean (the Q column, as ever) and a variance sigma^2 + DIST_SIGMA_MIN^2 with sigma = softplus(rho), or
@@ -90,7 +91,9 @@ returns (B, C, A, 2) = mean and variance, what the reference's visualize_value.p
 DISTRIBUTIONAL is refused (no effect); the TD branch without LINEAR and with LOSS_KIND l2; not together with CQL_ALPHA,
 CQL_CALIBRATED, MC_RETURN_FLOOR or IQL_EXPECTILE (deliberately out of scope); composes with N_STEP, PRIORITIZED_REPLAY, AUG_*,
 TARGET_TAU, ONE_ACTION, both architectures and N ranks; checkpoints keep the reference's keys and shapes and carry the head, its
-Adam moments and under TARGET_TAU its target rows under a key of their own, `spread_head`; validation is unchanged),
+Adam moments and under TARGET_TAU its target rows under a key of their own, `spread_head`; validation adds dist_kl/val,
+dist_sigma/val, dist_z2/val, dist_nll/val, dist_coverage/val — 0.683 when the spread is calibrated — and the backup's and the greedy
+action's sigma),
 BCQ_THRESHOLD (-1.0 = off; tau in [0, 1), 0.3 in the paper), BCQ_BC_WEIGHT (1.0; > 0) and BCQ_LOGIT_REG (0.01; >= 0): discrete
 batch-constrained Q-learning (BCQ, Fujimoto et al. 2019) — the network gets a policy head, one more row of its Q layer per action
 stored as policy.weight / policy.bias, whose logits i(a) are fitted to the logged action by cross-entropy (weight BCQ_BC_WEIGHT,
@@ -104,7 +107,8 @@ defaults without BCQ_THRESHOLD is refused (no effect); the TD branch without LIN
 with CQL_ALPHA, CQL_CALIBRATED, MC_RETURN_FLOOR, IQL_EXPECTILE or DISTRIBUTIONAL (deliberately out of scope); composes with N_STEP,
 PRIORITIZED_REPLAY, AUG_* (AUG_FLIP exchanges the action labels before the loss, so the behaviour target follows it), TARGET_TAU,
 LOSS_KIND huber, both architectures and N ranks; checkpoints keep the reference's keys and shapes and carry the head and its Adam
-moments under a key of their own, `policy_head`; validation is unchanged).
+moments under a key of their own, `policy_head`; validation adds bcq_bc_loss/val, bcq_accuracy/val, bcq_constrained_share/val,
+bcq_policy_agreement/val — the constrained policy at s against the logged action — and the rest of the policy head's held-out metrics).
 """
 from __future__ import annotations
 

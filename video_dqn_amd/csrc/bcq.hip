@@ -33,62 +33,9 @@
 
 #include "block_sum.h"
 #include "common.h"
+#include "bcq_math.h"  // bcq_kernel_args, bcq_logit_max, bcq_allowed, bcq_choice, bcq_error_of, bcq_logit_walk: shared with eval.hip
 
 namespace {
-
-struct bcq_kernel_args : vdqn_td_args {
-  const float* w;   // [batch] or NULL (= 1)
-  float* err;       // [batch] or NULL
-  const float* sg;  // [batch] per-sample discount or NULL (= gamma)
-  float* stats;     // f32[3] or NULL
-  float lt;         // (float)log((double)threshold), -inf for 0
-  float bc_weight, logit_reg;
-};
-
-// The allowed set: action a of a row of logits is allowed iff (logits[a] - max logits) > lt.  The only statement of the constraint
-// (the loss's target and vdqn_bcq_constrain both take it from here).
-__device__ __forceinline__ float bcq_logit_max(const float* logits, int n_act) {
-  float m = logits[0];
-#pragma clang loop unroll(disable) vectorize(disable) interleave(disable)
-  for (int k = 1; k < n_act; ++k) m = fmaxf(m, logits[k]);
-  return m;
-}
-__device__ __forceinline__ bool bcq_allowed(const float* logits, int a, float m, float lt) { return (logits[a] - m) > lt; }
-
-// a': the first maximum of the online Q(s') of category c over the allowed actions; *free_best: over all actions (torch.argmax;
-// td_error_of's loop), m the largest logit of the row (bcq_logit_max: the same for every category of the sample).  Should no action
-// pass (logits that are not numbers), a' is the free arg-max: the index stays inside the row.
-__device__ __forceinline__ int bcq_choice(const bcq_kernel_args& a, int b, int c, float m, int* free_best = nullptr) {
-  const float* qo = a.q_after_online + (size_t)b * a.ldq + c * a.n_act;
-  const float* lg = a.q_after_online + (size_t)b * a.ldq + a.n_cat * a.n_act;
-  int best = -1, fb = 0;
-  float bv = 0.f, fv = qo[0];
-#pragma clang loop unroll(disable) vectorize(disable) interleave(disable)
-  for (int k = 0; k < a.n_act; ++k) {  // (selects, no branches: strict comparisons, the first maximum wins)
-    const float v = qo[k];
-    const bool up = k > 0 && v > fv;
-    fv = up ? v : fv;
-    fb = up ? k : fb;
-    const bool take = bcq_allowed(lg, k, m, a.lt) && (best < 0 || v > bv);
-    bv = take ? v : bv;
-    best = take ? k : best;
-  }
-  if (free_best) *free_best = fb;
-  return best < 0 ? fb : best;
-}
-
-// d = Q(s)[b, c*A + a*] - y, y from the target network at a' in td_error_of's expression order.  Every product and sum rounds on
-// its own (no contraction into a fused multiply-add): what td_loss_kernel's instances evaluate.
-__device__ __forceinline__ float bcq_error_of(const bcq_kernel_args& a, int b, int c, int act, float gamma, int best) {
-#pragma clang fp contract(off)
-  const float qb = a.q_before[(size_t)b * a.ldq + c * a.n_act + act];
-  float qa = a.q_after_target[(size_t)b * a.ldq + c * a.n_act + best];
-  qa = qa * (1.0f - a.term[b * a.n_cat + c]);
-  const float r = a.rew[b * a.n_cat + c];
-  float y = r + gamma * qa;
-  if (a.clip_rect) y = fminf(fmaxf(y, 0.f), 1.f);
-  return qb - y;
-}
 
 template <typename T>
 __global__ __launch_bounds__(256) void bcq_loss_kernel(const bcq_kernel_args a) {
@@ -132,16 +79,9 @@ __global__ __launch_bounds__(256) void bcq_loss_kernel(const bcq_kernel_args a) 
       const int ac = col - nq;
       const float* lg = a.q_before + (size_t)b * a.ldq + nq;
       const float m = bcq_logit_max(lg, a.n_act);
-      float S = 0.f, sq = 0.f, top = lg[0];
-      int first = 0;
-#pragma clang loop unroll(disable) vectorize(disable) interleave(disable)
-      for (int k = 0; k < a.n_act; ++k) {  // the softmax's sum, the sum of squares and the first arg-max in one walk
-        const float v = lg[k];
-        S += expf(v - m);
-        sq += v * v;
-        first = v > top ? k : first;
-        top = v > top ? v : top;
-      }
+      float S, sq;
+      int first;
+      bcq_logit_walk(lg, a.n_act, m, &S, &sq, &first);  // the softmax's sum, the sum of squares and the first arg-max in one walk
       const float x = lg[ac];
       const float hit = ac == act ? 1.0f : 0.0f;
       float dl = a.bc_weight * ((expf(x - m) / S - hit) + a.logit_reg * ((2.0f * x) / (float)a.n_act));
@@ -202,8 +142,6 @@ __global__ __launch_bounds__(256) void bcq_constrain_kernel(const float* __restr
     prob_out[(size_t)b * n_act + (j - nq)] = expf(lg[j - nq] - m) / S;
   }
 }
-
-inline float bcq_log_threshold(float threshold) { return threshold > 0.f ? (float)log((double)threshold) : -INFINITY; }
 
 }  // namespace
 

@@ -414,6 +414,7 @@ struct LossSpec {
 // One row per LossAlgo; the TD family's is that of vdqn_net_td_forward_mc, its one entry with statistics and row refusals.
 struct AlgoRow {
   const char* entry;
+  const char* eval_entry;        // its validation batch: vdqn_net_td_eval plus the head metrics launch (NULL: the TD family's is vdqn_net_td_eval alone)
   Head head;                     // the head the net must carry
   const char *no_gt, *no_linear;  // why train_on_ground_truth and linear are refused
   int n_stats;
@@ -421,23 +422,25 @@ struct AlgoRow {
 };
 const char kNoBootstrap[] = "the ground-truth branch regresses Q(s, a) on given targets and bootstraps nothing (train_on_ground_truth)";
 const AlgoRow kAlgos[] = {
-    {"vdqn_net_td_forward_mc", HEAD_NONE, "mc_return is given, but the ground-truth branch has no target to floor and no penalty to calibrate (train_on_ground_truth)",
+    {"vdqn_net_td_forward_mc", nullptr, HEAD_NONE, "mc_return is given, but the ground-truth branch has no target to floor and no penalty to calibrate (train_on_ground_truth)",
      "mc_return is given with linear: y = r + (Qa - 0.1) has no discount, and a discounted return bounds nothing of it", 2, false},
-    {"vdqn_net_td_forward_iql", HEAD_VALUE, kNoBootstrap,
+    {"vdqn_net_td_forward_iql", "vdqn_net_td_eval_iql", HEAD_VALUE, kNoBootstrap,
      "linear: y = r + (Qa - 0.1) is the reference's undiscounted Double-DQN target and has no V(s') form", 2, true},
-    {"vdqn_net_td_forward_dist", HEAD_SPREAD, kNoBootstrap,
+    {"vdqn_net_td_forward_dist", "vdqn_net_td_eval_dist", HEAD_SPREAD, kNoBootstrap,
      "linear: y = r + (Qa - 0.1) is the reference's undiscounted Double-DQN target; a variance has no backup without a discount", 2, false},
-    {"vdqn_net_td_forward_bcq", HEAD_POLICY, kNoBootstrap,
+    {"vdqn_net_td_forward_bcq", "vdqn_net_td_eval_bcq", HEAD_POLICY, kNoBootstrap,
      "linear: y = r + (Qa - 0.1) is the reference's undiscounted Double-DQN target; the constrained target is not defined for it", 3, false},
 };
 LossSpec loss_spec(LossAlgo algo, float* stats) { return {algo, stats, kAlgos[algo].n_stats}; }  // (the rest zero)
-// the refusals every row shares: the net lacks the row's head, the ground-truth branch, linear
-int refuse_by_row(const AlgoRow& r, const vdqn_net* net, const vdqn_step_args* a) {
+// the refusals every row shares: the net lacks the row's head, the ground-truth branch, linear; in the name of `entry` (NULL: the
+// row's update entry)
+int refuse_by_row(const AlgoRow& r, const vdqn_net* net, const vdqn_step_args* a, const char* entry = nullptr) {
+  if (!entry) entry = r.entry;
   static const char* const head_word[] = {"", "value", "spread", "policy"};
   static const char* const head_create[] = {"", "vdqn_net_create_v(cfg, 1, ..)", "vdqn_net_create_d(cfg, 0, 1, ..)", "vdqn_net_create_p(cfg, 0, 0, 1, ..)"};
-  VDQN_CHECK(r.head == HEAD_NONE || net->head == r.head, "%s: the net has no %s head (create it with %s)", r.entry, head_word[r.head], head_create[r.head]);
-  VDQN_CHECK(!a->train_on_ground_truth, "%s: %s", r.entry, r.no_gt);
-  VDQN_CHECK(!a->linear, "%s: %s", r.entry, r.no_linear);
+  VDQN_CHECK(r.head == HEAD_NONE || net->head == r.head, "%s: the net has no %s head (create it with %s)", entry, head_word[r.head], head_create[r.head]);
+  VDQN_CHECK(!a->train_on_ground_truth, "%s: %s", entry, r.no_gt);
+  VDQN_CHECK(!a->linear, "%s: %s", entry, r.no_linear);
   return VDQN_OK;
 }
 
@@ -652,6 +655,79 @@ extern "C" int vdqn_net_td_eval(vdqn_net* net, const vdqn_step_args* a, double* 
   const float* qf_online = reinterpret_cast<const float*>(ao + A.qf);
   const vdqn_td_args t = fill_td_args(net, a, qf_online, reinterpret_cast<const float*>(at + T.qf), B);
   return vdqn_td_eval(&t, acc, st);
+}
+
+// One held-out batch under a head algorithm: everything vdqn_net_td_eval does, its refusals included, and behind its metrics launch
+// the row's head metrics launch (csrc/eval.hip) into acc_head (device f64 [num_classes + 1][8], accumulated into).  Every refusal of
+// the entry, the row (refuse_by_row) and the head operator's scalars comes before any launch.
+namespace {
+struct HeadEval {
+  vdqn_td_args t;
+  hipStream_t st;
+  const unsigned char* t_in;  // the packed frames of [s; s'] in acts_online
+  unsigned char* at;
+  ActLayout T;
+};
+// vdqn_net_td_eval, then what the head launch needs: the operator's arguments on the two qf tensors, and where the target pass lives
+int head_eval_begin(vdqn_net* net, const vdqn_step_args* a, double* acc, const double* acc_head, LossAlgo algo, HeadEval* h, void* stream) {
+  const char* entry = kAlgos[algo].eval_entry;
+  VDQN_CHECK(acc_head, "%s: null arg", entry);
+  VDQN_CHECK((((uintptr_t)acc_head) & 7) == 0, "%s: acc_head must be 8-byte aligned", entry);
+  RC(vdqn_net_td_eval(net, a, acc, stream));
+  const int B = a->batch;
+  const ActLayout A = act_layout(net, 2 * B);
+  unsigned char* ao = (unsigned char*)a->acts_online;
+  h->st = (hipStream_t)stream;
+  h->t_in = ao + A.t_in;
+  h->at = (unsigned char*)a->acts_target;
+  h->T = act_layout(net, B);
+  h->t = fill_td_args(net, a, reinterpret_cast<const float*>(ao + A.qf), reinterpret_cast<const float*>(h->at + h->T.qf), B);
+  return VDQN_OK;
+}
+}  // namespace
+
+// IQL's head metrics read Q_target(s, a_data), and acts_target holds one pass of `batch` samples, so a SECOND target pass runs over
+// the `before` half of the packed frames into the same workspace.  The ordering, with the overlap on (off: one stream, program order):
+//   1. vdqn_net_td_eval's metrics launch, on `stream`, reads Q_target(s') in acts_target.  fork() behind it makes the side stream
+//      wait for everything queued on `stream` so far, that launch included, so the second pass overwrites acts_target only after it
+//      was read.  (The side stream's own order puts the second pass behind the first.)
+//   2. join() makes `stream` wait for the second pass; the head launch, on `stream`, then reads Q_target(s).
+//   3. The next batch's entry (this one, vdqn_net_td_eval or an update's vdqn_net_td_forward*) opens with fork(net, stream): its
+//      pack, which rewrites the packed frames the second pass read, and its target pass, which rewrites acts_target, wait for
+//      everything on `stream`, the head launch included.  Its online pass follows the head launch on `stream` itself.
+// The packed frames are written by nobody between the pack and step 3, and the online pass only reads them.
+extern "C" int vdqn_net_td_eval_iql(vdqn_net* net, const vdqn_step_args* a, float expectile, double* acc, double* acc_head, void* stream) {
+  VDQN_CHECK(net && a, "vdqn_net_td_eval_iql: null arg");
+  RC(refuse_by_row(kAlgos[ALGO_IQL], net, a, kAlgos[ALGO_IQL].eval_entry));
+  VDQN_CHECK(isfinite(expectile) && expectile >= 0.5f && expectile < 1.0f, "vdqn_net_td_eval_iql: expectile %g must be in [0.5, 1)", (double)expectile);
+  HeadEval h;
+  RC(head_eval_begin(net, a, acc, acc_head, ALGO_IQL, &h, stream));
+  hipStream_t tst = fork(net, h.st);  // == st when the overlap is off; behind the metrics launch that read Q_target(s')
+  RC(forward_impl(net, (const unsigned char*)a->packed_target, h.t_in, a->batch, h.at, h.T, tst, false, 0));  // the target over s
+  if (tst != h.st) join(net, net->side, h.st);
+  return vdqn_td_eval_iql(&h.t, expectile, acc_head, h.st);
+}
+
+// DIST and BCQ read the two qf tensors vdqn_net_td_eval's launch has just read: one more launch on `stream`, nothing to order.
+extern "C" int vdqn_net_td_eval_dist(vdqn_net* net, const vdqn_step_args* a, int32_t flags, float sigma_min, double* acc, double* acc_head, void* stream) {
+  VDQN_CHECK(net && a, "vdqn_net_td_eval_dist: null arg");
+  RC(refuse_by_row(kAlgos[ALGO_DIST], net, a, kAlgos[ALGO_DIST].eval_entry));
+  VDQN_CHECK(a->loss_kind == 0, "vdqn_net_td_eval_dist: loss_kind %d: the loss is a KL divergence, which has no Huber form (loss_kind must be 0)", a->loss_kind);
+  VDQN_CHECK((flags & ~3) == 0, "vdqn_net_td_eval_dist: flags 0x%x has unknown bits (bit 0 = KL_BACKWARDS, bit 1 = LOG_SIGMA)", (unsigned)flags);
+  VDQN_CHECK(isfinite(sigma_min) && sigma_min >= 1e-4f && sigma_min <= 10.0f, "vdqn_net_td_eval_dist: sigma_min %g must be in [1e-4, 10]", (double)sigma_min);
+  HeadEval h;
+  RC(head_eval_begin(net, a, acc, acc_head, ALGO_DIST, &h, stream));
+  return vdqn_td_eval_dist(&h.t, flags, sigma_min, acc_head, h.st);
+}
+
+extern "C" int vdqn_net_td_eval_bcq(vdqn_net* net, const vdqn_step_args* a, float threshold, double* acc, double* acc_head, void* stream) {
+  VDQN_CHECK(net && a, "vdqn_net_td_eval_bcq: null arg");
+  RC(refuse_by_row(kAlgos[ALGO_BCQ], net, a, kAlgos[ALGO_BCQ].eval_entry));
+  VDQN_CHECK(net->cfg.action_dim >= 2, "vdqn_net_td_eval_bcq: action_dim is 1: with one action there is nothing to constrain");
+  VDQN_CHECK(isfinite(threshold) && threshold >= 0.0f && threshold < 1.0f, "vdqn_net_td_eval_bcq: threshold %g must be in [0, 1)", (double)threshold);
+  HeadEval h;
+  RC(head_eval_begin(net, a, acc, acc_head, ALGO_BCQ, &h, stream));
+  return vdqn_td_eval_bcq(&h.t, threshold, acc_head, h.st);
 }
 
 namespace {

@@ -21,30 +21,9 @@
 
 #include "block_sum.h"
 #include "common.h"
+#include "iql_math.h"  // iql_kernel_args, iql_error_of, iql_omega: shared with the held-out head metrics (eval.hip)
 
 namespace {
-
-struct iql_kernel_args : vdqn_td_args {
-  const float* w;   // [batch] or NULL (= 1)
-  float* err;       // [batch] or NULL
-  const float* sg;  // [batch] per-sample discount or NULL (= gamma)
-  float* stats;     // f32[2] or NULL
-  float tau;
-};
-
-// d = Q(s)[b, Q(c, a*)] - y with the bootstrap taken from V(s').  Every product and sum rounds on its own (no contraction into a
-// fused multiply-add): that is what td_loss_kernel's instances evaluate, where the addition of r sits behind the select between the
-// LINEAR and the discounted form, and what makes this launch's Q part the weighted TD loss bit for bit (tests/test_gpu_iql.py).
-__device__ __forceinline__ float iql_error_of(const iql_kernel_args& a, int b, int c, int act, float gamma) {
-#pragma clang fp contract(off)
-  const float qb = a.q_before[(size_t)b * a.ldq + c * a.n_act + act];
-  float qa = a.q_after_online[(size_t)b * a.ldq + a.n_cat * a.n_act + c];
-  qa = qa * (1.0f - a.term[b * a.n_cat + c]);
-  const float r = a.rew[b * a.n_cat + c];
-  float y = r + gamma * qa;
-  if (a.clip_rect) y = fminf(fmaxf(y, 0.f), 1.f);
-  return qb - y;
-}
 
 template <typename T>
 __global__ __launch_bounds__(256) void iql_loss_kernel(const iql_kernel_args a) {
@@ -83,7 +62,7 @@ __global__ __launch_bounds__(256) void iql_loss_kernel(const iql_kernel_args a) 
       const float v = a.q_before[(size_t)b * a.ldq + col];
       const float qt = a.q_after_target[(size_t)b * a.ldq + c * a.n_act + act];
       const float u = qt - v;
-      const float om = u > 0.f ? a.tau : 1.0f - a.tau;
+      const float om = iql_omega(u, a.tau);
       float lv = om * u * u;
       float dv = -2.0f * om * u;
       const float vm = a.use_valid ? a.valid[b * a.n_cat + c] : 1.0f;

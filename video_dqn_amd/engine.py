@@ -20,7 +20,7 @@ from typing import Dict, Optional
 import torch
 
 from . import _lib
-from .algos import ALGOS, BCQ, LOSS_SLOTS, MODIFIERS, refuse
+from .algos import ALGOS, BCQ, HEAD_EVAL_SLOTS, LOSS_SLOTS, MODIFIERS, refuse
 
 LOSS_KINDS = {"l2": 0, "huber": 1}  # vdqn_td_args.loss_kind
 
@@ -503,6 +503,7 @@ class TDStepper:
             if self.target_tau > 0:
                 self.target_params = torch.empty_like(net.params)
         self.eval_acc = None   # f64 [num_classes][8] metric sums of the validation pass, allocated by the first eval_begin
+        self.eval_head_acc = None  # f64 [num_classes + 1][8], the head algorithm's sums beside them (None without one)
         self.val_history = []  # (update number, eval_result()) of every validation pass the trainer ran
         self.adam_step = 0
         self.sample_number = 0
@@ -770,6 +771,11 @@ class TDStepper:
                 self.eval_acc = torch.zeros((n.num_classes, 8), dtype=torch.float64, device=n.device)
             else:
                 self.eval_acc.zero_()
+            if self.algo is not None:  # the head table: the algorithm's own metrics, summed by a second launch per batch
+                if self.eval_head_acc is None:
+                    self.eval_head_acc = torch.zeros((n.num_classes + 1, HEAD_EVAL_SLOTS), dtype=torch.float64, device=n.device)
+                else:
+                    self.eval_head_acc.zero_()
 
     def eval_batch(self, before, after, src_kind, act, rew, term, valid=None):
         """Queue one held-out batch of 1 .. B samples behind `eval_begin`: the online pass over [s; s'], the target pass over s' and
@@ -785,15 +791,29 @@ class TDStepper:
         with torch.cuda.device(self.net.device):
             a = self._args(before, after, src_kind, act, rew, term, valid if valid is not None else self._ones, None)
             a.batch = nb
-            _lib.check(self.lib.vdqn_net_td_eval(self.net.handle, C.byref(a), self.eval_acc.data_ptr(), _stream()), "vdqn_net_td_eval")
+            if self.algo is not None:  # vdqn_net_td_eval and, behind its launch, the row's head metrics into eval_head_acc
+                entry, args = self.algo.eval_entry, (*self.algo.eval_args(self), self.eval_acc.data_ptr(), self.eval_head_acc.data_ptr())
+            else:
+                entry, args = "vdqn_net_td_eval", (self.eval_acc.data_ptr(),)
+            _lib.check(getattr(self.lib, entry)(self.net.handle, C.byref(a), *args, _stream()), entry)
         del keep
 
     def eval_result(self) -> dict:
         """Synchronise once and return the pass's means: {name: slot total / count} over all categories, {name + '_cat': [per
-        category]}, 'count' (the number of valid (sample, category) terms) and 'table' (the raw f64 [num_classes][8] sums, CPU)."""
+        category]}, 'count' (the number of valid (sample, category) terms) and 'table' (the raw f64 [num_classes][8] sums, CPU).
+        Under a head algorithm also 'head': the same over the algorithm's eval_slots from the head table's category rows, for BCQ
+        the means of eval_sample_slots over 'samples' from its per-sample row, and 'table' (f64 [num_classes + 1][8], CPU)."""
         if self.eval_acc is None:
             raise _lib.VdqnError("TDStepper.eval_result: call eval_begin first")
-        table = self.eval_acc.cpu()  # (the one synchronisation of the pass)
+        if self.algo is not None:  # both tables in one copy: the one synchronisation of the pass
+            both = torch.cat([self.eval_acc, self.eval_head_acc]).cpu()
+            table, head = both[:self.eval_acc.shape[0]].clone(), both[self.eval_acc.shape[0]:].clone()
+            out = self._eval_means(table)
+            out["head"] = self._head_means(head)
+            return out
+        return self._eval_means(self.eval_acc.cpu())  # (the one synchronisation of the pass)
+
+    def _eval_means(self, table) -> dict:
         total = table.sum(0)
         nan = float("nan")
         out = {"count": float(total[0]), "count_cat": [float(x) for x in table[:, 0]], "table": table}
@@ -802,6 +822,21 @@ class TDStepper:
                 continue
             out[name] = float(total[k] / total[0]) if total[0] > 0 else nan
             out[name + "_cat"] = [float(table[c, k] / table[c, 0]) if table[c, 0] > 0 else nan for c in range(table.shape[0])]
+        return out
+
+    def _head_means(self, head) -> dict:
+        """eval_result()['head'] from the head table (CPU): the category rows as _eval_means reads its table, the per-sample row."""
+        nan = float("nan")
+        cats, per = head[:-1], head[-1]
+        total = cats.sum(0)
+        out = {"count": float(total[0]), "count_cat": [float(x) for x in cats[:, 0]], "table": head}
+        for k, name in enumerate(self.algo.eval_slots):
+            if k == 0:
+                continue
+            out[name] = float(total[k] / total[0]) if total[0] > 0 else nan
+            out[name + "_cat"] = [float(cats[c, k] / cats[c, 0]) if cats[c, 0] > 0 else nan for c in range(cats.shape[0])]
+        for k, name in enumerate(self.algo.eval_sample_slots):
+            out[name] = float(per[0]) if k == 0 else (float(per[k] / per[0]) if per[0] > 0 else nan)
         return out
 
     @staticmethod

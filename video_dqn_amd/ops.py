@@ -412,6 +412,59 @@ def td_eval(q_before, q_after_online, q_after_target, act, rew, term, valid=None
     return acc
 
 
+def _eval_args(q_before, q_after_online, q_after_target, act, rew, term, valid, n_cat, n_act, gamma, clip_rect, linear, loss_kind):
+    a = _lib.TdArgs()
+    a.q_before, a.q_after_online, a.q_after_target = _ptr(q_before), _ptr(q_after_online), _ptr(q_after_target)
+    a.act, a.rew, a.term, a.valid = _ptr(act), _ptr(rew), _ptr(term), _ptr(valid)
+    a.batch, a.n_cat, a.n_act, a.ldq = q_before.shape[0], n_cat, n_act, q_before.shape[1]
+    a.gamma = gamma
+    a.clip_rect, a.linear, a.use_valid = int(clip_rect), int(linear), int(valid is not None)
+    a.loss_kind = LOSS_KINDS[loss_kind]
+    return a
+
+
+def _head_acc(acc, n_cat, device):
+    return torch.zeros((n_cat + 1, 8), dtype=torch.float64, device=device) if acc is None else acc
+
+
+def td_eval_iql(q_before, q_after_online, q_target_before, act, rew, term, valid=None, *, expectile, acc=None, n_cat=5, n_act=3, gamma=0.99,
+                clip_rect=True, linear=False, loss_kind="l2"):
+    """Held-out metrics of the implicit Q-learning head (vdqn_td_eval_iql), rows in td_loss_iql's layout; q_target_before: the TARGET
+    network at s.  Eight f64 sums per category — count, the expectile loss, Q_target(s, act) - V(s), the Q loss and |error| against rew +
+    gamma (1 - term) V(s'), V(s), that target, [advantage > 0] — ADDED into acc (f64 [n_cat + 1, 8] on the device, the last row
+    untouched; None: a fresh table of zeros).  Returns acc."""
+    acc = _head_acc(acc, n_cat, q_before.device)
+    a = _eval_args(q_before, q_after_online, q_target_before, act, rew, term, valid, n_cat, n_act, gamma, clip_rect, linear, loss_kind)
+    _lib.check(_lib.load().vdqn_td_eval_iql(C.byref(a), float(expectile), _ptr(acc), _stream()), "vdqn_td_eval_iql")
+    return acc
+
+
+def td_eval_dist(q_before, q_after_online, q_after_target, act, rew, term, valid=None, *, kl_backwards=False, log_sigma=False, sigma_min=0.1,
+                 flags=None, acc=None, n_cat=5, n_act=3, gamma=0.99, clip_rect=True, linear=False, loss_kind="l2"):
+    """Held-out metrics of the distributional head (vdqn_td_eval_dist), rows in td_loss_dist's layout.  Eight f64 sums per category —
+    count, the KL, the predicted sigma, the squared standardised error, the Gaussian NLL of the backup's mean (constant dropped), the
+    one-sigma coverage, the backup's sigma, the predicted sigma of the greedy action — ADDED into acc (f64 [n_cat + 1, 8] on the
+    device, the last row untouched; None: a fresh table of zeros).  Returns acc."""
+    acc = _head_acc(acc, n_cat, q_before.device)
+    a = _eval_args(q_before, q_after_online, q_after_target, act, rew, term, valid, n_cat, n_act, gamma, clip_rect, linear, loss_kind)
+    _lib.check(_lib.load().vdqn_td_eval_dist(C.byref(a), dist_flags(kl_backwards, log_sigma) if flags is None else int(flags), float(sigma_min),
+                                             _ptr(acc), _stream()), "vdqn_td_eval_dist")
+    return acc
+
+
+def td_eval_bcq(q_before, q_after_online, q_after_target, act, rew, term, valid=None, *, threshold=0.3, acc=None, n_cat=5, n_act=3,
+                gamma=0.99, clip_rect=True, linear=False, loss_kind="l2"):
+    """Held-out metrics of the BCQ policy head (vdqn_td_eval_bcq), rows in td_loss_bcq's layout.  Eight f64 sums per category — count,
+    the loss and |error| against the constrained target, that target, [the constraint changes the target's action], [the constrained
+    policy at s picks act], [the constraint changes the greedy action at s], the constrained policy's Q — and in the last row per
+    sample: count, cross-entropy, [arg-max of the logits == act], mean squared logit, allowed actions at s, softmax(logits)[act],
+    allowed actions at s', 0 — ADDED into acc (f64 [n_cat + 1, 8] on the device; None: a fresh table of zeros).  Returns acc."""
+    acc = _head_acc(acc, n_cat, q_before.device)
+    a = _eval_args(q_before, q_after_online, q_after_target, act, rew, term, valid, n_cat, n_act, gamma, clip_rect, linear, loss_kind)
+    _lib.check(_lib.load().vdqn_td_eval_bcq(C.byref(a), float(threshold), _ptr(acc), _stream()), "vdqn_td_eval_bcq")
+    return acc
+
+
 def gt_loss(q_before, act, gt, *, n_cat=5, n_act=3, inv_count=None, value_learning=False):
     lib = _lib.load()
     B, ldq = q_before.shape

@@ -617,7 +617,9 @@ def build_helpers(config, dataset, store, model, comm, rank, world_size, log):
         log(f"soft target updates: target <- target + {target_tau:g} * (online - target) inside every Adam launch, the target weights "
             "folded from the average in front of every update; TARGET_UPDATE_INTERVAL is unused")
     if stepper.algo is not None:
-        log(f"{stepper.algo.title}: {stepper.algo.log(stepper)}; validation is unchanged")
+        log(f"{stepper.algo.title}: {stepper.algo.log(stepper)}; validation adds the head's held-out metrics, one more launch per batch"
+            f"{' and a target pass over s' if stepper.algo.key == 'IQL_EXPECTILE' else ''}: "
+            + ", ".join(tag for tag, _ in algos.eval_tags(stepper.algo)))
     if cql_alpha > 0:
         log(f"conservative Q-learning: {cql_alpha:g} * (logsumexp_a Q(s, .) - Q(s, a_data)) added to the TD loss in the loss launch")
     if clip_norm > 0 or weight_decay > 0 or lr_fn is not None:

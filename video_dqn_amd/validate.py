@@ -3,7 +3,9 @@
 
 Every VAL_INTERVAL updates rank 0 walks the validation set in index order, in batches of BATCH_SIZE (the last short batch
 included), without augmentation or importance weights, through ``TDStepper.eval_begin / eval_batch / eval_result``: two forward
-passes and one metrics launch per batch, the sums kept in a small f64 table on the device and read back once per pass.  The pass
+passes and one metrics launch per batch, the sums kept in a small f64 table on the device and read back once per pass.  Under a
+head algorithm (video_dqn_amd/algos.py) a second launch per batch sums the algorithm's own metrics into a second table, read back in
+the same synchronisation and written as <slot name>/val beside the scalars below.  The pass
 indexes the dataset directly and draws nothing from torch's or numpy's global generators, so the training run's later shuffles —
 and with them its parameters — are those of the same run without validation.
 """
@@ -12,6 +14,7 @@ from __future__ import annotations
 import numpy as np
 import torch
 
+from .algos import eval_tags
 from .dataset import QLearningRealDataset, SyntheticTupleDataset
 from .shards import ShardDataset, is_shard_dir
 
@@ -104,4 +107,7 @@ class Validator:
                 writer.add_scalar(tag, result[key], sample_number)
             for c, v in enumerate(result["loss_cat"]):
                 writer.add_scalar(f"avg_q_loss_cat{c}/val", v, sample_number)
+            if "head" in result:  # the head algorithm's row: its slots' names are the tags
+                for tag, key in eval_tags(stepper.algo):
+                    writer.add_scalar(tag, result["head"][key], sample_number)
         return result
