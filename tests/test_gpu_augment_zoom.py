@@ -169,6 +169,45 @@ def test_identity_zoom_equals_the_pack_without_zoom(dtype):
         assert torch.equal(pack_input_aug(src, par, F, dtype, color=col, zoom=ident), pack_input_aug(src, par, F, dtype, color=col))
 
 
+# ---- the launcher's choice of one of the eight instances ------------------------------------------------------------------------------
+# two samples of two frames; rows under which every shared piece of the pack matters: a shift beyond the frame under a mirror, a zoom
+# row at a step of 1.0 with a fractional origin (its pairs stage all five rows), colour factors that are neither 1.0 nor clamped
+DISPATCH_PARAMS = _rows((-260, 9, 1, 0), (11, -6, 1, 0))
+DISPATCH_ZOOM = _rows((45000, ONE, 700000, 3 * ONE + 21845), (32768, 50000, FAR, 12345))
+DISPATCH_COLOR = _rows((300, 200, 128, 0), (180, 330, 400, 0))
+_dispatch_host = {}
+
+
+def _dispatch_reference(with_zoom, with_color, first_row):
+    """(the four frames, the rows from `first_row` on, the frames augmented on the host), computed once for both dtypes"""
+    key = (with_zoom, with_color, first_row)
+    if key not in _dispatch_host:
+        frames = np.random.default_rng(77).integers(0, 256, (4, 224, 224, 3), dtype=np.uint8)
+        par, zr, col = DISPATCH_PARAMS[first_row:], DISPATCH_ZOOM[first_row:], DISPATCH_COLOR[first_row:]
+        host = aug_oracle.augment_frames(frames, par, 2)
+        if with_zoom:
+            host = oracle.zoom(host, zr, 2)
+        if with_color:
+            host = aug_color_oracle.color(host, col, 2)
+        _dispatch_host[key] = (frames, par, zr, col, host)
+    return _dispatch_host[key]
+
+
+@pytest.mark.parametrize("with_color", [False, True], ids=["no_colour", "colour"])
+@pytest.mark.parametrize("with_zoom", [False, True], ids=["no_zoom", "zoom"])
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float32], ids=["bf16", "f32"])
+def test_pack_entries_launch_the_instance_for_dtype_zoom_and_colour(dtype, with_zoom, with_color):
+    from video_dqn_amd import ops
+    from video_dqn_amd.augment import pack_input_aug
+    assert any(len(oracle.source_rows(DISPATCH_ZOOM[0], DISPATCH_PARAMS[0][1], Y0)) == 5 for Y0 in range(0, 224, 4))
+    for first_row in (0, 1):  # two rows, then one: both samples take it (% n_params)
+        frames, par, zr, col, host = _dispatch_reference(with_zoom, with_color, first_row)
+        got = pack_input_aug(_dev(frames), _dev(par), 2, dtype, color=_dev(col) if with_color else None, zoom=_dev(zr) if with_zoom else None)
+        ref = ops.pack_input(_dev(host), 0, 4, dtype)
+        assert got.dtype == dtype and got.shape == ref.shape == (4, 115, 115, 16)
+        assert torch.equal(got, ref), first_row
+
+
 # ---- one update with the hooks against a plain update on host-zoomed inputs -----------------------------------------------------------
 def _step(stp, fb, fa, act, rew, term, gtb, **kw):
     gt = (rew * 0.5 + 0.25).contiguous().to(DEV) if gtb else None

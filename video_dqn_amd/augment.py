@@ -73,42 +73,41 @@ def _u64(v: int) -> int:
     return int(v) & (2**64 - 1)
 
 
-def aug_draw(seed: int, step: int, global_batch: int, first: int, n: int, pad: int, flip: bool, device="cuda",
-             out: torch.Tensor = None) -> torch.Tensor:
-    """vdqn_aug_draw on the current stream -> int32 [n][4] {sx, sy, flip, 0} of samples first .. first + n of the global batch."""
+def _draw(entry: str, seed: int, step: int, global_batch: int, first: int, n: int, scalars, device, out) -> torch.Tensor:
+    """The draw entry `entry` on the current stream of `out`'s device (a new int32 [n][4] on `device` when `out` is None)."""
     dev = torch.device(device) if out is None else out.device
     with torch.cuda.device(dev):
         if out is None:
             out = torch.empty((n, 4), dtype=torch.int32, device=dev)
-        _lib.check(_lib.load().vdqn_aug_draw(_u64(seed), _u64(step), global_batch, first, n, pad, int(bool(flip)), out.data_ptr(),
-                                             torch.cuda.current_stream().cuda_stream), "vdqn_aug_draw")
+        _lib.check(getattr(_lib.load(), entry)(_u64(seed), _u64(step), global_batch, first, n, *scalars, out.data_ptr(),
+                                               torch.cuda.current_stream().cuda_stream), entry)
     return out
+
+
+def aug_draw(seed: int, step: int, global_batch: int, first: int, n: int, pad: int, flip: bool, device="cuda",
+             out: torch.Tensor = None) -> torch.Tensor:
+    """vdqn_aug_draw on the current stream -> int32 [n][4] {sx, sy, flip, 0} of samples first .. first + n of the global batch."""
+    return _draw("vdqn_aug_draw", seed, step, global_batch, first, n, (pad, int(bool(flip))), device, out)
 
 
 def aug_draw_color(seed: int, step: int, global_batch: int, first: int, n: int, jb: int, jc: int, js: int, device="cuda",
                    out: torch.Tensor = None) -> torch.Tensor:
     """vdqn_aug_draw_color on the current stream -> int32 [n][4] {f_b, f_c, f_s, 0} (Q8, 256 = 1.0) of samples first .. first + n of
     the global batch; jb, jc, js are the Q8 half-widths (`jq`)."""
-    dev = torch.device(device) if out is None else out.device
-    with torch.cuda.device(dev):
-        if out is None:
-            out = torch.empty((n, 4), dtype=torch.int32, device=dev)
-        _lib.check(_lib.load().vdqn_aug_draw_color(_u64(seed), _u64(step), global_batch, first, n, jb, jc, js, out.data_ptr(),
-                                                   torch.cuda.current_stream().cuda_stream), "vdqn_aug_draw_color")
-    return out
+    return _draw("vdqn_aug_draw_color", seed, step, global_batch, first, n, (jb, jc, js), device, out)
 
 
 def aug_draw_zoom(seed: int, step: int, global_batch: int, first: int, n: int, jz: int, aspect: bool, device="cuda",
                   out: torch.Tensor = None) -> torch.Tensor:
     """vdqn_aug_draw_zoom on the current stream -> int32 [n][4] {ax, ay, bx, by} (Q16, 65536 = 1.0) of samples first .. first + n of
     the global batch; jz is the Q16 width (`jz`)."""
-    dev = torch.device(device) if out is None else out.device
-    with torch.cuda.device(dev):
-        if out is None:
-            out = torch.empty((n, 4), dtype=torch.int32, device=dev)
-        _lib.check(_lib.load().vdqn_aug_draw_zoom(_u64(seed), _u64(step), global_batch, first, n, jz, int(bool(aspect)), out.data_ptr(),
-                                                  torch.cuda.current_stream().cuda_stream), "vdqn_aug_draw_zoom")
-    return out
+    return _draw("vdqn_aug_draw_zoom", seed, step, global_batch, first, n, (jz, int(bool(aspect))), device, out)
+
+
+def _check_rows(name: str, rows: torch.Tensor, params: torch.Tensor) -> None:
+    if rows is not None and (rows.dtype != torch.int32 or not rows.is_contiguous() or rows.numel() != params.numel()
+                             or rows.device != params.device):
+        raise _lib.VdqnError(f"pack_input_aug: {name} must be contiguous int32 [*][4] with as many rows as params, on their device")
 
 
 def pack_input_aug(src: torch.Tensor, params: torch.Tensor, frames_per_sample: int, dtype: torch.dtype,
@@ -117,27 +116,21 @@ def pack_input_aug(src: torch.Tensor, params: torch.Tensor, frames_per_sample: i
     params) -> the augmented stem operand [n][115][115][16]."""
     if src.dtype != torch.uint8 or not src.is_contiguous() or params.dtype != torch.int32 or not params.is_contiguous():
         raise _lib.VdqnError("pack_input_aug: src must be contiguous uint8 NHWC frames and params contiguous int32 [*][4]")
-    if color is not None and (color.dtype != torch.int32 or not color.is_contiguous() or color.numel() != params.numel()
-                              or color.device != params.device):
-        raise _lib.VdqnError("pack_input_aug: color must be contiguous int32 [*][4] with as many rows as params, on their device")
-    if zoom is not None and (zoom.dtype != torch.int32 or not zoom.is_contiguous() or zoom.numel() != params.numel()
-                             or zoom.device != params.device):
-        raise _lib.VdqnError("pack_input_aug: zoom must be contiguous int32 [*][4] with as many rows as params, on their device")
+    _check_rows("color", color, params)
+    _check_rows("zoom", zoom, params)
+    # the entry that takes the arrays given, and those arrays behind params in its argument order (the zoom entry: colour may be NULL)
+    if zoom is not None:
+        entry, rows = "vdqn_pack_input_aug_zoom", (None if color is None else color.data_ptr(), zoom.data_ptr())
+    elif color is not None:
+        entry, rows = "vdqn_pack_input_aug_color", (color.data_ptr(),)
+    else:
+        entry, rows = "vdqn_pack_input_aug", ()
     n_img = src.numel() // (224 * 224 * 3)
     with torch.cuda.device(src.device):
         dst = torch.empty((n_img, 115, 115, 16), dtype=dtype, device=src.device)
         code = _lib.VDQN_BF16 if dtype == torch.bfloat16 else _lib.VDQN_F32
-        st = torch.cuda.current_stream().cuda_stream
-        if zoom is not None:
-            _lib.check(_lib.load().vdqn_pack_input_aug_zoom(src.data_ptr(), dst.data_ptr(), n_img, frames_per_sample, params.data_ptr(),
-                                                            None if color is None else color.data_ptr(), zoom.data_ptr(),
-                                                            params.numel() // 4, code, st), "vdqn_pack_input_aug_zoom")
-        elif color is not None:
-            _lib.check(_lib.load().vdqn_pack_input_aug_color(src.data_ptr(), dst.data_ptr(), n_img, frames_per_sample, params.data_ptr(),
-                                                             color.data_ptr(), params.numel() // 4, code, st), "vdqn_pack_input_aug_color")
-        else:
-            _lib.check(_lib.load().vdqn_pack_input_aug(src.data_ptr(), dst.data_ptr(), n_img, frames_per_sample, params.data_ptr(),
-                                                       params.numel() // 4, code, st), "vdqn_pack_input_aug")
+        _lib.check(getattr(_lib.load(), entry)(src.data_ptr(), dst.data_ptr(), n_img, frames_per_sample, params.data_ptr(), *rows,
+                                               params.numel() // 4, code, torch.cuda.current_stream().cuda_stream), entry)
     return dst
 
 

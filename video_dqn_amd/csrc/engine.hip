@@ -364,20 +364,16 @@ static int step_layout_samples(const vdqn_net* net, const vdqn_step_args* a) {
 static int pack_step_frames(const vdqn_net* net, const vdqn_step_args* a, unsigned char* dst, int B, hipStream_t st) {
   const int F = net->cfg.num_frames, dt = net->cfg.dtype;
   const bool gtb = a->train_on_ground_truth != 0;
-  unsigned char* dst_after = dst + (int64_t)B * F * frame_bytes(net);
-  if (a->aug_zoom) {  // the same [B][4] shift / mirror, zoom window and (NULL: none) colour factors for s and s'
-    RC(vdqn_pack_input_aug_zoom(a->before, dst, B * F, F, a->aug_params, a->aug_color, a->aug_zoom, B, dt, st));
-    if (!gtb) RC(vdqn_pack_input_aug_zoom(a->after, dst_after, B * F, F, a->aug_params, a->aug_color, a->aug_zoom, B, dt, st));
-  } else if (a->aug_color) {  // the same [B][4] shift / mirror and colour factors for s and s'
-    RC(vdqn_pack_input_aug_color(a->before, dst, B * F, F, a->aug_params, a->aug_color, B, dt, st));
-    if (!gtb) RC(vdqn_pack_input_aug_color(a->after, dst_after, B * F, F, a->aug_params, a->aug_color, B, dt, st));
-  } else if (a->aug_params) {  // the same [B][4] shift / mirror for s and s'
-    RC(vdqn_pack_input_aug(a->before, dst, B * F, F, a->aug_params, B, dt, st));
-    if (!gtb) RC(vdqn_pack_input_aug(a->after, dst_after, B * F, F, a->aug_params, B, dt, st));
-  } else if (!a->packed_frames) {
-    RC(vdqn_pack_input(a->before, a->src_kind, dst, B * F, dt, st));
-    if (!gtb) RC(vdqn_pack_input(a->after, a->src_kind, dst_after, B * F, dt, st));
-  }
+  // one pack for s and s': the same [B][4] shift / mirror, zoom window and colour factors (NULL: none) for both
+  const auto pack = [&](const void* src, void* to) {
+    if (a->aug_zoom) return vdqn_pack_input_aug_zoom(src, to, B * F, F, a->aug_params, a->aug_color, a->aug_zoom, B, dt, st);
+    if (a->aug_color) return vdqn_pack_input_aug_color(src, to, B * F, F, a->aug_params, a->aug_color, B, dt, st);
+    if (a->aug_params) return vdqn_pack_input_aug(src, to, B * F, F, a->aug_params, B, dt, st);
+    if (a->packed_frames) return (int)VDQN_OK;
+    return vdqn_pack_input(src, a->src_kind, to, B * F, dt, st);
+  };
+  RC(pack(a->before, dst));
+  if (!gtb) RC(pack(a->after, dst + (int64_t)B * F * frame_bytes(net)));
   return VDQN_OK;
 }
 

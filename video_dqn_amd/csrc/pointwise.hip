@@ -5,6 +5,7 @@
 
 #include "block_sum.h"  // wave_partials / add_partials of the loss kernels (shared with iql.hip)
 #include "common.h"
+#include "pack_common.h"  // what pack_input_rows_kernel shares with the augmented pack (augment.hip)
 
 namespace {
 
@@ -62,19 +63,15 @@ __global__ __launch_bounds__(256) void pack_input_kernel(const void* __restrict_
 // vectors into LDS and every thread builds one packed pixel from there.  The normalisation (u / 255 - mean) / std — two IEEE
 // divisions per element, 24 per packed pixel: what bounded this kernel at 2.9 TB/s — is evaluated ONCE per block for the 3 x 256
 // possible (channel, byte) pairs into an LDS table, with the same expression: same bits as the per-element arithmetic.
-constexpr int kPackPairs = 4;
+// (kPackPairs, the table entry and the store: pack_common.h, shared with the augmented pack of augment.hip.)
 template <typename T>
 __global__ __launch_bounds__(256) void pack_input_rows_kernel(const uint8_t* __restrict__ src, T* __restrict__ dst) {
   __shared__ uint4 rows[4][42];
   __shared__ T lut[3][256];
   const int n = blockIdx.y;
   const int tid = threadIdx.x;
-  {
-    const float mean[3] = {0.485f, 0.456f, 0.406f};
-    const float stdv[3] = {0.229f, 0.224f, 0.225f};
 #pragma unroll
-    for (int c = 0; c < 3; ++c) lut[c][tid] = from_f32<T>((((float)tid / 255.0f) - mean[c]) / stdv[c]);
-  }
+  for (int c = 0; c < 3; ++c) lut[c][tid] = pack_norm_entry<T>(tid, c);
   const int yy = tid / 115, x = tid - yy * 115;
   for (int pr = 0; pr < kPackPairs; ++pr) {
     const int y0 = 2 * ((int)blockIdx.x * kPackPairs + pr);  // packed rows y0, y0 + 1 -> source rows 2 (y0 - 2) .. + 3
@@ -101,10 +98,7 @@ __global__ __launch_bounds__(256) void pack_input_rows_kernel(const uint8_t* __r
         v[6 + e] = lut[e % 3][b1[e]];
       }
     }
-    T* d = dst + ((size_t)n * 115 * 115 + (size_t)y * 115 + x) * 16;
-    constexpr int V16 = (int)(16 * sizeof(T) / 16);
-#pragma unroll
-    for (int q = 0; q < V16; ++q) reinterpret_cast<uint4*>(d)[q] = reinterpret_cast<const uint4*>(v)[q];
+    pack_store16(dst + ((size_t)n * 115 * 115 + (size_t)y * 115 + x) * 16, v);
   }
 }
 
@@ -507,8 +501,8 @@ extern "C" int vdqn_pack_input(const void* src, int32_t src_kind, void* dst, int
   const int g = grid_for((long)n_img * 115 * 115);
   ProfScope ps_("pack_input", 0.0, (double)n_img * (224.0 * 224 * 3 * (src_kind == 0 ? 1 : 4) + 115.0 * 115 * 16 * (dtype == VDQN_BF16 ? 2 : 4)), (hipStream_t)stream);
   if (src_kind == 0 && n_img <= 65535 && (((uintptr_t)src) & 15) == 0) {  // frames are 150528 = 16 * 9408 bytes: every source row is 16-byte aligned
-    if (dtype == VDQN_BF16) hipLaunchKernelGGL((pack_input_rows_kernel<bf16raw>), dim3((58 + kPackPairs - 1) / kPackPairs, n_img), dim3(256), 0, (hipStream_t)stream, (const uint8_t*)src, (bf16raw*)dst);
-    else hipLaunchKernelGGL((pack_input_rows_kernel<float>), dim3((58 + kPackPairs - 1) / kPackPairs, n_img), dim3(256), 0, (hipStream_t)stream, (const uint8_t*)src, (float*)dst);
+    if (dtype == VDQN_BF16) hipLaunchKernelGGL((pack_input_rows_kernel<bf16raw>), pack_rows_grid(n_img), dim3(256), 0, (hipStream_t)stream, (const uint8_t*)src, (bf16raw*)dst);
+    else hipLaunchKernelGGL((pack_input_rows_kernel<float>), pack_rows_grid(n_img), dim3(256), 0, (hipStream_t)stream, (const uint8_t*)src, (float*)dst);
     VDQN_LAUNCH_CHECK();
     return VDQN_OK;
   }
