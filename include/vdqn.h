@@ -574,6 +574,12 @@ int64_t vdqn_net_bwd_bytes(const vdqn_net* net, int32_t n_samples);
 int64_t vdqn_net_act_offset(const vdqn_net* net, int32_t n_samples, const char* name);
 int64_t vdqn_net_bwd_offset(const vdqn_net* net, int32_t n_samples, const char* name);
 
+/* Byte offset of one layer's region inside a `packed` workspace (vdqn_net_packed_bytes), for element-by-element tests of the
+ * weight fold.  names: wf:<layer> (forward operand), wd:<layer> (data-gradient operand), bias:<layer> and scale:<layer> (f32
+ * [co_pad] each), e.g. "wf:resnet.layer1.0.conv1".  -1 if the region or the layer is unknown, -2 for the wd region of a
+ * layer that has no data-gradient operand (resnet.conv1).  Read only; added without a change of vdqn_abi_version(). */
+int64_t vdqn_net_packed_offset(const vdqn_net* net, const char* name);
+
 /* Fold eval-mode BatchNorm into the convolutions and pack the master weights (OIHW f32) into the K-contiguous
  * forward and data-gradient operands (set_train semantics: archs/HabitatDQNMultiAction.py:37-40 — in
  * extra_capacity all 20 BatchNorm layers run on running statistics). */

@@ -117,6 +117,7 @@ _SIGS = {
     "vdqn_net_bwd_bytes": (c_i64, [c_vp, c_i32]),
     "vdqn_net_act_offset": (c_i64, [c_vp, c_i32, C.c_char_p]),
     "vdqn_net_bwd_offset": (c_i64, [c_vp, c_i32, C.c_char_p]),
+    "vdqn_net_packed_offset": (c_i64, [c_vp, C.c_char_p]),
     "vdqn_net_pack_weights": (C.c_int, [c_vp, c_vp, c_vp, c_vp, c_i32, c_vp]),
     "vdqn_net_forward": (C.c_int, [c_vp, c_vp, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp]),
     "vdqn_net_trunk_forward": (C.c_int, [c_vp, c_vp, c_vp, c_i32, c_i32, c_vp, c_vp]),

@@ -597,6 +597,21 @@ extern "C" int vdqn_net_stage_range(const vdqn_net* net, int stage, int64_t* beg
   return VDQN_OK;
 }
 extern "C" int64_t vdqn_net_packed_bytes(const vdqn_net* net) { return net->packed_bytes; }
+extern "C" int64_t vdqn_net_packed_offset(const vdqn_net* net, const char* name) {
+  if (!net || !name) return -1;
+  const char* colon = strchr(name, ':');
+  if (!colon) return -1;
+  const std::string region(name, colon - name);
+  for (auto& L : net->layers) {
+    if (L.name != colon + 1) continue;
+    if (region == "wf") return L.wf_off;
+    if (region == "wd") return L.has_dgrad ? L.wd_off : -2;
+    if (region == "bias") return L.bias_off;
+    if (region == "scale") return L.scale_off;
+    return -1;
+  }
+  return -1;
+}
 extern "C" int64_t vdqn_net_acts_bytes(const vdqn_net* net, int32_t n_samples) { return act_layout(net, n_samples).total; }
 extern "C" int64_t vdqn_net_bwd_bytes(const vdqn_net* net, int32_t n_samples) { return bwd_layout(net, n_samples).total; }
 
