@@ -389,6 +389,21 @@ int vdqn_stem_wgrad_pool(const void* g_pool, const uint8_t* idx, const void* t_i
                          int64_t workspace_bytes, void* stream);
 int64_t vdqn_stem_wgrad_pool_workspace_bytes(int32_t n_img);
 
+/* The stem's DATA gradient, dL/d(frame), from the pooled gradient: autograd's max_pool2d backward followed by conv1's input
+ * gradient, `torch.autograd.grad(q, frames)` through resnet.maxpool / relu / bn1 / conv1 (torchvision resnet stem reached from
+ * archs/HabitatDQNMultiAction.py:30; the reference itself never asks for it).  g_pool [n][56][56][64] (already masked by
+ * pool > 0), idx as written by vdqn_stem_conv_pool / vdqn_maxpool_fwd, wt conv1's FORWARD operand [64][4][1][64] (BatchNorm
+ * folded), in the dtype's storage type; out f32 NCHW [n][3][224][224], every element written.  scale: HOST pointer to three f32,
+ * one per colour channel, multiplied into the result as one f32 product (NULL = 1).  dtype VDQN_BF16: one fused kernel, no
+ * workspace, no atomics (run-to-run bit-identical).  VDQN_F32 / VDQN_F32X3: vdqn_maxpool_bwd into `workspace`
+ * (vdqn_stem_input_grad_workspace_bytes) and an f32 kernel.  Refused with a message: NULL or not 16-byte aligned pointers,
+ * n_img <= 0, an n_img whose g_pool exceeds the bf16 kernel's 2 GiB buffer addressing, a workspace that is too small.
+ * Added without a change of vdqn_abi_version(). */
+int vdqn_stem_input_grad(const void* g_pool, const uint8_t* idx, const void* wt, const float* scale, float* out, int32_t n_img,
+                         int32_t dtype, void* workspace, int64_t workspace_bytes, void* stream);
+/* Bytes of that workspace: 0 for VDQN_BF16; -1 for n_img <= 0 or an unknown dtype.  Host only. */
+int64_t vdqn_stem_input_grad_workspace_bytes(int32_t n_img, int32_t dtype);
+
 /* Row-wise softmax over the first n_valid columns of x[rows][ld] (f32), written to y[rows][ld] (other columns 0):
  * `torch.softmax(x, dim=1)` of the inverse-action model's 3-way output (archs/inverse_action2.py:95). n_valid <= 64. */
 int vdqn_softmax_rows(const float* x, float* y, int32_t rows, int32_t ld, int32_t n_valid, void* stream);
@@ -755,6 +770,14 @@ int vdqn_net_backward_begin(vdqn_net* net, const vdqn_step_args* a, const float*
 /* The HIP stream (hipStream_t) on which a stage's gradients become complete; NULL when the overlap is off (then it is the
  * stream passed to vdqn_net_backward_stage). */
 void* vdqn_net_grad_stream(vdqn_net* net);
+/* dL/d(frames) of the same call: `frames.grad` after loss.backward() when the frames passed to `model(frames)` require a gradient
+ * (torch.autograd through archs/HabitatDQNMultiAction.py:44-54 down to resnet.conv1's input).  Valid after
+ * vdqn_net_backward_stage(net, a, 2, stream) of the same `a`, on the same stream: reads the pooled gradient (bf16) or conv1's
+ * output gradient (f32 / bf16x3) from a->bwd, the arg-max codes from a->acts_online and conv1's forward operand from
+ * a->packed_online.  out f32 NCHW [batch * num_frames][3][224][224].  scale_kind 0: with respect to the normalised frame;
+ * 1: with respect to the uint8 pixel value, i.e. times 1 / (255 std_c).  extra_capacity only: ARCHITECTURE='basic' is refused.
+ * Added without a change of vdqn_abi_version(). */
+int vdqn_net_input_grad(vdqn_net* net, const vdqn_step_args* a, float* out, int32_t scale_kind, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Prioritized experience replay (Schaul et al., ICLR 2016), sampled and updated on the device: no host round trip.

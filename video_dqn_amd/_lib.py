@@ -184,6 +184,9 @@ _SIGS = {
     "vdqn_net_td_eval_iql": (C.c_int, [c_vp, C.POINTER(StepArgs), c_f32, c_vp, c_vp, c_vp]),
     "vdqn_net_td_eval_dist": (C.c_int, [c_vp, C.POINTER(StepArgs), c_i32, c_f32, c_vp, c_vp, c_vp]),
     "vdqn_net_td_eval_bcq": (C.c_int, [c_vp, C.POINTER(StepArgs), c_f32, c_vp, c_vp, c_vp]),
+    "vdqn_stem_input_grad": (C.c_int, [c_vp, c_vp, c_vp, C.POINTER(c_f32), c_vp, c_i32, c_i32, c_vp, c_i64, c_vp]),
+    "vdqn_stem_input_grad_workspace_bytes": (c_i64, [c_i32, c_i32]),
+    "vdqn_net_input_grad": (C.c_int, [c_vp, C.POINTER(StepArgs), c_vp, c_i32, c_vp]),
 }
 COMM_UID_BYTES = 128
 EXPORTS = tuple(_SIGS)

@@ -945,3 +945,26 @@ extern "C" int vdqn_net_backward_stage(vdqn_net* net, const vdqn_step_args* a, i
   VDQN_LAUNCH_CHECK();
   return VDQN_OK;
 }
+
+extern "C" int vdqn_net_input_grad(vdqn_net* net, const vdqn_step_args* a, float* out, int32_t scale_kind, void* stream) {
+  VDQN_CHECK(net && a && out, "vdqn_net_input_grad: null arg");
+  VDQN_CHECK(!net->basic(), "vdqn_net_input_grad: ARCHITECTURE='basic' has no frame gradient (its backward runs through train-mode BatchNorm inside "
+                            "vdqn_net_td_forward's update only); extra_capacity only");
+  VDQN_CHECK(a->packed_online && a->acts_online && a->bwd, "vdqn_net_input_grad: null buffer");
+  VDQN_CHECK(((uintptr_t)out & 15) == 0, "vdqn_net_input_grad: out must be 16-byte aligned");
+  VDQN_CHECK(scale_kind == 0 || scale_kind == 1, "vdqn_net_input_grad: scale_kind %d (0: normalised frame, 1: uint8 pixel value)", scale_kind);
+  VDQN_CHECK(a->batch >= 1 && a->batch <= net->cfg.max_batch, "vdqn_net_input_grad: batch %d", a->batch);
+  const int n = a->batch * net->cfg.num_frames;
+  const ActLayout A = act_layout(net, step_layout_samples(net, a));
+  const BwdLayout W = bwd_layout(net, a->batch);
+  const unsigned char* pk = (const unsigned char*)a->packed_online;
+  const unsigned char* ao = (const unsigned char*)a->acts_online;
+  const unsigned char* bw = (const unsigned char*)a->bwd;
+  const Layer& L1 = net->layers[net->l_conv1];
+  float sc[3];
+  vdqn_stem_pixel_scale(sc);
+  const float* scale = scale_kind ? sc : nullptr;
+  // bf16: from the pooled gradient in one launch.  f32 / bf16x3: stage 2 has left g_c1 = vdqn_maxpool_bwd(g_pool) for conv1's weight gradient
+  if (net->cfg.dtype == VDQN_BF16) return vdqn_stem_input_grad(bw + W.g_pool, ao + A.idx, pk + L1.wf_off, scale, out, n, VDQN_BF16, nullptr, 0, stream);
+  return vdqn_stem_dgrad_from_c1(reinterpret_cast<const float*>(bw + W.g_c1), reinterpret_cast<const float*>(pk + L1.wf_off), scale, out, n, (hipStream_t)stream);
+}

@@ -146,5 +146,8 @@ bool wgrad_two_stage();
 void launch_unfold(const vdqn_net* net, const PartTable& pt, int first_layer, int n_layers, int max_co, int raw, const vdqn_step_args* a,
                    hipStream_t stream, double bytes);
 void launch_dq_pad(const vdqn_net* net, const float* dq_f32, void* dst, int rows, hipStream_t stream);
+// stem_dgrad.hip
+void vdqn_stem_pixel_scale(float* scale3);  // 1 / (255 std_c): d(normalised value) / d(uint8 pixel value)
+int vdqn_stem_dgrad_from_c1(const float* g_c1, const float* wt, const float* scale, float* out, int n_img, hipStream_t st);
 
 #pragma GCC visibility pop

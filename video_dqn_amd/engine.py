@@ -267,11 +267,16 @@ class NetEngine:
                                                  _stream()), "vdqn_net_forward")
         return q, acts
 
-    def backward_from_dq(self, acts: torch.Tensor, packed: torch.Tensor, dq: torch.Tensor, n_samples: int) -> torch.Tensor:
+    def backward_from_dq(self, acts: torch.Tensor, packed: torch.Tensor, dq: torch.Tensor, n_samples: int, want_input_grad: bool = False,
+                         pixel_units: bool = False):
         """Backward of one `forward_saved` call from dL/dQ (f32 [n_samples, num_classes*action_dim]): the flat f32 gradient
         over the trainable range, complete on the current stream (loss.backward() through `model(before)`,
-        train_q_network.py:131,226).  extra_capacity only."""
+        train_q_network.py:131,226).  extra_capacity only.  want_input_grad: -> (grads, gx) with gx f32 [n_samples * num_frames, 3,
+        224, 224] = dL/d(frames) (vdqn_net_input_grad: one more launch behind stage 2), with respect to the normalised frames or,
+        with pixel_units, to the uint8 pixel values."""
         self._need_gpu()
+        if want_input_grad and not self.extra_capacity:
+            raise _lib.VdqnError("backward_from_dq(want_input_grad=True): ARCHITECTURE='basic' has no frame gradient (extra_capacity only)")
         with torch.cuda.device(self.device):
             bwd = getattr(self, "_bwd_ws", None)
             if bwd is None or bwd[0] != n_samples:
@@ -286,8 +291,12 @@ class NetEngine:
             _lib.check(self.lib.vdqn_net_backward_begin(self.handle, C.byref(a), _ptr(dq), st), "vdqn_net_backward_begin")
             for stage in range(3):  # stage 2 joins the engine's gradient stream back into `st`
                 _lib.check(self.lib.vdqn_net_backward_stage(self.handle, C.byref(a), stage, st), "vdqn_net_backward_stage")
+            gx = None
+            if want_input_grad:
+                gx = torch.empty((n_samples * self.num_frames, 3, 224, 224), dtype=torch.float32, device=self.device)
+                _lib.check(self.lib.vdqn_net_input_grad(self.handle, C.byref(a), _ptr(gx), int(bool(pixel_units)), st), "vdqn_net_input_grad")
             dq.record_stream(torch.cuda.current_stream())
-        return grads
+        return (grads, gx) if want_input_grad else grads
 
     # ---- SyncBN (ARCHITECTURE='basic' under data parallelism) ----------------------------------------
     def set_bn_sync(self, world_size: int, allreduce=None) -> None:

@@ -22,6 +22,8 @@ differentiable for ``extra_capacity`` (the shipped configuration): with grad mod
 ``.grad``, so the reference's own loop — ``model(before)``, ``target_net(after)``, ``model(after)``,
 ``loss.backward()``, ``optim.Adam(model.parameters()).step()`` (train_q_network.py:124,131,140-142,226-227) — runs
 unmodified on the HIP kernels (three separate passes and torch's Adam: slower than ``TDStepper``, same numbers).
+For ``extra_capacity`` a float input that requires a gradient receives one too (``vdqn_net_input_grad``: one more launch behind
+the backward), and ``input_gradient`` / ``saliency`` give it without a graph.
 No arithmetic happens on the CPU.
 """
 from __future__ import annotations
@@ -48,7 +50,9 @@ def head_of(net):
 class _QFunction(torch.autograd.Function):
     """`model(x)` for autograd: forward = vdqn_net_forward into a workspace this call owns, backward = the engine's staged
     backward of that call from dL/dQ.  `params` are the module's trainable Parameters (slot order); their gradients are slices
-    of one flat buffer."""
+    of one flat buffer.
+    Frames that require a gradient (f32 [n_samples, F, 3, 224, 224]) receive dL/d(frames) from the same backward, one launch
+    behind its last stage (the weight gradients are computed on that path too, and dropped where no parameter asks for them)."""
 
     @staticmethod
     def forward(ctx, module, frames, src_kind, n_samples, *params):
@@ -56,15 +60,22 @@ class _QFunction(torch.autograd.Function):
         packed = module._packed_with_dgrad()
         q, acts = eng.forward_saved(frames, src_kind, n_samples, packed)
         ctx.module, ctx.acts, ctx.packed, ctx.n = module, acts, packed, n_samples
+        ctx.frames_shape = tuple(frames.shape)
         return q
 
     @staticmethod
     def backward(ctx, gq):
         module, eng = ctx.module, ctx.module.engine
-        flat = eng.backward_from_dq(ctx.acts, ctx.packed, gq, ctx.n)
+        want_gx = ctx.needs_input_grad[1]
+        flat = eng.backward_from_dq(ctx.acts, ctx.packed, gq, ctx.n, want_input_grad=want_gx)
+        gx = None
+        if want_gx:
+            flat, gx = flat
+            gx = gx.view(ctx.frames_shape)
         ctx.acts = ctx.packed = None
-        grads = tuple(flat[s.offset:s.offset + s.numel].view(s.shape) for s in module._trainable_slots)
-        return (None, None, None, None) + grads
+        grads = tuple(flat[s.offset:s.offset + s.numel].view(s.shape) if need else None
+                      for s, need in zip(module._trainable_slots, ctx.needs_input_grad[4:]))
+        return (None, gx, None, None) + grads
 
 
 class _Holder(nn.Module):
@@ -314,9 +325,10 @@ class HabitatDQNMultiAction(nn.Module):
                 raise Exception("bad shape")
             inp = inp.float()
             src_kind = 1
-        if inp.requires_grad:
-            raise NotImplementedError("HabitatDQNMultiAction on the HIP engine differentiates with respect to its parameters only "
-                                      "(the reference never asks for the gradient of a frame): detach the input")
+        if inp.requires_grad and not self.extra_capacity:
+            raise NotImplementedError("HabitatDQNMultiAction with ARCHITECTURE='basic' on the HIP engine has no gradient of a frame (its "
+                                      "train-mode BatchNorm backward exists inside the fused update only): detach the input, or use "
+                                      "extra_capacity")
         b = inp.shape[0]
         inp = inp.to(eng.device).contiguous()
         if b > eng.max_batch:
@@ -324,7 +336,8 @@ class HabitatDQNMultiAction(nn.Module):
             return torch.cat(outs, 0)
         if self.training and not self.extra_capacity:  # the ResNet's BatchNorm layers are in train mode (:37-40)
             q = eng.forward_train(inp, src_kind, b)  # (no autograd graph: 'basic' trains through TDStepper)
-        elif self.extra_capacity and torch.is_grad_enabled() and any(p.requires_grad for p in self._trainable_params):
+        elif self.extra_capacity and torch.is_grad_enabled() and (inp.requires_grad or any(p.requires_grad for p in self._trainable_params)):
+            # (frames that require a gradient build the graph on their own: saliency on a frozen network)
             q = _QFunction.apply(self, inp, src_kind, b, *self._trainable_params)
         else:
             q = eng.forward(inp, src_kind, b)
@@ -385,6 +398,49 @@ class HabitatDQNMultiAction(nn.Module):
     def behaviour(self, frames):
         """f32 [B, action_dim]: the behaviour head's probabilities pi_b(a | s), from one forward pass (no gradient)."""
         return self._bcq_readout(frames, 0.0)[1]
+
+    def input_gradient(self, frames, dq, pixel_units=False):
+        """f32 [B, F, 3, 224, 224]: the gradient of sum(Q * dq) with respect to the frames, for `dq` [B, num_classes, action_dim].
+        `frames` as `forward` takes them: uint8 [B,(F,)224,224,3] or normalised float [B,(F,)3,224,224]; the gradient is with
+        respect to the normalised values, or with pixel_units to the uint8 pixel values (times 1 / (255 std_c)).  One forward and
+        one backward on the engine in eval mode (the module's flag is left as it was); no autograd graph, no parameter gradient is
+        kept.  extra_capacity only."""
+        if not self.extra_capacity:
+            raise NotImplementedError("input_gradient: ARCHITECTURE='basic' has no gradient of a frame on the HIP engine (extra_capacity only)")
+        eng = self.engine
+        src_kind = 0 if frames.dtype == torch.uint8 else 1
+        if self.num_frames == 1 and frames.dim() == 4:
+            frames = frames.unsqueeze(1)
+        if frames.shape[1] != self.num_frames:
+            raise Exception("bad shape")
+        frames = (frames if src_kind == 0 else frames.detach().float()).to(eng.device).contiguous()
+        b = frames.shape[0]
+        dq = dq.reshape(b, self.num_classes * self.action_dim)
+        if b > eng.max_batch:
+            return torch.cat([self.input_gradient(frames[i:i + eng.max_batch], dq[i:i + eng.max_batch], pixel_units)
+                              for i in range(0, b, eng.max_batch)], 0)
+        was_training = self.training
+        self.training = False  # (this module's flag alone, as in state_values)
+        try:
+            with torch.no_grad():
+                packed = self._packed_with_dgrad()
+                _, acts = eng.forward_saved(frames, src_kind, b, packed)
+                _, gx = eng.backward_from_dq(acts, packed, dq, b, want_input_grad=True, pixel_units=pixel_units)
+        finally:
+            self.training = was_training
+        return gx.view(b, self.num_frames, 3, 224, 224)
+
+    def saliency(self, frames, category, action=None):
+        """f32 [B, F, 224, 224]: the maximum over colour of |dQ[category, action] / d pixel|; action=None: the greedy action of
+        every sample.  uint8 frames: per unit of the pixel value; float frames: per unit of the normalised value."""
+        if not self.extra_capacity:
+            raise NotImplementedError("saliency: ARCHITECTURE='basic' has no gradient of a frame on the HIP engine (extra_capacity only)")
+        with torch.no_grad():
+            q = self.forward(frames.detach())
+        act = q[:, category].argmax(-1) if action is None else torch.full((q.shape[0],), int(action), device=q.device)
+        dq = torch.zeros_like(q)
+        dq[torch.arange(q.shape[0], device=q.device), category, act] = 1.0
+        return self.input_gradient(frames, dq, pixel_units=(frames.dtype == torch.uint8)).abs().amax(2)
 
 
 def build_model(config, max_batch=None):

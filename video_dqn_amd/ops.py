@@ -165,6 +165,32 @@ def stem_wgrad_pool(g_pool: torch.Tensor, idx: torch.Tensor, t_in: torch.Tensor,
     return dw
 
 
+def stem_pixel_scale():
+    """f32 [3] numpy: d(normalised value) / d(uint8 pixel value) = 1 / (255 std_c), in f32 as the library computes it."""
+    import numpy as np
+    return np.float32(1.0) / (np.float32(255.0) * np.array([0.229, 0.224, 0.225], dtype=np.float32))
+
+
+def stem_input_grad(g_pool: torch.Tensor, idx: torch.Tensor, wt: torch.Tensor, pixel_units: bool = False,
+                    precision: Optional[str] = None) -> torch.Tensor:
+    """The stem's data gradient: g_pool [n,56,56,64] (bf16 or f32), idx uint8 (stem_conv_pool / maxpool_fwd), wt conv1's forward
+    operand [64,4,1,64] in g_pool's dtype -> f32 [n,3,224,224] == the input gradient of conv1 applied to maxpool_bwd(g_pool, idx).
+    bf16: one fused kernel; f32 (precision None or "bf16x3"): maxpool_bwd into a workspace + an f32 kernel.  pixel_units: times
+    stem_pixel_scale() per colour channel (the gradient with respect to the uint8 pixel value)."""
+    lib = _lib.load()
+    n = g_pool.shape[0]
+    code = gemm_dtype_code(g_pool, precision)
+    if wt.dtype != g_pool.dtype:
+        raise TypeError(f"stem_input_grad: wt is {wt.dtype}, g_pool {g_pool.dtype}")
+    out = torch.empty((n, 3, 224, 224), dtype=torch.float32, device=g_pool.device)
+    nbytes = lib.vdqn_stem_input_grad_workspace_bytes(n, code)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=g_pool.device) if nbytes > 0 else None
+    scale = (C.c_float * 3)(*[float(v) for v in stem_pixel_scale()]) if pixel_units else None
+    _lib.check(lib.vdqn_stem_input_grad(_ptr(g_pool), _ptr(idx), _ptr(wt), scale, _ptr(out), n, code, _ptr(ws), max(nbytes, 0), _stream()),
+               "vdqn_stem_input_grad")
+    return out
+
+
 LOSS_KINDS = {"l2": 0, "huber": 1}  # vdqn_td_args.loss_kind
 
 
