@@ -778,6 +778,65 @@ void* vdqn_net_grad_stream(vdqn_net* net);
  * 1: with respect to the uint8 pixel value, i.e. times 1 / (255 std_c).  extra_capacity only: ARCHITECTURE='basic' is refused.
  * Added without a change of vdqn_abi_version(). */
 int vdqn_net_input_grad(vdqn_net* net, const vdqn_step_args* a, float* out, int32_t scale_kind, void* stream);
+/* The same dL/d(frames), from a backward that computes nothing else: vdqn_net_backward_begin + vdqn_net_backward_stage(0..2) +
+ * vdqn_net_input_grad of ONE earlier vdqn_net_forward (or vdqn_net_forward_attrib) call, without the weight gradients.  It launches
+ * the dL/dQ conversion and the data-gradient chain (the head's four links, features.8, the eight BasicBlocks' data gradients, then
+ * the stem's: vdqn_stem_input_grad for bf16, vdqn_maxpool_bwd + an f32 kernel for f32 / bf16x3), every launch with the arguments the
+ * training walk gives it, the column-sum partial buffers included (the choice of kernel depends on them), so `out` holds the bits
+ * the three-call sequence writes.  No weight gradient, no unfold, no clear of the accumulators, no side stream: everything is
+ * queued on `stream`.  `a` carries packed_online (packed with the data-gradient operands), acts_online, batch = acts_samples, bwd;
+ * grads may be NULL, params and bnstats are not read.  extra_capacity only: ARCHITECTURE='basic' is refused.
+ * Added without a change of vdqn_abi_version(). */
+int vdqn_net_backward_data(vdqn_net* net, const vdqn_step_args* a, const float* dq_f32, float* out, int32_t scale_kind, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Attribution: perturbed copies of frames packed straight into the stem operand, and the sums over them (csrc/attrib.hip).
+ * Integrated gradients (Sundararajan et al., ICML 2017) walks a straight path from a baseline to the frame; SmoothGrad (Smilkov
+ * et al., 2017) averages the gradient over noisy copies.  Neither is in the reference.  In all three kernels every product and
+ * every sum rounds on its own (no contraction into a fused multiply-add): tests/attrib_oracle.py restates them in numpy float32.
+ *
+ * x is the normalised f32 value of a pixel: the float source's value, or ((float)u / 255 - mean_c) / std_c of a uint8 source
+ * (vdqn_pack_input's expression).  b is the baseline: base_const[c] (normalised units), or, with `baseline` given, the value of a
+ * second image tensor of the source's kind and shape.  Copy s of image i is image s * n_base + i of the output.
+ *   mode 0 (path):   x_s = b + coef[s] * (x - b)                           coef: DEVICE f32 [n_copies]
+ *   mode 1 (noise):  x_s = x + sigma[c] * z                                sigma: normalised units
+ *     h = splitmix64(splitmix64(splitmix64(seed ^ 0x4154545249423031) ^ ((uint64)(s0 + s) << 32 | (uint32)(i0 + i))) ^ e)
+ *     z = (float)(h0 + h1 + h2 + h3 - 131070) * kZ,  h_k = (h >> 16 k) & 0xFFFF,  kZ = (float)(1 / sqrt((2^32 - 1) / 3))
+ *   with e = (c * 224 + Y) * 224 + X the element's NCHW index inside its image ("ATTRIB01": a stream of its own).  z is
+ *   Irwin-Hall of order 4 on integers: mean 0, variance 1, |z| <= 3.4641; s0 and i0 make a run's noise independent of how it
+ *   is cut into calls.  x_s is rounded to the storage type once. */
+/* The arguments the attribution entries share, in this order wherever they appear:
+ *   src, src_kind   n_base images: uint8 NHWC [n_base][224][224][3] (src_kind 0) or f32 NCHW [n_base][3][224][224] (1)
+ *   baseline        optional: the baseline images, same kind and shape as src; NULL: base_const
+ *   base_const      HOST f32 [3], normalised units (NULL: zeros); not read when baseline is given
+ *   n_base
+ * and for the pack: n_copies, mode, coef (mode 0: DEVICE f32 [n_copies]), sigma (mode 1: HOST f32 [3], normalised units), seed,
+ * s0, i0 (mode 1: global index of copy 0 and of image 0).
+ * dst: [n_copies * n_base][115][115][16] in the dtype's storage type (VDQN_BF16 / VDQN_F32), borders and pad channels zero as
+ * vdqn_pack_input writes them.  Refused with a message: null or misaligned (16 bytes; coef 4) pointers, src_kind or mode out of
+ * range, n_base < 1, n_copies outside [1, 65535], 2^31 packed pixels or more, negative s0 / i0, a sigma that is negative or not
+ * finite, a base_const that is not finite. */
+int vdqn_attrib_pack(const void* src, int32_t src_kind, const void* baseline, const float* base_const, int32_t n_base, int32_t n_copies,
+                     int32_t mode, const float* coef, const float* sigma, uint64_t seed, int32_t s0, int32_t i0, void* dst, int32_t dtype,
+                     void* stream);
+/* acc[i][e] = (accumulate ? acc[i][e] : 0) + w[0] * g[i][e] + w[1] * g[n_base + i][e] + ... in ascending s, one rounding per
+ * product and per sum; squared: (w[s] * g) * g.  g f32 [n_copies * n_base][3][224][224], acc f32 [n_base][3][224][224], w DEVICE
+ * f32 [n_copies].  No atomics: run-to-run bit-identical, and chunks of copies continued with `accumulate` give the bits of one call. */
+int vdqn_attrib_reduce(const float* g, const float* w, float* acc, int32_t n_base, int32_t n_copies, int32_t squared,
+                       int32_t accumulate, void* stream);
+/* mode 0: out[i][c][y][x] = acc * (x - b) (then times 1 / (255 std_c) with scale_kind 1), x and b as vdqn_attrib_pack takes them;
+ * out f32 [n_base][3][224][224].
+ * mode 1: out[i][y][x] = max over c of |acc[i][c][y][x]| (a NaN stays one); the source arguments are not read and may be NULL;
+ * out f32 [n_base][224][224]. */
+int vdqn_attrib_finish(const float* acc, const void* src, int32_t src_kind, const void* baseline, const float* base_const, int32_t n_base,
+                       int32_t mode, int32_t scale_kind, float* out, void* stream);
+/* vdqn_net_forward over perturbed copies: vdqn_attrib_pack straight into the workspace's packed-input region, then the forward
+ * pass; no float copy of the perturbed frames exists.  n_copies * n_base must equal n_samples * num_frames and n_base be a whole
+ * number of samples (a sample's frames are consecutive base images); `acts` then feeds vdqn_net_backward_data like a
+ * vdqn_net_forward workspace.  extra_capacity only. */
+int vdqn_net_forward_attrib(vdqn_net* net, const void* packed, const void* src, int32_t src_kind, const void* baseline, const float* base_const,
+                            int32_t n_base, int32_t n_copies, int32_t mode, const float* coef, const float* sigma, uint64_t seed, int32_t s0,
+                            int32_t i0, int32_t n_samples, void* acts, float* q_out, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Prioritized experience replay (Schaul et al., ICLR 2016), sampled and updated on the device: no host round trip.

@@ -187,6 +187,14 @@ _SIGS = {
     "vdqn_stem_input_grad": (C.c_int, [c_vp, c_vp, c_vp, C.POINTER(c_f32), c_vp, c_i32, c_i32, c_vp, c_i64, c_vp]),
     "vdqn_stem_input_grad_workspace_bytes": (c_i64, [c_i32, c_i32]),
     "vdqn_net_input_grad": (C.c_int, [c_vp, C.POINTER(StepArgs), c_vp, c_i32, c_vp]),
+    "vdqn_net_backward_data": (C.c_int, [c_vp, C.POINTER(StepArgs), c_vp, c_vp, c_i32, c_vp]),
+    # (src, src_kind, baseline, base_const, n_base | n_copies, mode, coef, sigma, seed, s0, i0): the attribution entries' shared arguments
+    "vdqn_attrib_pack": (C.c_int, [c_vp, c_i32, c_vp, C.POINTER(c_f32), c_i32, c_i32, c_i32, c_vp, C.POINTER(c_f32), C.c_uint64, c_i32, c_i32,
+                                   c_vp, c_i32, c_vp]),
+    "vdqn_attrib_reduce": (C.c_int, [c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp]),
+    "vdqn_attrib_finish": (C.c_int, [c_vp, c_vp, c_i32, c_vp, C.POINTER(c_f32), c_i32, c_i32, c_i32, c_vp, c_vp]),
+    "vdqn_net_forward_attrib": (C.c_int, [c_vp, c_vp, c_vp, c_i32, c_vp, C.POINTER(c_f32), c_i32, c_i32, c_i32, c_vp, C.POINTER(c_f32),
+                                          C.c_uint64, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),
 }
 COMM_UID_BYTES = 128
 EXPORTS = tuple(_SIGS)

@@ -75,13 +75,6 @@ constexpr int kMaxJz = 32768;              // Q16 width of the zoom's side range
 constexpr int kZoomOne = 65536;            // Q16 1.0: the largest source step (no zoom-out)
 constexpr int kZoomMaxOrigin = 224 << 16;  // |bx|, |by| beyond it already select an edge pixel everywhere
 
-__host__ __device__ inline uint64_t splitmix64(uint64_t x) {
-  uint64_t z = x + 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-
 // ---- the draws: one thread per sample --------------------------------------------------------------------------------------------
 // the hash of sample j of the global batch G at update `step`, in the stream `stream` of the run's seed
 __device__ __forceinline__ uint64_t sample_hash(uint64_t stream, uint64_t seed, uint64_t step, int G, int j) {

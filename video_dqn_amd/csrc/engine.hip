@@ -728,8 +728,10 @@ extern "C" int vdqn_net_td_eval_bcq(vdqn_net* net, const vdqn_step_args* a, floa
 
 namespace {
 
-// backward of BasicBlock b (gradient of its output, already ReLU-masked, is in g_o[b])
-int block_backward(vdqn_net* net, const vdqn_step_args* a, int b, const ActLayout& A, const BwdLayout& W, int n, hipStream_t st) {
+// backward of BasicBlock b (gradient of its output, already ReLU-masked, is in g_o[b]).  want_wgrad false (vdqn_net_backward_data):
+// the data gradients alone, each launch with the arguments the training walk gives it, all on `st`.
+int block_backward(vdqn_net* net, const vdqn_step_args* a, int b, const ActLayout& A, const BwdLayout& W, int n, hipStream_t st,
+                   bool want_wgrad = true) {
   const unsigned char* pk = (const unsigned char*)a->packed_online;
   unsigned char* ao = (unsigned char*)a->acts_online;
   unsigned char* bw = (unsigned char*)a->bwd;
@@ -739,12 +741,13 @@ int block_backward(vdqn_net* net, const vdqn_step_args* a, int b, const ActLayou
   unsigned char* gx = b == 0 ? bw + W.g_pool : bw + W.g_o[b - 1];
   const void* g_out = bw + W.g_o[b];
   // conv2: weight gradient, then data gradient into g_h masked by relu(h)
-  hipStream_t ws = wgrad_stream(net, st);  // g_out is complete on `st`
-  RC(run_wgrad(net, c2, bw, W, g_out, ao + A.h[b], n, ws));
-  if (net->l_b_ds[b] >= 0) RC(run_wgrad(net, net->layers[net->l_b_ds[b]], bw, W, g_out, x, n, ws));
+  if (want_wgrad) {
+    hipStream_t ws = wgrad_stream(net, st);  // g_out is complete on `st`
+    RC(run_wgrad(net, c2, bw, W, g_out, ao + A.h[b], n, ws));
+    if (net->l_b_ds[b] >= 0) RC(run_wgrad(net, net->layers[net->l_b_ds[b]], bw, W, g_out, x, n, ws));
+  }
   RC(run_dgrad(net, c2, pk, g_out, bw + W.g_h[b], n, nullptr, ao + A.h[b], st, bw + W.part[part_h(b)]));
-  ws = wgrad_stream(net, st);  // g_h is complete
-  RC(run_wgrad(net, c1, bw, W, bw + W.g_h[b], x, n, ws));
+  if (want_wgrad) RC(run_wgrad(net, c1, bw, W, bw + W.g_h[b], x, n, wgrad_stream(net, st)));  // g_h is complete
   const void* resid = g_out;  // identity shortcut
   if (net->l_b_ds[b] >= 0) {
     const Layer& ds = net->layers[net->l_b_ds[b]];
@@ -756,6 +759,28 @@ int block_backward(vdqn_net* net, const vdqn_step_args* a, int b, const ActLayou
     resid = bw + W.dsg[b];
   }
   RC(run_dgrad(net, c1, pk, bw + W.g_h[b], gx, n, resid, x, st, bw + W.part[b > 0 ? part_o(b - 1) : kPartPool]));
+  return VDQN_OK;
+}
+
+// extra_capacity, the head's four links and features.8: from dq down to g_o[7].  part_rows[i]: rows per entry of the column-sum
+// partials that are layer i's bias gradient, as their producer reports them.
+int head_backward(vdqn_net* net, const vdqn_step_args* a, const ActLayout& A, const BwdLayout& W, int B, int n, hipStream_t st, int* part_rows,
+                  bool want_wgrad = true) {
+  const unsigned char* pk = (const unsigned char*)a->packed_online;
+  unsigned char* ao = (unsigned char*)a->acts_online;
+  unsigned char* bw = (unsigned char*)a->bwd;
+  const Layer& t4 = net->layers[net->l_top4];
+  const Layer& t2 = net->layers[net->l_top2];
+  const Layer& t0 = net->layers[net->l_top0];
+  const Layer& f8 = net->layers[net->l_f8];
+  if (want_wgrad) RC(run_wgrad(net, t4, bw, W, bw + W.dq, ao + A.l1, B, wgrad_stream(net, st), true));
+  RC(run_dgrad(net, t4, pk, bw + W.dq, bw + W.g_l1, B, nullptr, ao + A.l1, st, bw + W.part[kPartL1], nullptr, nullptr, &part_rows[net->l_top2]));
+  if (want_wgrad) RC(run_wgrad(net, t2, bw, W, bw + W.g_l1, ao + A.l0, B, wgrad_stream(net, st)));
+  RC(run_dgrad(net, t2, pk, bw + W.g_l1, bw + W.g_l0, B, nullptr, ao + A.l0, st, bw + W.part[kPartL0], nullptr, nullptr, &part_rows[net->l_top0]));
+  if (want_wgrad) RC(run_wgrad(net, t0, bw, W, bw + W.g_l0, ao + A.f8, B, wgrad_stream(net, st)));
+  RC(run_dgrad(net, t0, pk, bw + W.g_l0, bw + W.g_f8, B, nullptr, ao + A.f8, st, bw + W.part[kPartF8], nullptr, nullptr, &part_rows[net->l_f8]));
+  if (want_wgrad) RC(run_wgrad(net, f8, bw, W, bw + W.g_f8, ao + A.o[7], n, wgrad_stream(net, st)));
+  RC(run_dgrad(net, f8, pk, bw + W.g_f8, bw + W.g_o[7], n, nullptr, ao + A.o[7], st, bw + W.part[part_o(7)]));
   return VDQN_OK;
 }
 
@@ -862,18 +887,7 @@ extern "C" int vdqn_net_backward_stage(vdqn_net* net, const vdqn_step_args* a, i
       RC(run_wgrad(net, net->layers[net->l_conv1], bw, W, bw + W.g_c1, a->packed_frames ? a->packed_frames : ao + A.t_in, n, wgrad_stream(net, st)));
     }
   } else if (stage == 0) {
-    const Layer& t4 = net->layers[net->l_top4];
-    const Layer& t2 = net->layers[net->l_top2];
-    const Layer& t0 = net->layers[net->l_top0];
-    const Layer& f8 = net->layers[net->l_f8];
-    RC(run_wgrad(net, t4, bw, W, bw + W.dq, ao + A.l1, B, wgrad_stream(net, st), true));
-    RC(run_dgrad(net, t4, pk, bw + W.dq, bw + W.g_l1, B, nullptr, ao + A.l1, st, bw + W.part[kPartL1], nullptr, nullptr, &part_rows[net->l_top2]));
-    RC(run_wgrad(net, t2, bw, W, bw + W.g_l1, ao + A.l0, B, wgrad_stream(net, st)));
-    RC(run_dgrad(net, t2, pk, bw + W.g_l1, bw + W.g_l0, B, nullptr, ao + A.l0, st, bw + W.part[kPartL0], nullptr, nullptr, &part_rows[net->l_top0]));
-    RC(run_wgrad(net, t0, bw, W, bw + W.g_l0, ao + A.f8, B, wgrad_stream(net, st)));
-    RC(run_dgrad(net, t0, pk, bw + W.g_l0, bw + W.g_f8, B, nullptr, ao + A.f8, st, bw + W.part[kPartF8], nullptr, nullptr, &part_rows[net->l_f8]));
-    RC(run_wgrad(net, f8, bw, W, bw + W.g_f8, ao + A.o[7], n, wgrad_stream(net, st)));
-    RC(run_dgrad(net, f8, pk, bw + W.g_f8, bw + W.g_o[7], n, nullptr, ao + A.o[7], st, bw + W.part[part_o(7)]));
+    RC(head_backward(net, a, A, W, B, n, st, part_rows));
     RC(block_backward(net, a, 7, A, W, n, st));
     RC(block_backward(net, a, 6, A, W, n, st));
   } else if (stage == 1) {
@@ -946,6 +960,24 @@ extern "C" int vdqn_net_backward_stage(vdqn_net* net, const vdqn_step_args* a, i
   return VDQN_OK;
 }
 
+// The stem's link of the data-gradient chain: g_pool -> dL/d(frames).  bf16: from the pooled gradient in one launch.  f32 / bf16x3:
+// the plain f32 kernel on g_c1 = vdqn_maxpool_bwd(g_pool), which `pool_bwd` launches first (the training walk's stage 2 already has).
+static int stem_data_grad(vdqn_net* net, const vdqn_step_args* a, float* out, int scale_kind, bool pool_bwd, hipStream_t st) {
+  const int n = a->batch * net->cfg.num_frames;
+  const ActLayout A = act_layout(net, step_layout_samples(net, a));
+  const BwdLayout W = bwd_layout(net, a->batch);
+  const unsigned char* pk = (const unsigned char*)a->packed_online;
+  const unsigned char* ao = (const unsigned char*)a->acts_online;
+  unsigned char* bw = (unsigned char*)a->bwd;
+  const Layer& L1 = net->layers[net->l_conv1];
+  float sc[3];
+  vdqn_stem_pixel_scale(sc);
+  const float* scale = scale_kind ? sc : nullptr;
+  if (net->cfg.dtype == VDQN_BF16) return vdqn_stem_input_grad(bw + W.g_pool, ao + A.idx, pk + L1.wf_off, scale, out, n, VDQN_BF16, nullptr, 0, st);
+  if (pool_bwd) RC(vdqn_maxpool_bwd(bw + W.g_pool, ao + A.idx, nullptr, bw + W.g_c1, n, 112, 112, 64, net->cfg.dtype, st));
+  return vdqn_stem_dgrad_from_c1(reinterpret_cast<const float*>(bw + W.g_c1), reinterpret_cast<const float*>(pk + L1.wf_off), scale, out, n, st);
+}
+
 extern "C" int vdqn_net_input_grad(vdqn_net* net, const vdqn_step_args* a, float* out, int32_t scale_kind, void* stream) {
   VDQN_CHECK(net && a && out, "vdqn_net_input_grad: null arg");
   VDQN_CHECK(!net->basic(), "vdqn_net_input_grad: ARCHITECTURE='basic' has no frame gradient (its backward runs through train-mode BatchNorm inside "
@@ -954,17 +986,51 @@ extern "C" int vdqn_net_input_grad(vdqn_net* net, const vdqn_step_args* a, float
   VDQN_CHECK(((uintptr_t)out & 15) == 0, "vdqn_net_input_grad: out must be 16-byte aligned");
   VDQN_CHECK(scale_kind == 0 || scale_kind == 1, "vdqn_net_input_grad: scale_kind %d (0: normalised frame, 1: uint8 pixel value)", scale_kind);
   VDQN_CHECK(a->batch >= 1 && a->batch <= net->cfg.max_batch, "vdqn_net_input_grad: batch %d", a->batch);
-  const int n = a->batch * net->cfg.num_frames;
-  const ActLayout A = act_layout(net, step_layout_samples(net, a));
-  const BwdLayout W = bwd_layout(net, a->batch);
-  const unsigned char* pk = (const unsigned char*)a->packed_online;
-  const unsigned char* ao = (const unsigned char*)a->acts_online;
-  const unsigned char* bw = (const unsigned char*)a->bwd;
-  const Layer& L1 = net->layers[net->l_conv1];
-  float sc[3];
-  vdqn_stem_pixel_scale(sc);
-  const float* scale = scale_kind ? sc : nullptr;
-  // bf16: from the pooled gradient in one launch.  f32 / bf16x3: stage 2 has left g_c1 = vdqn_maxpool_bwd(g_pool) for conv1's weight gradient
-  if (net->cfg.dtype == VDQN_BF16) return vdqn_stem_input_grad(bw + W.g_pool, ao + A.idx, pk + L1.wf_off, scale, out, n, VDQN_BF16, nullptr, 0, stream);
-  return vdqn_stem_dgrad_from_c1(reinterpret_cast<const float*>(bw + W.g_c1), reinterpret_cast<const float*>(pk + L1.wf_off), scale, out, n, (hipStream_t)stream);
+  // f32 / bf16x3: stage 2 has left g_c1 = vdqn_maxpool_bwd(g_pool) for conv1's weight gradient
+  return stem_data_grad(net, a, out, scale_kind, false, (hipStream_t)stream);
+}
+
+// The data gradients of one forward call and nothing else: the walk of vdqn_net_backward_stage(0..2) with want_wgrad false, every
+// data gradient with the partial buffer the training walk hands it (vdqn_conv2d's choice of kernel and epilogue depends on it), then
+// the stem's link.  One stream, no fork, no join, no clear: nothing here accumulates.
+extern "C" int vdqn_net_backward_data(vdqn_net* net, const vdqn_step_args* a, const float* dq_f32, float* out, int32_t scale_kind, void* stream) {
+  VDQN_CHECK(net && a && dq_f32 && out, "vdqn_net_backward_data: null arg");
+  VDQN_CHECK(!net->basic(), "vdqn_net_backward_data: ARCHITECTURE='basic' has no frame gradient (its backward runs through train-mode BatchNorm inside "
+                            "vdqn_net_td_forward's update only); extra_capacity only");
+  VDQN_CHECK(a->packed_online && a->acts_online && a->bwd, "vdqn_net_backward_data: null buffer");
+  VDQN_CHECK(a->batch >= 1 && a->batch <= net->cfg.max_batch && a->acts_samples == a->batch,
+             "vdqn_net_backward_data: acts_samples (%d) must equal batch (%d) <= max_batch", a->acts_samples, a->batch);
+  VDQN_CHECK(((uintptr_t)out & 15) == 0, "vdqn_net_backward_data: out must be 16-byte aligned");
+  VDQN_CHECK(scale_kind == 0 || scale_kind == 1, "vdqn_net_backward_data: scale_kind %d (0: normalised frame, 1: uint8 pixel value)", scale_kind);
+  hipStream_t st = (hipStream_t)stream;
+  const int B = a->batch, n = B * net->cfg.num_frames;
+  const ActLayout A = act_layout(net, B);
+  const BwdLayout W = bwd_layout(net, B);
+  int part_rows[kMaxLayers];  // (what the unfold would read: nobody does here)
+  launch_dq_pad(net, dq_f32, (unsigned char*)a->bwd + W.dq, B, st);
+  VDQN_LAUNCH_CHECK();
+  RC(head_backward(net, a, A, W, B, n, st, part_rows, false));
+  for (int b = 7; b >= 0; --b) RC(block_backward(net, a, b, A, W, n, st, false));
+  return stem_data_grad(net, a, out, scale_kind, true, st);
+}
+
+extern "C" int vdqn_net_forward_attrib(vdqn_net* net, const void* packed, const void* src, int32_t src_kind, const void* baseline, const float* base_const,
+                                       int32_t n_base, int32_t n_copies, int32_t mode, const float* coef, const float* sigma, uint64_t seed, int32_t s0,
+                                       int32_t i0, int32_t n_samples, void* acts, float* q_out, void* stream) {
+  VDQN_CHECK(net && packed && acts && q_out, "vdqn_net_forward_attrib: null arg");
+  VDQN_CHECK(!net->basic(), "vdqn_net_forward_attrib: ARCHITECTURE='basic' has no frame gradient to attribute with; extra_capacity only");
+  VDQN_CHECK(n_samples >= 1 && n_samples <= net->cfg.max_batch, "vdqn_net_forward_attrib: n_samples %d exceeds max_batch %d", n_samples, net->cfg.max_batch);
+  const int F = net->cfg.num_frames;
+  VDQN_CHECK(n_base >= 1 && n_copies >= 1 && (int64_t)n_copies * n_base == (int64_t)n_samples * F,
+             "vdqn_net_forward_attrib: %d copies of %d images are not %d samples of %d frames", n_copies, n_base, n_samples, F);
+  VDQN_CHECK(n_base % F == 0, "vdqn_net_forward_attrib: n_base %d is not a whole number of %d-frame samples", n_base, F);
+  hipStream_t st = (hipStream_t)stream;
+  const ActLayout A = act_layout(net, n_samples);
+  unsigned char* ab = (unsigned char*)acts;
+  RC(vdqn_attrib_pack(src, src_kind, baseline, base_const, n_base, n_copies, mode, coef, sigma, seed, s0, i0, ab + A.t_in, net->cfg.dtype, st));
+  RC(forward_impl(net, (const unsigned char*)packed, ab + A.t_in, n_samples, ab, A, st));
+  const int nq = net->cfg.action_dim * net->cfg.num_classes;
+  hipError_t e = hipMemcpy2DAsync(q_out, (size_t)nq * 4, ab + A.qf, 64 * 4, (size_t)nq * 4, (size_t)n_samples, hipMemcpyDeviceToDevice, st);
+  VDQN_CHECK(e == hipSuccess, "vdqn_net_forward_attrib: q copy failed: %s", hipGetErrorString(e));
+  return VDQN_OK;
 }

@@ -16,6 +16,14 @@ __device__ __forceinline__ T pack_norm_entry(int t, int c) {
   return from_f32<T>((((float)t / 255.0f) - mean[c]) / stdv[c]);
 }
 
+// the counter hash of every draw a pack makes (augment.hip's per-sample draws, attrib.hip's per-element noise)
+__host__ __device__ inline uint64_t splitmix64(uint64_t x) {
+  uint64_t z = x + 0x9E3779B97F4A7C15ull;
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  return z ^ (z >> 31);
+}
+
 // the 16 elements of one packed pixel (12 values + 4 zero padding channels), as 16-byte vectors; v and d are 16-byte aligned
 template <typename T>
 __device__ __forceinline__ void pack_store16(T* d, const T* v) {

@@ -69,6 +69,36 @@ def require_gpu(device=None) -> torch.device:
     return torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
 
 
+def norm_pixel(values):
+    """f32 [3] numpy: pixel values (0 .. 255, one per colour channel) in normalised units, (v / 255 - mean_c) / std_c in float32 with
+    every operation rounded on its own: the bits vdqn_pack_input gives a uint8 pixel of that value."""
+    import numpy as np
+    v = np.asarray(values, dtype=np.float32).reshape(3)
+    return (v / np.float32(255.0) - np.array([0.485, 0.456, 0.406], dtype=np.float32)) / np.array([0.229, 0.224, 0.225], dtype=np.float32)
+
+
+def attrib_source_args(src: torch.Tensor, baseline=None):
+    """The (src, src_kind, baseline, base_const, n_base) arguments the attribution entries share, plus what must stay alive.  src: uint8
+    [n,224,224,3] or f32 [n,3,224,224], contiguous; baseline: None (zeros in normalised units), three floats in NORMALISED units, or
+    a tensor of src's dtype and shape."""
+    kind = 0 if src.dtype == torch.uint8 else 1
+    shape = (224, 224, 3) if kind == 0 else (3, 224, 224)
+    if src.dim() != 4 or tuple(src.shape[1:]) != shape or (kind == 1 and src.dtype != torch.float32) or not src.is_contiguous():
+        raise ValueError(f"attribution source must be contiguous uint8 [n,224,224,3] or float32 [n,3,224,224], not {src.dtype} {tuple(src.shape)}")
+    base_t, const = None, None
+    if isinstance(baseline, torch.Tensor):
+        if baseline.dtype != src.dtype or baseline.shape != src.shape or baseline.device != src.device:
+            raise ValueError(f"baseline tensor must have the source's kind and shape ({src.dtype} {tuple(src.shape)}), not {baseline.dtype} "
+                             f"{tuple(baseline.shape)}")
+        base_t = baseline.contiguous()
+    elif baseline is not None:
+        vals = [float(v) for v in baseline]
+        if len(vals) != 3:
+            raise ValueError(f"baseline must be three per-channel values or a tensor shaped like the source, not {len(vals)} values")
+        const = (C.c_float * 3)(*vals)
+    return (_ptr(src), kind, _ptr(base_t), const, src.shape[0]), (src, base_t, const)
+
+
 @dataclass
 class ParamSlot:
     name: str
@@ -297,6 +327,59 @@ class NetEngine:
                 _lib.check(self.lib.vdqn_net_input_grad(self.handle, C.byref(a), _ptr(gx), int(bool(pixel_units)), st), "vdqn_net_input_grad")
             dq.record_stream(torch.cuda.current_stream())
         return (grads, gx) if want_input_grad else grads
+
+    def _bwd_for(self, n_samples: int) -> torch.Tensor:
+        bwd = getattr(self, "_bwd_ws", None)
+        if bwd is None or bwd[0] != n_samples:
+            bwd = self._bwd_ws = (n_samples, torch.empty(self.bwd_bytes(n_samples), dtype=torch.uint8, device=self.device))
+        return bwd[1]
+
+    def backward_data(self, acts: torch.Tensor, packed: torch.Tensor, dq: torch.Tensor, n_samples: int, pixel_units: bool = False) -> torch.Tensor:
+        """dL/d(frames) f32 [n_samples * num_frames, 3, 224, 224] of one `forward_saved` / `forward_attrib` call from dL/dQ, and nothing
+        else (vdqn_net_backward_data): the data-gradient chain on the current stream, no weight gradient, no flat gradient buffer.
+        The bits of `backward_from_dq(.., want_input_grad=True)`'s gx.  extra_capacity only."""
+        self._need_gpu()
+        if not self.extra_capacity:
+            raise _lib.VdqnError("backward_data: ARCHITECTURE='basic' has no frame gradient (extra_capacity only)")
+        with torch.cuda.device(self.device):
+            dq = dq.to(device=self.device, dtype=torch.float32).contiguous()
+            a = _lib.StepArgs()
+            a.packed_online = _ptr(packed)
+            a.batch = a.acts_samples = n_samples
+            a.acts_online, a.bwd = _ptr(acts), _ptr(self._bwd_for(n_samples))
+            gx = torch.empty((n_samples * self.num_frames, 3, 224, 224), dtype=torch.float32, device=self.device)
+            _lib.check(self.lib.vdqn_net_backward_data(self.handle, C.byref(a), _ptr(dq), _ptr(gx), int(bool(pixel_units)), _stream()),
+                       "vdqn_net_backward_data")
+            dq.record_stream(torch.cuda.current_stream())
+        return gx
+
+    def forward_attrib(self, src: torch.Tensor, n_copies: int, packed: torch.Tensor, *, coef: Optional[torch.Tensor] = None, baseline=None,
+                       sigma=None, seed: int = 0, s0: int = 0, i0: int = 0, acts: Optional[torch.Tensor] = None):
+        """`forward_saved` over `n_copies` perturbed copies of the frames `src` (uint8 [n,224,224,3] or f32 [n,3,224,224], n a whole
+        number of samples), built by the pack itself (vdqn_net_forward_attrib; arguments as ops.attrib_pack): -> (q [n_copies * n /
+        num_frames, num_classes * action_dim], acts).  Copy s of sample b is sample s * (n / num_frames) + b.  `acts`: a workspace
+        of that many samples to reuse."""
+        self._need_gpu()
+        if not self.extra_capacity:
+            raise _lib.VdqnError("forward_attrib: ARCHITECTURE='basic' has no frame gradient to attribute with (extra_capacity only)")
+        if (coef is None) == (sigma is None):
+            raise _lib.VdqnError("forward_attrib: give coef (path mode) or sigma (noise mode), not both")
+        shared, keep = attrib_source_args(src, baseline)
+        n_samples, rest = divmod(n_copies * src.shape[0], self.num_frames)
+        if rest or src.shape[0] % self.num_frames or n_copies < 1:
+            raise _lib.VdqnError(f"forward_attrib: {n_copies} copies of {src.shape[0]} frames are not whole samples of {self.num_frames} frames")
+        if n_samples > self.max_batch:
+            raise _lib.VdqnError(f"batch {n_samples} exceeds max_batch {self.max_batch}")
+        with torch.cuda.device(self.device):
+            q = torch.empty((n_samples, self.num_classes * self.action_dim), dtype=torch.float32, device=self.device)
+            if acts is None:
+                acts = torch.empty(self.acts_bytes(n_samples), dtype=torch.uint8, device=self.device)
+            sg = None if sigma is None else (C.c_float * 3)(*[float(v) for v in sigma])
+            _lib.check(self.lib.vdqn_net_forward_attrib(self.handle, _ptr(packed), *shared, n_copies, 0 if coef is not None else 1, _ptr(coef), sg,
+                                                        int(seed) & (2**64 - 1), s0, i0, n_samples, _ptr(acts), _ptr(q), _stream()),
+                       "vdqn_net_forward_attrib")
+        del keep
+        return q, acts
 
     # ---- SyncBN (ARCHITECTURE='basic' under data parallelism) ----------------------------------------
     def set_bn_sync(self, world_size: int, allreduce=None) -> None:

@@ -34,6 +34,7 @@ from collections import OrderedDict
 import torch
 import torch.nn as nn
 
+from . import ops
 from .algos import ALGOS
 from .engine import NetEngine, _say_once, head_kept_message
 
@@ -52,7 +53,7 @@ class _QFunction(torch.autograd.Function):
     backward of that call from dL/dQ.  `params` are the module's trainable Parameters (slot order); their gradients are slices
     of one flat buffer.
     Frames that require a gradient (f32 [n_samples, F, 3, 224, 224]) receive dL/d(frames) from the same backward, one launch
-    behind its last stage (the weight gradients are computed on that path too, and dropped where no parameter asks for them)."""
+    behind its last stage; where no parameter asks for a gradient, from the data-gradient chain alone (vdqn_net_backward_data)."""
 
     @staticmethod
     def forward(ctx, module, frames, src_kind, n_samples, *params):
@@ -67,6 +68,10 @@ class _QFunction(torch.autograd.Function):
     def backward(ctx, gq):
         module, eng = ctx.module, ctx.module.engine
         want_gx = ctx.needs_input_grad[1]
+        if want_gx and not any(ctx.needs_input_grad[4:]):  # a frozen network: the data-gradient chain alone, the same bits
+            gx = eng.backward_data(ctx.acts, ctx.packed, gq, ctx.n).view(ctx.frames_shape)
+            ctx.acts = ctx.packed = None
+            return (None, gx, None, None) + (None,) * len(ctx.needs_input_grad[4:])
         flat = eng.backward_from_dq(ctx.acts, ctx.packed, gq, ctx.n, want_input_grad=want_gx)
         gx = None
         if want_gx:
@@ -425,7 +430,7 @@ class HabitatDQNMultiAction(nn.Module):
             with torch.no_grad():
                 packed = self._packed_with_dgrad()
                 _, acts = eng.forward_saved(frames, src_kind, b, packed)
-                _, gx = eng.backward_from_dq(acts, packed, dq, b, want_input_grad=True, pixel_units=pixel_units)
+                gx = eng.backward_data(acts, packed, dq, b, pixel_units=pixel_units)
         finally:
             self.training = was_training
         return gx.view(b, self.num_frames, 3, 224, 224)
@@ -440,7 +445,148 @@ class HabitatDQNMultiAction(nn.Module):
         act = q[:, category].argmax(-1) if action is None else torch.full((q.shape[0],), int(action), device=q.device)
         dq = torch.zeros_like(q)
         dq[torch.arange(q.shape[0], device=q.device), category, act] = 1.0
-        return self.input_gradient(frames, dq, pixel_units=(frames.dtype == torch.uint8)).abs().amax(2)
+        gx = self.input_gradient(frames, dq, pixel_units=(frames.dtype == torch.uint8))
+        return ops.attrib_finish(gx.view(-1, 3, 224, 224)).view(gx.shape[0], self.num_frames, 224, 224)
+
+    # ---- attribution: integrated gradients and SmoothGrad on the engine (csrc/attrib.hip) ------------------------------------------
+    def _attrib_frames(self, what, frames):
+        """-> (frames [B, F, ...] contiguous on the device, whether a frame axis was added); refuses 'basic' and bad shapes by name."""
+        if not self.extra_capacity:
+            raise NotImplementedError(f"{what}: ARCHITECTURE='basic' has no gradient of a frame on the HIP engine (extra_capacity only)")
+        added = self.num_frames == 1 and frames.dim() == 4
+        if added:
+            frames = frames.unsqueeze(1)
+        if frames.dim() != 5 or frames.shape[1] != self.num_frames:
+            raise Exception("bad shape")
+        frames = (frames if frames.dtype == torch.uint8 else frames.detach().float()).to(self.engine.device).contiguous()
+        return frames, added
+
+    def _attrib_target(self, frames, category, action):
+        """(q [B, C, A], act [B], dq [B, C * A]) at `frames`: the one-hot dL/dQ of (category, action), action None = greedy."""
+        with torch.no_grad():
+            q = self.forward(frames)
+        act = q[:, category].argmax(-1) if action is None else torch.full((q.shape[0],), int(action), device=q.device)
+        dq = torch.zeros_like(q)
+        dq[torch.arange(q.shape[0], device=q.device), category, act] = 1.0
+        return q, act, dq.view(q.shape[0], -1)
+
+    def _attrib_accumulate(self, frames, dq, n_copies, weight, squared, pixel_units, **pack):
+        """sum over `n_copies` perturbed copies of weight * gradient (squared: weight * gradient^2), f32 [B * F, 3, 224, 224]: chunks of
+        max(1, max_batch // B) copies per forward / backward pair, the perturbed operand built by the pack (`pack`: coef / baseline, or
+        sigma / seed / i0, as NetEngine.forward_attrib takes them), the sum continued on the device in ascending copy order."""
+        eng = self.engine
+        b = frames.shape[0]
+        src = frames.view((b * self.num_frames,) + tuple(frames.shape[2:]))
+        chunk = max(1, eng.max_batch // b)
+        w = torch.full((n_copies,), weight, dtype=torch.float32, device=eng.device)
+        coef = pack.pop("coef", None)
+        packed = self._packed_with_dgrad()
+        acc, acts = None, None
+        for k0 in range(0, n_copies, chunk):
+            k = min(chunk, n_copies - k0)
+            if acts is not None and k * b != acts_samples:
+                acts = None
+            part = dict(pack, coef=coef[k0:k0 + k]) if coef is not None else dict(pack, s0=k0)
+            _, acts = eng.forward_attrib(src, k, packed, acts=acts, **part)
+            acts_samples = k * b
+            gx = eng.backward_data(acts, packed, dq.repeat(k, 1), k * b, pixel_units=pixel_units)
+            acc = ops.attrib_reduce(gx, w[k0:k0 + k], acc, squared=squared)
+        return acc
+
+    def integrated_gradients(self, frames, category, action=None, steps=32, baseline=None, pixel_units=False, return_delta=False):
+        """f32 [B, F, 3, 224, 224] (a 4-D input: [B, 3, 224, 224]): integrated gradients of Q[category, action] along the straight
+        path from the baseline b to the frames x, (x - b) * mean_k dQ/dx at b + c_k (x - b) with the `steps` midpoints c_k =
+        float32((k + 0.5) / steps); x, b and the gradient in normalised units, with pixel_units times 1 / (255 std_c).  baseline:
+        None = a black frame (pixel value 0), three pixel values (0 .. 255, one per colour), or frames shaped and typed like `frames`.
+        action None: the greedy action at `frames`.  return_delta: -> (attr, delta) with delta f32 [B] = sum(attr) - (Q(x) - Q(b)),
+        the completeness gap (of the normalised-unit attribution), from one more forward over [x; b].  The path points are built
+        inside the input pack and the sum runs on the device (vdqn_net_forward_attrib, vdqn_net_backward_data, vdqn_attrib_reduce /
+        _finish); the module's training flag is left as it was.  extra_capacity only."""
+        frames, added = self._attrib_frames("integrated_gradients", frames)
+        if not isinstance(steps, int) or isinstance(steps, bool) or steps < 1:
+            raise ValueError(f"integrated_gradients: steps must be an integer >= 1, not {steps!r}")
+        if isinstance(baseline, torch.Tensor):
+            if added and baseline.dim() == 4:
+                baseline = baseline.unsqueeze(1)
+            if baseline.shape != frames.shape or (baseline.dtype == torch.uint8) != (frames.dtype == torch.uint8):
+                raise ValueError(f"integrated_gradients: a baseline tensor must have the frames' shape and kind ({frames.dtype} "
+                                 f"{tuple(frames.shape)}), not {baseline.dtype} {tuple(baseline.shape)}")
+            baseline = (baseline if baseline.dtype == torch.uint8 else baseline.detach().float()).to(frames.device).contiguous()
+        else:
+            try:
+                pixels = [0.0, 0.0, 0.0] if baseline is None else [float(v) for v in baseline]
+            except TypeError:
+                pixels = []
+            if len(pixels) != 3 or not all(0.0 <= v <= 255.0 for v in pixels):
+                raise ValueError(f"integrated_gradients: baseline must be None, three pixel values in [0, 255] or frames shaped like the input, not {baseline!r}")
+            baseline = ops.norm_pixel(pixels)
+        eng = self.engine
+        b = frames.shape[0]
+        if b > eng.max_batch:
+            parts = [self.integrated_gradients(frames[i:i + eng.max_batch], category, action, steps,
+                                               baseline[i:i + eng.max_batch] if isinstance(baseline, torch.Tensor) else pixels, pixel_units, True)
+                     for i in range(0, b, eng.max_batch)]
+            attr = torch.cat([p[0] for p in parts], 0)
+            attr = attr.squeeze(1) if added else attr
+            return (attr, torch.cat([p[1] for p in parts], 0)) if return_delta else attr
+        was_training = self.training
+        self.training = False  # (this module's flag alone, as in state_values)
+        try:
+            with torch.no_grad():
+                _, act, dq = self._attrib_target(frames, category, action)
+                base_src = baseline.view((-1,) + tuple(frames.shape[2:])) if isinstance(baseline, torch.Tensor) else baseline
+                coef = torch.tensor([(k + 0.5) / steps for k in range(steps)], dtype=torch.float32, device=eng.device)
+                acc = self._attrib_accumulate(frames, dq, steps, 1.0 / steps, False, False, coef=coef, baseline=base_src)
+                src = frames.view((-1,) + tuple(frames.shape[2:]))
+                attr = ops.attrib_finish(acc, src, base_src, pixel_units=pixel_units)
+                delta = None
+                if return_delta:
+                    plain = ops.attrib_finish(acc, src, base_src) if pixel_units else attr
+                    ends = torch.tensor([1.0, 0.0], dtype=torch.float32, device=eng.device)
+                    packed = self._packed_with_dgrad()
+                    if 2 * b <= eng.max_batch:
+                        q2, _ = eng.forward_attrib(src, 2, packed, coef=ends, baseline=base_src)
+                    else:
+                        q2 = torch.cat([eng.forward_attrib(src, 1, packed, coef=ends[k:k + 1], baseline=base_src)[0] for k in range(2)], 0)
+                    q2 = q2.view(2, b, self.num_classes, self.action_dim)[:, torch.arange(b, device=eng.device), category, act]
+                    delta = (plain.view(b, -1).double().sum(1) - (q2[0].double() - q2[1].double())).float()
+        finally:
+            self.training = was_training
+        attr = attr.view(b, 3, 224, 224) if added else attr.view(b, self.num_frames, 3, 224, 224)
+        return (attr, delta) if return_delta else attr
+
+    def smoothgrad(self, frames, category, action=None, samples=32, sigma=0.15, squared=False, seed=0, _i0=0):
+        """f32 [B, F, 224, 224] (a 4-D input: [B, 224, 224]): SmoothGrad, the maximum over colour of |mean over `samples` noisy copies of
+        dQ[category, action] / d pixel| (squared: of the mean of its square).  The copies are x + sigma_c z with sigma_c = sigma / std_c,
+        `sigma` a fraction of each channel's normalised range, and z the unit-variance counter-hash noise of (seed, copy, image,
+        element) (include/vdqn.h), drawn inside the input pack: a run draws the same noise however it is cut into chunks or batches.
+        Units as `saliency`: uint8 frames per unit of the pixel value, float frames per unit of the normalised value.  action None: the
+        greedy action at the clean frames.  The module's training flag is left as it was.  extra_capacity only."""
+        frames, added = self._attrib_frames("smoothgrad", frames)
+        if not isinstance(samples, int) or isinstance(samples, bool) or samples < 1:
+            raise ValueError(f"smoothgrad: samples must be an integer >= 1, not {samples!r}")
+        sigma = float(sigma)
+        if not (0.0 <= sigma <= 1.0):  # (a NaN fails both comparisons)
+            raise ValueError(f"smoothgrad: sigma must be in [0, 1] (a fraction of each channel's normalised range), not {sigma}")
+        eng = self.engine
+        b = frames.shape[0]
+        if b > eng.max_batch:
+            out = torch.cat([self.smoothgrad(frames[i:i + eng.max_batch], category, action, samples, sigma, squared, seed, _i0 + i * self.num_frames)
+                             for i in range(0, b, eng.max_batch)], 0)
+            return out.squeeze(1) if added and out.dim() == 4 else out
+        import numpy as np
+        sig = np.float32(sigma) / np.array([0.229, 0.224, 0.225], dtype=np.float32)
+        was_training = self.training
+        self.training = False  # (this module's flag alone, as in state_values)
+        try:
+            with torch.no_grad():
+                _, _, dq = self._attrib_target(frames, category, action)
+                acc = self._attrib_accumulate(frames, dq, samples, 1.0 / samples, bool(squared), frames.dtype == torch.uint8,
+                                              sigma=sig, seed=seed, i0=_i0)
+                out = ops.attrib_finish(acc)
+        finally:
+            self.training = was_training
+        return out.view(b, 224, 224) if added else out.view(b, self.num_frames, 224, 224)
 
 
 def build_model(config, max_batch=None):

@@ -9,7 +9,7 @@ from typing import Optional
 import torch
 
 from . import _lib
-from .engine import _ptr, _stream, require_gpu
+from .engine import _ptr, _stream, attrib_source_args, norm_pixel, require_gpu  # noqa: F401 (re-exported)
 
 TORCH_DTYPE = {_lib.VDQN_F32: torch.float32, _lib.VDQN_BF16: torch.bfloat16}
 
@@ -188,6 +188,67 @@ def stem_input_grad(g_pool: torch.Tensor, idx: torch.Tensor, wt: torch.Tensor, p
     scale = (C.c_float * 3)(*[float(v) for v in stem_pixel_scale()]) if pixel_units else None
     _lib.check(lib.vdqn_stem_input_grad(_ptr(g_pool), _ptr(idx), _ptr(wt), scale, _ptr(out), n, code, _ptr(ws), max(nbytes, 0), _stream()),
                "vdqn_stem_input_grad")
+    return out
+
+
+def attrib_pack(src: torch.Tensor, n_copies: int, dtype: torch.dtype, *, coef: Optional[torch.Tensor] = None, baseline=None, sigma=None,
+                seed: int = 0, s0: int = 0, i0: int = 0) -> torch.Tensor:
+    """`n_copies` perturbed copies of the n images of `src` as the stem operand [n_copies * n, 115, 115, 16] of `dtype` (copy s of
+    image i at s * n + i), equal to pack_input of the perturbed float frames.  coef (device f32 [n_copies]): path mode, x_s = b +
+    coef[s] * (x - b) with the baseline of attrib_source_args; sigma (three floats, normalised units): noise mode, x_s = x + sigma_c * z
+    with z the counter-hash noise of (seed, s0 + s, i0 + i, element) (include/vdqn.h)."""
+    lib = _lib.load()
+    require_gpu()
+    if (coef is None) == (sigma is None):
+        raise ValueError("attrib_pack: give coef (path mode) or sigma (noise mode), not both")
+    shared, keep = attrib_source_args(src, baseline)
+    mode = 0 if coef is not None else 1
+    if coef is not None and (coef.dtype != torch.float32 or coef.numel() != n_copies or coef.device != src.device or not coef.is_contiguous()):
+        raise ValueError(f"attrib_pack: coef must be a contiguous float32 device tensor of {n_copies} elements")
+    sg = None if sigma is None else (C.c_float * 3)(*[float(v) for v in sigma])
+    dst = torch.empty((max(n_copies, 1) * src.shape[0], 115, 115, 16), dtype=dtype, device=src.device)
+    _lib.check(lib.vdqn_attrib_pack(*shared, n_copies, mode, _ptr(coef), sg, int(seed) & (2**64 - 1), s0, i0, _ptr(dst), dtype_code(dst), _stream()),
+               "vdqn_attrib_pack")
+    del keep
+    return dst
+
+
+def attrib_reduce(g: torch.Tensor, w: torch.Tensor, acc: Optional[torch.Tensor] = None, squared: bool = False) -> torch.Tensor:
+    """acc[i] (+)= sum_s w[s] * g[s * n + i] (squared: w[s] * g * g) in ascending s: g f32 [S * n, 3, 224, 224], w device f32 [S]; acc
+    None: a new f32 [n, 3, 224, 224] is written, else `acc` is continued in place (chunks then give the bits of one call)."""
+    lib = _lib.load()
+    S = w.numel()
+    if g.dtype != torch.float32 or w.dtype != torch.float32 or S < 1 or g.dim() != 4 or g.shape[0] % S or tuple(g.shape[1:]) != (3, 224, 224):
+        raise ValueError(f"attrib_reduce: g must be float32 [S * n, 3, 224, 224] and w float32 [S], not {tuple(g.shape)} and {tuple(w.shape)}")
+    n = g.shape[0] // S
+    cont = acc is not None
+    if cont and (acc.dtype != torch.float32 or tuple(acc.shape) != (n, 3, 224, 224) or not acc.is_contiguous()):
+        raise ValueError(f"attrib_reduce: acc must be contiguous float32 [{n}, 3, 224, 224]")
+    if not cont:
+        acc = torch.empty((n, 3, 224, 224), dtype=torch.float32, device=g.device)
+    _lib.check(lib.vdqn_attrib_reduce(_ptr(g.contiguous()), _ptr(w.contiguous()), _ptr(acc), n, S, int(bool(squared)), int(cont), _stream()),
+               "vdqn_attrib_reduce")
+    return acc
+
+
+def attrib_finish(acc: torch.Tensor, src: Optional[torch.Tensor] = None, baseline=None, pixel_units: bool = False) -> torch.Tensor:
+    """src given: integrated gradients' read-out acc * (x - b) f32 [n, 3, 224, 224], x and b as attrib_pack takes them, with
+    pixel_units times stem_pixel_scale().  src None: the saliency read-out max over colour of |acc|, f32 [n, 224, 224]."""
+    lib = _lib.load()
+    if acc.dtype != torch.float32 or acc.dim() != 4 or tuple(acc.shape[1:]) != (3, 224, 224):
+        raise ValueError(f"attrib_finish: acc must be float32 [n, 3, 224, 224], not {acc.dtype} {tuple(acc.shape)}")
+    acc = acc.contiguous()
+    n = acc.shape[0]
+    if src is None:
+        out = torch.empty((n, 224, 224), dtype=torch.float32, device=acc.device)
+        _lib.check(lib.vdqn_attrib_finish(_ptr(acc), None, 0, None, None, n, 1, 0, _ptr(out), _stream()), "vdqn_attrib_finish")
+        return out
+    shared, keep = attrib_source_args(src, baseline)
+    if src.shape[0] != n:
+        raise ValueError(f"attrib_finish: acc has {n} images, src {src.shape[0]}")
+    out = torch.empty_like(acc)
+    _lib.check(lib.vdqn_attrib_finish(_ptr(acc), *shared, 0, int(bool(pixel_units)), _ptr(out), _stream()), "vdqn_attrib_finish")
+    del keep
     return out
 
 
