@@ -40,8 +40,13 @@ def conv2d(x: torch.Tensor, wt: torch.Tensor, *, ho: int, wo: int, co: int, r: i
            relu: bool = False, mode: int = 0, pix_stride: Optional[int] = None, ci: Optional[int] = None,
            want_f32: bool = False, ldo: Optional[int] = None, want_colsum: bool = False,
            wt2: Optional[torch.Tensor] = None, bias2: Optional[torch.Tensor] = None, co2: int = 0, relu2: bool = False,
-           in2: Optional[torch.Tensor] = None, precision: Optional[str] = None):
+           in2: Optional[torch.Tensor] = None, precision: Optional[str] = None,
+           out: Optional[torch.Tensor] = None, out_f32: Optional[torch.Tensor] = None, colsum: Optional[torch.Tensor] = None):
     """x: [n, hi, wi, c] NHWC; wt: [co_pad, r, s, ci].  Returns out [n, ho, wo, ldo] (and the f32 copy).
+    out / out_f32 / colsum: caller-allocated outputs ([n, ho, wo, ldo] of x's dtype / of f32; f32 [entries, ldo] with at least the
+    entries want_colsum would allocate), written in place of fresh tensors — what the call does not write keeps the caller's bytes.
+    out_f32 / colsum imply want_f32 / want_colsum.  With any of the three given the return value is (out, out_f32, colsum), None for
+    what the call has not (a forward sibling call still returns (out, out2)).
     precision="bf16x3" (f32 tensors): the GEMM as split bf16 x 3 instead of exact f32 MFMAs (gemm_dtype_code).
     Fused sibling 1x1 / stride 2 (include/vdqn.h): forward — wt2 [co2, 1, 1, ci] (+ bias2, relu2) gives a second output
     (returned after `out`); data gradient — in2 [n, hi, wi, ci2] and wt2 [co, 1, 1, ci2] add the sibling's gradient."""
@@ -51,8 +56,16 @@ def conv2d(x: torch.Tensor, wt: torch.Tensor, *, ho: int, wo: int, co: int, r: i
     ci = cx if ci is None else ci
     pix_stride = cx if pix_stride is None else pix_stride
     ldo = co if ldo is None else ldo
-    out = torch.empty((n, ho, wo, ldo), dtype=x.dtype, device=x.device)
-    out_f32 = torch.empty((n, ho, wo, ldo), dtype=torch.float32, device=x.device) if want_f32 else None
+    given = out is not None or out_f32 is not None or colsum is not None
+    want_f32 = want_f32 or out_f32 is not None
+    want_colsum = want_colsum or colsum is not None
+    for name, t, dt in (("out", out, x.dtype), ("out_f32", out_f32, torch.float32)):
+        if t is not None and (tuple(t.shape) != (n, ho, wo, ldo) or t.dtype != dt or t.device != x.device or not t.is_contiguous()):
+            raise ValueError(f"conv2d: {name} must be a contiguous {dt} tensor [{n}, {ho}, {wo}, {ldo}] on {x.device}")
+    if out is None:
+        out = torch.empty((n, ho, wo, ldo), dtype=x.dtype, device=x.device)
+    if out_f32 is None and want_f32:
+        out_f32 = torch.empty((n, ho, wo, ldo), dtype=torch.float32, device=x.device)
     a = _lib.ConvArgs()
     a.in_, a.wt, a.bias, a.resid, a.mask = _ptr(x), _ptr(wt), _ptr(bias), _ptr(resid), _ptr(mask)
     a.out, a.out_f32 = _ptr(out), _ptr(out_f32)
@@ -76,11 +89,18 @@ def conv2d(x: torch.Tensor, wt: torch.Tensor, *, ho: int, wo: int, co: int, r: i
             n_tiles = sum((n * hc * wc + rows - 1) // rows for hc in ((ho + 1) // 2, ho // 2) for wc in ((wo + 1) // 2, wo // 2))
         else:
             n_tiles = (n * ho * wo + rows - 1) // rows
-        part = torch.empty((n_tiles, ldo), dtype=torch.float32, device=x.device)
+        part = colsum
+        if part is None:
+            part = torch.empty((n_tiles, ldo), dtype=torch.float32, device=x.device)
+        elif (part.dim() != 2 or part.shape[0] < n_tiles or part.shape[1] != ldo or part.dtype != torch.float32 or part.device != x.device
+              or not part.is_contiguous()):
+            raise ValueError(f"conv2d: colsum must be a contiguous float32 tensor [>= {n_tiles}, {ldo}] on {x.device}")
     a.colsum_part = _ptr(part)
     _lib.check(lib.vdqn_conv2d(C.byref(a), _stream()), "vdqn_conv2d")
-    if out2 is not None:
+    if out2 is not None:  # (a forward sibling has neither an f32 copy nor column sums: the library refuses them)
         return out, out2
+    if given:
+        return out, out_f32, part
     if want_colsum:
         return out, part
     return (out, out_f32) if want_f32 else out
