@@ -106,33 +106,81 @@ def conv2d(x: torch.Tensor, wt: torch.Tensor, *, ho: int, wo: int, co: int, r: i
     return (out, out_f32) if want_f32 else out
 
 
+def _wgrad_args(*, n, hi, wi, ci, pix_stride, ho, wo, co, ldg, r, s, stride, pad, splitk, code):
+    a = _lib.WgradArgs()
+    a.n_img, a.hi, a.wi, a.ci, a.pix_stride = n, hi, wi, ci, pix_stride
+    a.ho, a.wo, a.co, a.ldg = ho, wo, co, ldg
+    a.r, a.s, a.stride, a.pad = r, s, stride, pad
+    a.splitk, a.dtype = splitk, code
+    return a
+
+
+def _wgrad_workspace_query(lib, a) -> int:
+    nbytes = lib.vdqn_conv2d_wgrad_workspace_bytes(C.byref(a))
+    if nbytes < 0:
+        _lib.check(-1, "vdqn_conv2d_wgrad_workspace_bytes")
+    return nbytes
+
+
+def conv2d_wgrad_workspace_bytes(*, n: int, hi: int, wi: int, ci: int, ho: int, wo: int, co: int, r: int, s: int, stride: int, pad: int,
+                                 dtype: torch.dtype = torch.bfloat16, precision: Optional[str] = None, ldg: Optional[int] = None,
+                                 pix_stride: Optional[int] = None, splitk: int = 0) -> int:
+    """Bytes of the workspace the deterministic mode of conv2d_wgrad needs for this geometry (vdqn_conv2d_wgrad_workspace_bytes: one
+    partial copy of dw per split that has pixels).  Needs no GPU.  A geometry the library refuses raises VdqnError with its message.
+    ldg defaults to co padded to 64, pix_stride to ci."""
+    lib = _lib.load()
+    code = gemm_dtype_code(torch.empty(0, dtype=dtype), precision)
+    a = _wgrad_args(n=n, hi=hi, wi=wi, ci=ci, pix_stride=ci if pix_stride is None else pix_stride, ho=ho, wo=wo, co=co,
+                    ldg=(co + 63) // 64 * 64 if ldg is None else ldg, r=r, s=s, stride=stride, pad=pad, splitk=splitk, code=code)
+    return _wgrad_workspace_query(lib, a)
+
+
+def _check_given(what, name, t, shape, dtype, device):
+    if tuple(t.shape) != tuple(shape) or t.dtype != dtype or t.device != device or not t.is_contiguous():
+        raise ValueError(f"{what}: {name} must be a contiguous {dtype} tensor {list(shape)} on {device}")
+
+
+def _check_workspace(what, ws, nbytes, device):
+    if ws.dtype != torch.uint8 or ws.dim() != 1 or not ws.is_contiguous() or ws.device != device or ws.numel() < nbytes:
+        raise ValueError(f"{what}: workspace must be a contiguous uint8 tensor of at least {nbytes} bytes on {device}")
+
+
 def conv2d_wgrad(gy: torch.Tensor, x: torch.Tensor, *, co: int, r: int, s: int, stride: int, pad: int,
                  ci: Optional[int] = None, pix_stride: Optional[int] = None, splitk: int = 0, want_dbias: bool = True,
-                 deterministic: bool = False, poison_workspace: bool = False, precision: Optional[str] = None):
+                 deterministic: bool = False, poison_workspace: bool = False, precision: Optional[str] = None,
+                 dw: Optional[torch.Tensor] = None, dbias: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None):
     """gy: [n, ho, wo, ldg]; x: [n, hi, wi, c].  Returns dw f32 [co_pad, r, s, ci] (and dbias [co_pad]).
     precision="bf16x3" (f32 tensors): split bf16 x 3 MFMAs (gemm_dtype_code).
     deterministic: the two-stage ordered reduction (a workspace of vdqn_conv2d_wgrad_workspace_bytes) instead of atomics;
-    poison_workspace fills that workspace with NaN first (tests: nothing the call does not write may reach dw)."""
+    poison_workspace fills that workspace with NaN first (tests: nothing the call does not write may reach dw).
+    dw / dbias: caller-allocated f32 [co_pad, r, s, ci] / [co_pad], ACCUMULATED into (the ABI's dw +=, dbias +=) instead of fresh zero
+    tensors; dbias implies want_dbias.  workspace: a uint8 tensor used instead of the one the call allocates (implies deterministic);
+    it must hold at least conv2d_wgrad_workspace_bytes, and the library is told exactly that many bytes, whatever lies behind."""
     lib = _lib.load()
     n, ho, wo, ldg = gy.shape
     _, hi, wi, cx = x.shape
     ci = cx if ci is None else ci
     pix_stride = cx if pix_stride is None else pix_stride
     co_pad = (co + 63) // 64 * 64
-    dw = torch.zeros((co_pad, r, s, ci), dtype=torch.float32, device=x.device)
-    db = torch.zeros((co_pad,), dtype=torch.float32, device=x.device) if want_dbias else None
-    a = _lib.WgradArgs()
+    want_dbias = want_dbias or dbias is not None
+    if dw is not None:
+        _check_given("conv2d_wgrad", "dw", dw, (co_pad, r, s, ci), torch.float32, x.device)
+    else:
+        dw = torch.zeros((co_pad, r, s, ci), dtype=torch.float32, device=x.device)
+    if dbias is not None:
+        _check_given("conv2d_wgrad", "dbias", dbias, (co_pad,), torch.float32, x.device)
+    db = dbias if dbias is not None else (torch.zeros((co_pad,), dtype=torch.float32, device=x.device) if want_dbias else None)
+    a = _wgrad_args(n=n, hi=hi, wi=wi, ci=ci, pix_stride=pix_stride, ho=ho, wo=wo, co=co, ldg=ldg, r=r, s=s, stride=stride, pad=pad,
+                    splitk=splitk, code=gemm_dtype_code(x, precision))
     a.gy, a.x, a.dw, a.dbias = _ptr(gy), _ptr(x), _ptr(dw), _ptr(db)
-    a.n_img, a.hi, a.wi, a.ci, a.pix_stride = n, hi, wi, ci, pix_stride
-    a.ho, a.wo, a.co, a.ldg = ho, wo, co, ldg
-    a.r, a.s, a.stride, a.pad = r, s, stride, pad
-    a.splitk, a.dtype = splitk, gemm_dtype_code(x, precision)
     ws = None
-    if deterministic:
-        nbytes = lib.vdqn_conv2d_wgrad_workspace_bytes(C.byref(a))
-        if nbytes < 0:
-            _lib.check(-1, "vdqn_conv2d_wgrad_workspace_bytes")
-        ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=x.device)
+    if deterministic or workspace is not None:
+        nbytes = _wgrad_workspace_query(lib, a)
+        if workspace is not None:
+            _check_workspace("conv2d_wgrad", workspace, nbytes, x.device)
+            ws = workspace
+        else:
+            ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=x.device)
         if poison_workspace:
             ws.fill_(0xFF)  # every f32 word a NaN
         a.workspace, a.workspace_bytes = _ptr(ws), nbytes
@@ -171,16 +219,27 @@ def maxpool_bwd(gy: torch.Tensor, idx: torch.Tensor, x: Optional[torch.Tensor] =
     return gx
 
 
-def stem_wgrad_pool(g_pool: torch.Tensor, idx: torch.Tensor, t_in: torch.Tensor, deterministic: bool = False) -> torch.Tensor:
+def stem_wgrad_pool(g_pool: torch.Tensor, idx: torch.Tensor, t_in: torch.Tensor, deterministic: bool = False,
+                    dw: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
     """conv1's weight gradient from the pooled gradient: g_pool [n,56,56,64] bf16, idx uint8 (stem_conv_pool / maxpool_fwd),
-    t_in [n,115,115,16] (pack_input) -> dw f32 [64,4,1,64] == conv2d_wgrad(maxpool_bwd(g_pool, idx), t_in) on the stem geometry."""
+    t_in [n,115,115,16] (pack_input) -> dw f32 [64,4,1,64] == conv2d_wgrad(maxpool_bwd(g_pool, idx), t_in) on the stem geometry.
+    dw: caller-allocated f32 [64,4,1,64], accumulated into.  workspace: a uint8 tensor of at least
+    vdqn_stem_wgrad_pool_workspace_bytes(n) used instead of the one the call allocates (implies deterministic); the library is told
+    exactly that many bytes."""
     lib = _lib.load()
     n = g_pool.shape[0]
-    dw = torch.zeros((64, 4, 1, 64), dtype=torch.float32, device=g_pool.device)
+    if dw is not None:
+        _check_given("stem_wgrad_pool", "dw", dw, (64, 4, 1, 64), torch.float32, g_pool.device)
+    else:
+        dw = torch.zeros((64, 4, 1, 64), dtype=torch.float32, device=g_pool.device)
     ws, nbytes = None, 0
-    if deterministic:
+    if deterministic or workspace is not None:
         nbytes = lib.vdqn_stem_wgrad_pool_workspace_bytes(n)
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=g_pool.device)
+        if workspace is not None:
+            _check_workspace("stem_wgrad_pool", workspace, nbytes, g_pool.device)
+            ws = workspace
+        else:
+            ws = torch.empty(nbytes, dtype=torch.uint8, device=g_pool.device)
     _lib.check(lib.vdqn_stem_wgrad_pool(_ptr(g_pool), _ptr(idx), _ptr(t_in), _ptr(dw), n, _ptr(ws), nbytes, _stream()), "vdqn_stem_wgrad_pool")
     return dw
 
