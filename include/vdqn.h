@@ -954,7 +954,8 @@ int vdqn_pack_input_aug_color(const void* src, void* dst, int32_t n_img, int32_t
  *   xa = clamp(x0, 0, 223), xb = clamp(x0 + 1, 0, 223), ya, yb likewise
  *   top = Z[ya][xa] * (256 - wx) + Z[ya][xb] * wx;   bot = the same on row yb;   out = (top * (256 - wy) + bot * wy + 32768) >> 16
  * Z is the frame after shift and mirror (vdqn_pack_input_aug's remap applied to each tap); the colour transform works on the
- * resampled bytes.  {65536, 65536, 0, 0} is the identity on every byte.  Zoom-out and rotation are not covered. */
+ * resampled bytes.  {65536, 65536, 0, 0} is the identity on every byte.  Zoom-out is not covered; rotation is vdqn_pack_input_aug_affine's
+ * (below). */
 /* zoom[i] (int32 [n][4], 16-byte aligned) = the draw of sample first + i of a global batch of `global_batch` samples at update `step`:
  *   h = splitmix64(splitmix64(seed ^ 0x4155475A4F4F4D31 "AUGZOOM1") ^ (step * global_batch + first + i));   h_k = (h >> 16 k) & 0xFFFF
  *   ax = 65536 - ((h_0 * (jz + 1)) >> 16);   ay = aspect ? 65536 - ((h_1 * (jz + 1)) >> 16) : ax
@@ -970,6 +971,38 @@ int vdqn_aug_draw_zoom(uint64_t seed, uint64_t step, int32_t global_batch, int32
  * vdqn_pack_input_aug's (vdqn_pack_input_aug_color's) output. */
 int vdqn_pack_input_aug_zoom(const void* src, void* dst, int32_t n_img, int32_t frames_per_sample, const int32_t* params,
                              const int32_t* color /* NULL ok */, const int32_t* zoom, int32_t n_params, int32_t dtype, void* stream);
+
+/* Random rotation (camera roll) about the picture's centre by an angle uniform in [-J, J], J <= 30 degrees, composed with the sample's
+ * zoom row into ONE affine map and resampled with the zoom's integer bilinear, so the packed operand still equals vdqn_pack_input of
+ * host-augmented frames bit for bit (tests/aug_rotate_oracle.py).  One int32 [8] = {axx, axy, bx, 0, ayx, ayy, by, 0} per SAMPLE (Q16, two
+ * 16-byte vectors), shared by its frames and by s and s'.  ">>" is arithmetic, "/" floors, products are int64; the unit of angle is
+ * 1 / 64 degree.  Output pixel (Y, X) of a frame Z, per channel:
+ *   u = bx + X * axx + Y * axy;  x0 = u >> 16;  wx = (u >> 8) & 255;   v = by + X * ayx + Y * ayy;  y0 = v >> 16;  wy = (v >> 8) & 255
+ *   taps, top, bot and out as vdqn_pack_input_aug_zoom's
+ * Z is the frame after shift and mirror; the colour transform works on the resampled bytes.  Out-of-frame taps replicate the edge.
+ * {65536, 0, 0, 0, 0, 65536, 0, 0} is the identity on every byte; a row with axy = ayx = 0 gives vdqn_pack_input_aug_zoom's output for
+ * {axx, ayy, bx, by}.  Zoom-out is not covered. */
+/* affine[i] (int32 [n][8], 16-byte aligned) = the draw of sample first + i of a global batch of `global_batch` samples at update `step`:
+ *   h = splitmix64(splitmix64(seed ^ 0x415547524F544131 "AUGROTA1") ^ (step * global_batch + first + i))
+ *   k = (((h & 0xFFFF) * (2 jr + 1)) >> 16) - jr                                     the angle, in [-jr, jr]
+ *   t = k * 292818 (Q30 radians);  t2 = (t * t) >> 30;  ONE = 1 << 30
+ *   a = ONE - t2 / 42;  a = ONE - ((t2 * a) >> 30) / 20;  a = ONE - ((t2 * a) >> 30) / 6;   s = (t * a) >> 30
+ *   b = ONE - t2 / 56;  b = ONE - ((t2 * b) >> 30) / 30;  b = ONE - ((t2 * b) >> 30) / 12;  b = ONE - ((t2 * b) >> 30) / 2
+ *   S = (s + 8192) >> 14;  C = (b + 8192) >> 14                                      Q16 sine and cosine, within 2^-16 of the exact ones
+ *   {ax, ay, bxz, byz} = zoom[i] (int32 [n][4], the slice's zoom rows, 16-byte aligned), or {65536, 65536, 0, 0} when zoom is NULL
+ *   axx = (ax * C + 32768) >> 16;  axy = -((ax * S + 32768) >> 16);  bx = bxz + ((223 * (ax - axx - axy)) >> 1)
+ *   ayx = (ay * S + 32768) >> 16;  ayy = (ay * C + 32768) >> 16;     by = byz + ((223 * (ay - ayx - ayy)) >> 1)
+ * i.e. rotate the output pixel centre about index (111.5, 111.5), then apply the zoom map.  jr is int(J * 64 + 0.5), 0 .. 1920; jr = 0
+ * gives {ax, 0, bxz, 0, 0, ay, byz, 0}.  A stream of its own: the other draws at the same seed and update do not depend on it.  Slices
+ * as vdqn_aug_draw. */
+int vdqn_aug_draw_rotate(uint64_t seed, uint64_t step, int32_t global_batch, int32_t first, int32_t n, int32_t jr /* 0 .. 1920 */,
+                         const int32_t* zoom /* NULL = identity */, int32_t* affine, void* stream);
+/* vdqn_pack_input_aug(_color) of the affinely resampled frames: frame i takes params, color and affine row (i / frames_per_sample) %
+ * n_params (params and color int32 [n_params][4], affine int32 [n_params][8], 16-byte aligned; color may be NULL: no colour transform).
+ * axx, ayy are clamped to [0, 65536], axy, ayx to +-65536 and bx, by to +-448 * 65536 (where every tap already sits on an edge) before
+ * use, words 3 and 7 are ignored and every tap is clamped into the frame: any int32 content is safe.  dtype VDQN_BF16 or VDQN_F32. */
+int vdqn_pack_input_aug_affine(const void* src, void* dst, int32_t n_img, int32_t frames_per_sample, const int32_t* params,
+                               const int32_t* color /* NULL ok */, const int32_t* affine, int32_t n_params, int32_t dtype, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Data-parallel exchange: one process per GPU, the flat f32 gradient SUM-all-reduced over RCCL (xGMI)

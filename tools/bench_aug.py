@@ -7,14 +7,18 @@
                       draw launch, vdqn_pack_input_aug_color).
     --compare zoom    "shift" against "zoom": AUG_ZOOM at --zoom (0.25, --aspect: AUG_ZOOM_ASPECT) on top of it (one more draw launch,
                       vdqn_pack_input_aug_zoom: four taps per output pixel where the baseline reads one).
+    --compare rotate  "shift" against "rotate": AUG_ROTATE at --rotate (10 degrees) on top of it (one more draw launch; the stepper packs
+                      the frames itself with vdqn_pack_input_aug_affine, 2-D tiles, and hands them over as packed_frames).  A third mode,
+                      "zoom", runs in the launch-profiler window only: the zoom pack's device time in the same process.
     --compare plain   "off" against "plain", the same unaugmented update: what two modes differ by when nothing differs.
 
     python tools/bench_aug.py --compare zoom [--batch 256] [--steps 30] [--rounds 6 (shift: 5)] [--out profiles/augzoom_bench.json]
+    python tools/bench_aug.py --compare rotate --out profiles/augrot_bench.json
 
 Prints ms/update per mode (every window, the median and the window spread (max - min) / median) and the launch-profiler device time of
 the pack and draw launches over the same 2 B frames (a separate window per mode).  The figures to read are the difference between the
 medians next to the baseline's own window spread and to the 1.5 % of an update DESIGN 3i allows an augmentation, and the mode's pack
-launch next to the baseline's.  The JSON keeps the key names of profiles/aug_bench.json, augcolor_bench.json and augzoom_bench.json."""
+launch next to the baseline's.  The JSON keeps the key names of profiles/aug_bench.json, augcolor_bench.json, augzoom_bench.json and augrot_bench.json."""
 import argparse
 import json
 import os
@@ -30,9 +34,10 @@ sys.path.insert(0, ROOT)
 COMPARISONS = {"plain": ("off", "plain", "pack_input", "pack_input"),
                "shift": ("off", "aug", "pack_input", "pack_input_aug"),
                "color": ("shift", "color", "pack_input_aug", "pack_input_aug_color"),
-               "zoom": ("shift", "zoom", "pack_input_aug", "pack_input_aug_zoom")}
-KERNELS = ("pack_input", "pack_input_aug", "pack_input_aug_color", "pack_input_aug_zoom", "aug_draw", "aug_draw_color", "aug_draw_zoom",
-           "aug_swap_actions")
+               "zoom": ("shift", "zoom", "pack_input_aug", "pack_input_aug_zoom"),
+               "rotate": ("shift", "rotate", "pack_input_aug", "pack_input_aug_affine")}
+KERNELS = ("pack_input", "pack_input_aug", "pack_input_aug_color", "pack_input_aug_zoom", "pack_input_aug_affine", "aug_draw", "aug_draw_color",
+           "aug_draw_zoom", "aug_draw_rotate", "aug_swap_actions")
 
 
 def main():
@@ -47,6 +52,7 @@ def main():
     ap.add_argument("--jitter", type=float, default=0.4)
     ap.add_argument("--zoom", type=float, default=0.25)
     ap.add_argument("--aspect", action="store_true")
+    ap.add_argument("--rotate", type=float, default=10.0)
     ap.add_argument("--bound", type=float, default=0.015)
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
@@ -68,9 +74,10 @@ def main():
     shift = dict(pad=args.pad, flip=True, flip_actions=[1, 2], seed=1)
     j = args.jitter
     settings = {"off": None, "plain": None, "aug": shift, "shift": shift, "color": dict(shift, brightness=j, contrast=j, saturation=j),
-                "zoom": dict(shift, zoom=args.zoom, zoom_aspect=args.aspect)}
+                "zoom": dict(shift, zoom=args.zoom, zoom_aspect=args.aspect), "rotate": dict(shift, rotate=args.rotate)}
     modes = [base, mode]
-    augs = {m: None if settings[m] is None else Augmenter(B, dev, **settings[m]) for m in modes}
+    profiled = modes + (["zoom"] if args.compare == "rotate" else [])  # (the launch-profiler window alone)
+    augs = {m: None if settings[m] is None else Augmenter(B, dev, **settings[m]) for m in profiled}
     uniform_idx = [torch.randint(0, 1 << 30, (B,), device=dev) for _ in range(16)]
 
     def update(k, m):
@@ -81,7 +88,7 @@ def main():
         else:
             params = aug.draw(k)
             stp.step(before[idx], after[idx], 0, aug.actions(act[idx]), rew[idx], term[idx], augment=params, augment_color=aug.color,
-                     augment_zoom=aug.zoom)
+                     augment_zoom=aug.zoom if aug.affine is None else None, augment_affine=aug.affine)
 
     k = 0
     for m in modes:
@@ -100,7 +107,10 @@ def main():
             torch.cuda.synchronize()
             res[m].append((time.perf_counter() - t0) * 1e3 / args.steps)
     kernels = {}
-    for m in modes:
+    for m in profiled:
+        for _ in range(args.warmup if m not in modes else 0):
+            k += 1
+            update(k, m)
         _lib.profile_enable(True)
         for _ in range(args.steps):
             k += 1
@@ -119,6 +129,8 @@ def main():
         out["jitter"] = j
     if args.compare == "zoom":
         out.update(zoom=args.zoom, zoom_aspect=args.aspect)
+    if args.compare == "rotate":
+        out.update(rotate=args.rotate, zoom_in_profile_window=args.zoom)
     out.update({"steps_per_window": args.steps, "rounds": args.rounds, "ms_per_update": res, "ms_per_update_median": med, "window_spread": spread,
                 f"{mode}_over_{base}": over})
     if args.compare == "shift":  # the one comparison with a threshold: an augmentation against none

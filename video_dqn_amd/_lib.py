@@ -147,6 +147,8 @@ _SIGS = {
     "vdqn_pack_input_aug_color": (C.c_int, [c_vp, c_vp, c_i32, c_i32, c_vp, c_vp, c_i32, c_i32, c_vp]),
     "vdqn_aug_draw_zoom": (C.c_int, [C.c_uint64, C.c_uint64, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp]),
     "vdqn_pack_input_aug_zoom": (C.c_int, [c_vp, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_i32, c_i32, c_vp]),
+    "vdqn_aug_draw_rotate": (C.c_int, [C.c_uint64, C.c_uint64, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),
+    "vdqn_pack_input_aug_affine": (C.c_int, [c_vp, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_i32, c_i32, c_vp]),
     "vdqn_clip_workspace_bytes": (c_i64, [c_i32]),
     "vdqn_grad_sumsq": (C.c_int, [c_vp, c_i64, c_vp, c_i32, c_vp]),
     "vdqn_clip_finalize": (C.c_int, [c_vp, c_i32, C.c_double, c_vp, c_vp]),

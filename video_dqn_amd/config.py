@@ -34,7 +34,11 @@ mid-grey 128, inside the same input pack on the GPU), AUG_ZOOM (0.0 = off, in [0
 [1 - AUG_ZOOM, 1] of the frame's, at a uniform position inside the frame, resampled back to 224 x 224 with an integer bilinear filter
 inside the same input pack; a magnification of at most 2, never a zoom-out; one window per update and sample, shared by its frames
 and by s and s'), AUG_ZOOM_ASPECT (False: the window's two sides are drawn independently, each from [1 - AUG_ZOOM, 1], which also
-stretches the picture; needs AUG_ZOOM > 0), GRAD_CLIP_NORM (0.0 = off; > 0: the whole gradient is rescaled so that its global L2 norm
+stretches the picture; needs AUG_ZOOM > 0), AUG_ROTATE (0.0 = off, in [0, 30] degrees: random rotation, camera roll — an angle uniform in
+[-AUG_ROTATE, AUG_ROTATE] about the picture's centre, one per update and sample, shared by its frames and by s and s'; composed with
+the zoom window into one affine map and resampled with the same integer bilinear filter by a tiled pack kernel on the GPU; pixels
+that fall outside the frame replicate its edge; costs one packed-frame buffer of 2 * BATCH_SIZE * NUM_FRAMES * 115 * 115 * 16 elements),
+GRAD_CLIP_NORM (0.0 = off; > 0: the whole gradient is rescaled so that its global L2 norm
 is at most this, torch.nn.utils.clip_grad_norm_: coef = min(1, max_norm / (norm + 1e-6)), norm and coefficient computed on the GPU
 and never read back for the update), WEIGHT_DECAY (0.0: decoupled, as torch.optim.AdamW: p <- p * (1 - lr * wd) in front of the
 Adam update, over every trainable element; resnet.fc, which never receives a gradient, stays untouched), LR_WARMUP_STEPS (0:
@@ -243,6 +247,7 @@ def get_cfg_defaults() -> CfgNode:
     c.AUG_SATURATION = 0.0        # saturation factor, uniform in [1 - AUG_SATURATION, 1 + AUG_SATURATION] (0 = off, <= 1)
     c.AUG_ZOOM = 0.0              # random zoom: the window's side is uniform in [1 - AUG_ZOOM, 1] of the frame's, resampled to 224 (0 = off, <= 0.5)
     c.AUG_ZOOM_ASPECT = False     # draw the window's two sides independently (a stretch); needs AUG_ZOOM > 0
+    c.AUG_ROTATE = 0.0            # random rotation about the picture's centre: the angle is uniform in [-AUG_ROTATE, AUG_ROTATE] degrees (0 = off, <= 30)
     c.GRAD_CLIP_NORM = 0.0        # > 0: rescale the gradient to this global L2 norm at most (clip_grad_norm_, on the GPU); 0 = off
     c.WEIGHT_DECAY = 0.0          # decoupled weight decay (AdamW): p <- p * (1 - lr * WEIGHT_DECAY) in front of the Adam update
     c.LR_WARMUP_STEPS = 0         # the learning rate of update t is multiplied by min(1, t / LR_WARMUP_STEPS)

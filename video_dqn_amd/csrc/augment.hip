@@ -61,6 +61,27 @@
 // Colour jitter works on the resampled bytes: operand = pack(color(zoom(shift_mirror(frames)))).
 // The kernel clamps ax, ay to [0, 65536] and bx, by to +-224 * 65536 first: |u|, |v| < 2^25, and every tap is clamped into the frame,
 // whatever int32 the row holds.  A step of at most 1.0 is also what bounds the rows a pair of packed rows needs (below).
+//
+// Random rotation (camera roll) about the picture's centre, composed with the zoom into one affine map per SAMPLE, int32 [8] = {axx, axy,
+// bx, 0, ayx, ayy, by, 0} in Q16, shared by its F frames and by s and s'.  All integers, ">>" arithmetic, "/" floors; the unit of angle
+// is 1 / 64 degree.  tests/aug_rotate_oracle.py restates it in numpy; the operand is still EXACTLY vdqn_pack_input of host-augmented frames.
+// Draw of sample j of the global batch G at update `step`, Jr = int(J * 64 + 0.5) in 0 .. 1920 (J <= 30 degrees):
+//   key = splitmix64(seed ^ 0x415547524F544131)           "AUGROTA1": a stream of its own, the other draws do not move
+//   h   = splitmix64(key ^ (step * G + j));   k = (((h & 0xFFFF) * (2 Jr + 1)) >> 16) - Jr          in [-Jr, Jr]
+// Sine and cosine of k, Q16, in int64 (rot_sincos): Taylor polynomials in Q30, Horner form; no libm, so numpy gives the same bits
+//   t = k * 292818 (Q30 radians, 292818 = round(pi / 11520 * 2^30), |t| < 2^30);   t2 = (t * t) >> 30;   ONE = 1 << 30
+//   a = ONE - t2 / 42;  a = ONE - ((t2 * a) >> 30) / 20;  a = ONE - ((t2 * a) >> 30) / 6;   s = (t * a) >> 30
+//   b = ONE - t2 / 56;  b = ONE - ((t2 * b) >> 30) / 30;  b = ONE - ((t2 * b) >> 30) / 12;  b = ONE - ((t2 * b) >> 30) / 2
+//   S = (s + 8192) >> 14;   C = (b + 8192) >> 14          S(0) = 0, C(0) = 65536, S odd and C even in k, both within 0.53 * 2^-16 of float64
+// The row, from the sample's zoom row {ax, ay, bxz, byz} (none: the identity {65536, 65536, 0, 0}), products in int64:
+//   axx = (ax * C + 32768) >> 16      axy = -((ax * S + 32768) >> 16)     bx = bxz + ((223 * (ax - axx - axy)) >> 1)
+//   ayx = (ay * S + 32768) >> 16      ayy = (ay * C + 32768) >> 16        by = byz + ((223 * (ay - ayx - ayy)) >> 1)
+// i.e. rotate the output pixel centre about index (111.5, 111.5), then apply the zoom map; k = 0 gives {ax, 0, bxz, 0, 0, ay, byz, 0}.
+// Resample of output pixel (Y, X): u = bx + X * axx + Y * axy, v = by + X * ayx + Y * ayy, then taps, weights and the bilinear exactly as
+// the zoom's (above), on Z, the frame after shift and mirror; colour jitter works on the resampled bytes.  A row without cross terms
+// gives the zoom entry's bits.  The kernel clamps axx, ayy to [0, 65536], axy, ayx to +-65536 and bx, by to +-448 * 65536 first: beyond
+// that origin every tap of every output pixel already sits on one edge (a diagonal term adds at least 0 and a cross term at least
+// -223 * 65536), |u|, |v| < 2^26, and a 32 x 32 tile of output pixels spans at most 62 source pixels per axis (pack_affine_kernel).
 #include "pack_common.h"
 
 namespace {
@@ -74,6 +95,9 @@ constexpr uint64_t kZoomStream = 0x4155475A4F4F4D31ull;
 constexpr int kMaxJz = 32768;              // Q16 width of the zoom's side range: J in [0, 0.5]
 constexpr int kZoomOne = 65536;            // Q16 1.0: the largest source step (no zoom-out)
 constexpr int kZoomMaxOrigin = 224 << 16;  // |bx|, |by| beyond it already select an edge pixel everywhere
+constexpr uint64_t kRotateStream = 0x415547524F544131ull;
+constexpr int kMaxJr = 1920;                  // 30 degrees in 1 / 64 degree
+constexpr int kAffineMaxOrigin = 448 << 16;   // |bx|, |by| beyond it already select an edge pixel everywhere, whatever the cross term
 
 // ---- the draws: one thread per sample --------------------------------------------------------------------------------------------
 // the hash of sample j of the global batch G at update `step`, in the stream `stream` of the run's seed
@@ -115,6 +139,38 @@ __global__ __launch_bounds__(256) void aug_draw_zoom_kernel(uint64_t seed, uint6
   const int ax = kZoomOne - (int)draw16(h, 0, span), ay_own = kZoomOne - (int)draw16(h, 1, span);
   const int ay = aspect ? ay_own : ax;
   zoom[i] = make_int4(ax, ay, zoom_origin(ax, h, 2), zoom_origin(ay, h, 3));
+}
+
+// Q16 sine and cosine of k / 64 degrees, |k| <= 1920 (the arithmetic is written out at the top of this file)
+__device__ __forceinline__ void rot_sincos(int k, int64_t& S, int64_t& C) {
+  constexpr int64_t kOne = (int64_t)1 << 30;
+  const int64_t t = (int64_t)k * 292818;
+  const int64_t t2 = (t * t) >> 30;  // >= 0, as every dividend below: "/" floors
+  int64_t a = kOne - t2 / 42;
+  a = kOne - ((t2 * a) >> 30) / 20;
+  a = kOne - ((t2 * a) >> 30) / 6;
+  int64_t b = kOne - t2 / 56;
+  b = kOne - ((t2 * b) >> 30) / 30;
+  b = kOne - ((t2 * b) >> 30) / 12;
+  b = kOne - ((t2 * b) >> 30) / 2;
+  S = (((t * a) >> 30) + 8192) >> 14;
+  C = (b + 8192) >> 14;
+}
+
+__global__ __launch_bounds__(256) void aug_draw_rotate_kernel(uint64_t seed, uint64_t step, int G, int first, int n, int jr,
+                                                              const int4* __restrict__ zoom, int4* __restrict__ affine) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const uint64_t h = sample_hash(kRotateStream, seed, step, G, first + i);
+  const int k = (int)draw16(h, 0, 2u * (uint32_t)jr + 1u) - jr;
+  const int4 z = zoom ? zoom[i] : make_int4(kZoomOne, kZoomOne, 0, 0);
+  int64_t S, C;
+  rot_sincos(k, S, C);
+  const int64_t ax = z.x, ay = z.y;
+  const int64_t axx = (ax * C + 32768) >> 16, axy = -((ax * S + 32768) >> 16);
+  const int64_t ayx = (ay * S + 32768) >> 16, ayy = (ay * C + 32768) >> 16;
+  affine[2 * i] = make_int4((int)axx, (int)axy, (int)(z.z + ((223 * (ax - axx - axy)) >> 1)), 0);
+  affine[2 * i + 1] = make_int4((int)ayx, (int)ayy, (int)(z.w + ((223 * (ay - ayx - ayy)) >> 1)), 0);
 }
 
 // ---- aug_swap_actions: a0 <-> a1 for the flipped samples, a copy otherwise -------------------------------------------------------
@@ -159,6 +215,39 @@ __device__ __forceinline__ int src_y(const Shift& s, int y) { return clamp223(y 
 __device__ __forceinline__ int src_x3(const Shift& s, int x) {
   const int xs = clamp223(x + s.sx);
   return 3 * (s.flip ? 223 - xs : xs);
+}
+
+// pack_aug_kernel's table fill and saturation stage as functions, for pack_affine_kernel.  pack_aug_kernel keeps them written out in
+// its body: calling these from it changed the code generated for its eight instances (register allocation and scheduling), and those
+// instances stay as they were measured.
+// Thread `tid` of a block of 256 writes entry `tid` of the block's normalisation table; COLOR: at bc(tid), brightness then contrast of
+// byte `tid` under the factors of colour row `row`.  Returns the saturation factor (256 without COLOR).
+template <typename T, bool COLOR>
+__device__ __forceinline__ int pack_lut_fill(T (*lut)[256], int tid, const int4* __restrict__ color, int row) {
+  int fs = 256;
+  int t = tid;
+  if constexpr (COLOR) {
+    const int4 f = color[row];
+    const int fb = min(max(f.x, 0), kMaxFactor), fc = min(max(f.y, 0), kMaxFactor);
+    fs = min(max(f.z, 0), kMaxFactor);
+    t = min(255, (t * fb + 128) >> 8);                  // brightness
+    t = clamp255(128 + (((t - 128) * fc + 128) >> 8));  // contrast about mid-grey (>> of a negative int: arithmetic, i.e. floor)
+  }
+#pragma unroll
+  for (int c = 0; c < 3; ++c) lut[c][tid] = pack_norm_entry<T>(t, c);
+  return fs;
+}
+// a pixel's three elements of the operand from its three bytes: the saturation stage (COLOR), then the table
+template <typename T, bool COLOR>
+__device__ __forceinline__ void pack_pixel(T* o, const int (&px)[3], const T (*lut)[256], int fs) {
+  if constexpr (COLOR) {
+    const int g = (77 * px[0] + 150 * px[1] + 29 * px[2] + 128) >> 8;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) o[c] = lut[c][clamp255(g + (((px[c] - g) * fs + 128) >> 8))];
+  } else {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) o[c] = lut[c][px[c]];
+  }
 }
 
 struct ZoomRow {
@@ -334,6 +423,131 @@ int launch_pack_aug(const char* name, const char* aligned, const void* src, void
   return VDQN_OK;
 }
 
+// ---- the affine pack: rotation (and zoom) as one 2-D resample ----------------------------------------------------------------------
+// Under a cross term an output row no longer reads one source row (at 30 degrees the four output rows of a pair of packed rows read
+// 116 distinct source rows), so pack_aug_kernel's row staging does not carry over.  A block owns a TILE instead: kAffineTile x
+// kAffineTile packed positions of one frame = 32 x 32 output pixels, one thread per packed position (its 2 x 2 pixels x 3 channels, stored
+// with pack_store16: threads that are neighbours in x write contiguous 32 or 64 bytes); 8 x 8 tiles cover the 115 x 115 positions.
+// u and v are affine in (X, Y), so over the tile's output pixels inside the frame they take their extremes at its four corners: the
+// taps lie in the box [x0(umin), x0(umax) + 1] x [y0(vmin), y0(vmax) + 1] of Z, clamped into the frame as the taps are (the clamp is
+// monotone: a clamped tap stays in the clamped box).  The block stages that box of Z — the shift / mirror remap is applied while
+// staging, so the box is indexed in Z's coordinates — as one 32-bit word per pixel, and a tap is one LDS read.  With the clamped
+// coefficients (|each| <= 1.0) 31 steps along X and 31 along Y move u by at most 62 pixels: x0 spans at most 63, the second tap one
+// more, kAffineBox = 65 per axis always holds the box (at 30 degrees and step 1.0 it is at most 45 x 45).  Every LDS index is clamped into
+// the array all the same.
+constexpr int kAffineTile = 16;
+constexpr int kAffineTiles = 8;  // per axis: 8 * 16 >= 115
+constexpr int kAffineBox = 65;
+
+struct AffineRow {
+  int axx, axy, bx, ayx, ayy, by;
+};
+__device__ __forceinline__ AffineRow affine_clamped(const int4 x, const int4 y) {
+  return {min(max(x.x, 0), kZoomOne),         min(max(x.y, -kZoomOne), kZoomOne), min(max(x.z, -kAffineMaxOrigin), kAffineMaxOrigin),
+          min(max(y.x, -kZoomOne), kZoomOne), min(max(y.y, 0), kZoomOne),         min(max(y.z, -kAffineMaxOrigin), kAffineMaxOrigin)};
+}
+
+template <typename T, bool COLOR>
+__global__ __launch_bounds__(256) void pack_affine_kernel(const uint8_t* __restrict__ src, T* __restrict__ dst, int frames_per_sample,
+                                                          const int4* __restrict__ params, const int4* __restrict__ color,
+                                                          const int4* __restrict__ affine, int n_params) {
+  __shared__ uint32_t box[kAffineBox * kAffineBox];
+  __shared__ T lut[3][256];
+  const int n = blockIdx.y;
+  const int tid = threadIdx.x;
+  const int row = (n / frames_per_sample) % n_params;
+  const int fs = pack_lut_fill<T, COLOR>(lut, tid, color, row);
+  const Shift s = shift_clamped(params[row]);
+  const AffineRow a = affine_clamped(affine[2 * row], affine[2 * row + 1]);
+  const int ty = (int)blockIdx.x / kAffineTiles, tx = (int)blockIdx.x - ty * kAffineTiles;
+  const int ly = tid / kAffineTile, lx = tid - ly * kAffineTile;
+  // the tile's output pixels inside the frame, X0 .. X1 by Y0 .. Y1 (never empty: packed 2 .. 113 hold pixels, every tile has some)
+  const int X0 = max(2 * (tx * kAffineTile - 2), 0), X1 = min(2 * (tx * kAffineTile + kAffineTile - 3) + 1, 223);
+  const int Y0 = max(2 * (ty * kAffineTile - 2), 0), Y1 = min(2 * (ty * kAffineTile + kAffineTile - 3) + 1, 223);
+  const int u00 = a.bx + X0 * a.axx + Y0 * a.axy, u01 = a.bx + X1 * a.axx + Y0 * a.axy;
+  const int u10 = a.bx + X0 * a.axx + Y1 * a.axy, u11 = a.bx + X1 * a.axx + Y1 * a.axy;
+  const int v00 = a.by + X0 * a.ayx + Y0 * a.ayy, v01 = a.by + X1 * a.ayx + Y0 * a.ayy;
+  const int v10 = a.by + X0 * a.ayx + Y1 * a.ayy, v11 = a.by + X1 * a.ayx + Y1 * a.ayy;
+  const int zx0 = clamp223(min(min(u00, u01), min(u10, u11)) >> 16), zx1 = clamp223((max(max(u00, u01), max(u10, u11)) >> 16) + 1);
+  const int zy0 = clamp223(min(min(v00, v01), min(v10, v11)) >> 16), zy1 = clamp223((max(max(v00, v01), max(v10, v11)) >> 16) + 1);
+  const int bw = min(zx1 - zx0 + 1, kAffineBox), bh = min(zy1 - zy0 + 1, kAffineBox);
+  const uint8_t* frame = src + (size_t)n * (224 * 672);
+  // Staging: box pixel i = ry * bw + rx goes to thread i % 256, so a wave reads runs of neighbouring pixels of one source row, and
+  // kAffineBatch pixels per thread are loaded before the first is stored: the loads of a batch are in flight together (one pixel per
+  // trip of a loop over the box's rows exposed the full load latency nine times per block and measured 146 us over 512 frames).
+  // i / bw as a multiply and shift: exact for bw <= 65 and i < 65 * bw, where i * m < 2^32.
+  constexpr int kAffineBatch = 4;
+  const int total = bw * bh;
+  const uint32_t m = ((1u << 19) + (uint32_t)bw - 1u) / (uint32_t)bw;
+  for (int i0 = tid; i0 < total; i0 += 256 * kAffineBatch) {
+    uint32_t pix[kAffineBatch];
+    int at[kAffineBatch];
+#pragma unroll
+    for (int j = 0; j < kAffineBatch; ++j) {
+      const int i = min(i0 + 256 * j, total - 1);  // (past the end: the last pixel again, not stored)
+      const int ry = (int)(((uint32_t)i * m) >> 19), rx = i - ry * bw;
+      const uint8_t* p = frame + src_y(s, zy0 + ry) * 672 + src_x3(s, zx0 + rx);
+      pix[j] = (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16);
+      at[j] = ry * kAffineBox + rx;
+    }
+#pragma unroll
+    for (int j = 0; j < kAffineBatch; ++j)
+      if (i0 + 256 * j < total) box[at[j]] = pix[j];
+  }
+  __syncthreads();  // the box and the table are written
+  const int y = ty * kAffineTile + ly, x = tx * kAffineTile + lx;
+  if (y >= 115 || x >= 115) return;
+  const int ys = y - 2, xs = x - 2;
+  __attribute__((aligned(16))) T v[16];
+#pragma unroll
+  for (int e = 0; e < 16; ++e) v[e] = from_f32<T>(0.f);
+  if ((unsigned)ys < 112u && (unsigned)xs < 112u) {
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+#pragma unroll
+      for (int k = 0; k < 2; ++k) {
+        const int X = 2 * xs + k, Y = 2 * ys + r;
+        const int uq = a.bx + X * a.axx + Y * a.axy, vq = a.by + X * a.ayx + Y * a.ayy;
+        const int wx = (uq >> 8) & 255, wy = (vq >> 8) & 255;
+        const int xa = min(max(clamp223(uq >> 16) - zx0, 0), kAffineBox - 1), xb = min(max(clamp223((uq >> 16) + 1) - zx0, 0), kAffineBox - 1);
+        const int ya = min(max(clamp223(vq >> 16) - zy0, 0), kAffineBox - 1), yb = min(max(clamp223((vq >> 16) + 1) - zy0, 0), kAffineBox - 1);
+        const uint32_t taa = box[ya * kAffineBox + xa], tab = box[ya * kAffineBox + xb];
+        const uint32_t tba = box[yb * kAffineBox + xa], tbb = box[yb * kAffineBox + xb];
+        int px[3];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+          const int top = (int)((taa >> (8 * c)) & 255u) * (256 - wx) + (int)((tab >> (8 * c)) & 255u) * wx;
+          const int bot = (int)((tba >> (8 * c)) & 255u) * (256 - wx) + (int)((tbb >> (8 * c)) & 255u) * wx;
+          px[c] = (top * (256 - wy) + bot * wy + 32768) >> 16;
+        }
+        pack_pixel<T, COLOR>(v + 3 * (2 * r + k), px, lut, fs);
+      }
+    }
+  }
+  pack_store16(dst + ((size_t)n * 115 * 115 + (size_t)y * 115 + x) * 16, v);
+}
+
+// launch_pack_aug for the affine entry: the same checks, the same profiler scope naming, the instance for (T, colour rows given)
+int launch_pack_affine(const char* name, const void* src, void* dst, int32_t n_img, int32_t frames_per_sample, const int32_t* params,
+                       const int32_t* color, const int32_t* affine, int32_t n_params, int32_t dtype, void* stream) {
+  VDQN_CHECK(n_img > 0 && frames_per_sample > 0 && n_params > 0, "%s: n_img %d, frames_per_sample %d, n_params %d must be > 0", name, n_img,
+             frames_per_sample, n_params);
+  VDQN_CHECK(dtype == VDQN_F32 || dtype == VDQN_BF16, "%s: bad dtype", name);
+  VDQN_CHECK((((uintptr_t)src | (uintptr_t)dst | (uintptr_t)params | (uintptr_t)color | (uintptr_t)affine) & 15) == 0,
+             "%s: src, dst, params, color and affine must be 16-byte aligned", name);
+  ProfScope ps_(name + 5, 0.0, (double)n_img * (224.0 * 224 * 3 + 115.0 * 115 * 16 * (dtype == VDQN_BF16 ? 2 : 4)), (hipStream_t)stream);
+  const int4 *p = (const int4*)params, *c = (const int4*)color, *a = (const int4*)affine;
+  const dim3 grid(kAffineTiles * kAffineTiles, n_img);
+  if (dtype == VDQN_BF16)
+    hipLaunchKernelGGL((c ? pack_affine_kernel<bf16raw, true> : pack_affine_kernel<bf16raw, false>), grid, dim3(256), 0, (hipStream_t)stream,
+                       (const uint8_t*)src, (bf16raw*)dst, (int)frames_per_sample, p, c, a, (int)n_params);
+  else
+    hipLaunchKernelGGL((c ? pack_affine_kernel<float, true> : pack_affine_kernel<float, false>), grid, dim3(256), 0, (hipStream_t)stream,
+                       (const uint8_t*)src, (float*)dst, (int)frames_per_sample, p, c, a, (int)n_params);
+  VDQN_LAUNCH_CHECK();
+  return VDQN_OK;
+}
+
 }  // namespace
 
 extern "C" int vdqn_aug_draw(uint64_t seed, uint64_t step, int32_t global_batch, int32_t first, int32_t n, int32_t pad, int32_t flip,
@@ -408,4 +622,25 @@ extern "C" int vdqn_pack_input_aug_zoom(const void* src, void* dst, int32_t n_im
   VDQN_CHECK(src && dst && params && zoom, "vdqn_pack_input_aug_zoom: null arg");
   return launch_pack_aug("vdqn_pack_input_aug_zoom", "src, dst, params, color and zoom", src, dst, n_img, frames_per_sample, params, color, zoom,
                          n_params, dtype, stream);
+}
+
+// zoom NULL: the identity zoom row for every sample
+extern "C" int vdqn_aug_draw_rotate(uint64_t seed, uint64_t step, int32_t global_batch, int32_t first, int32_t n, int32_t jr, const int32_t* zoom,
+                                    int32_t* affine, void* stream) {
+  if (const int rc = check_draw("vdqn_aug_draw_rotate", "affine", affine, global_batch, first, n, jr >= 0 && jr <= kMaxJr,
+                                "vdqn_aug_draw_rotate: range %d outside [0, %d] (1 / 64 degree: int(J * 64 + 0.5), J in [0, 30])", jr, kMaxJr))
+    return rc;
+  VDQN_CHECK(((uintptr_t)zoom & 15) == 0, "vdqn_aug_draw_rotate: zoom must be 16-byte aligned");
+  ProfScope ps_("aug_draw_rotate", 0.0, (double)n * (zoom ? 48.0 : 32.0), (hipStream_t)stream);
+  hipLaunchKernelGGL(aug_draw_rotate_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, seed, step, (int)global_batch, (int)first,
+                     (int)n, (int)jr, (const int4*)zoom, (int4*)affine);
+  VDQN_LAUNCH_CHECK();
+  return VDQN_OK;
+}
+
+// colour NULL: none
+extern "C" int vdqn_pack_input_aug_affine(const void* src, void* dst, int32_t n_img, int32_t frames_per_sample, const int32_t* params,
+                                          const int32_t* color, const int32_t* affine, int32_t n_params, int32_t dtype, void* stream) {
+  VDQN_CHECK(src && dst && params && affine, "vdqn_pack_input_aug_affine: null arg");
+  return launch_pack_affine("vdqn_pack_input_aug_affine", src, dst, n_img, frames_per_sample, params, color, affine, n_params, dtype, stream);
 }

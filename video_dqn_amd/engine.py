@@ -695,9 +695,22 @@ class TDStepper:
                 _lib.check(self.lib.vdqn_pack_input(_ptr(na), int(nk), buf.data_ptr() + half, nf, dt, _stream()), "vdqn_pack_input")
         self._ahead = (self._frames_key(nb, na, nk), slot, (nb, na))  # (the tensors are kept alive until they are consumed)
 
+    def _pack_affine(self, before, after, augment, augment_color, augment_affine) -> int:
+        """Pack this update's frames with vdqn_pack_input_aug_affine on the current stream — `before` into the first half of packed-frame
+        buffer 0 and `after` (TD branch) into the second, with the same rows — and return the buffer's address for
+        vdqn_step_args.packed_frames: the struct has no field for affine rows, and every engine entry already reads packed frames."""
+        n = self.net
+        buf = self._packed_buffer(0)
+        nf = self.B * n.num_frames
+        dt = _lib.VDQN_BF16 if n.dtype_name == "bf16" else _lib.VDQN_F32
+        for src, off in ((before, 0),) if self.gtb else ((before, 0), (after, buf.numel() // 2)):
+            _lib.check(self.lib.vdqn_pack_input_aug_affine(_ptr(src), buf.data_ptr() + off, nf, n.num_frames, _ptr(augment), _ptr(augment_color),
+                                                           _ptr(augment_affine), self.B, dt, _stream()), "vdqn_pack_input_aug_affine")
+        return buf.data_ptr()
+
     def forward_backward(self, before, after, src_kind, act, rew, term, valid=None, gt=None, early_adam: bool = False, next_frames=None,
                          *, weights=None, td_error=None, augment=None, discount=None, augment_color=None, mc_return=None,
-                         augment_zoom=None):
+                         augment_zoom=None, augment_affine=None):
         """Everything of one update up to (and including) the gradient all-reduce; no optimiser step.
 
         early_adam (only `step` passes it: single process, no exchange, eval-mode BatchNorm): the optimiser update of stage 0 and stage 1 is
@@ -706,18 +719,29 @@ class TDStepper:
         the packed copies); `optimizer_step` then only covers what is left.  Same arithmetic, same results.
 
         weights, td_error, augment, discount, augment_color, augment_zoom: as `step` describes and validates them (vdqn_step_args.
-        sample_weight / sample_err / aug_params / sample_gamma / aug_color / aug_zoom); mc_return: vdqn_net_td_forward_mc's plain argument."""
+        sample_weight / sample_err / aug_params / sample_gamma / aug_color / aug_zoom); mc_return: vdqn_net_td_forward_mc's plain argument;
+        augment_affine: as `step` describes it — the frames are packed here with `augment` and `augment_color` and handed over as
+        vdqn_step_args.packed_frames, and the three aug_* pointers stay NULL."""
+        if augment_affine is not None:
+            self._check_affine(augment, augment_zoom, augment_affine, src_kind, next_frames)
         n = self.net
         self._adam_done = []
         self._clip_slots = 0
-        keep = (before, after, act, rew, term, valid, gt, weights, td_error, augment, discount, augment_color, mc_return, augment_zoom)  # keep inputs alive until the launches are queued
+        keep = (before, after, act, rew, term, valid, gt, weights, td_error, augment, discount, augment_color, mc_return, augment_zoom,
+                augment_affine)  # keep inputs alive until the launches are queued
         with torch.cuda.device(n.device):
-            a = self._args(before, after, src_kind, act, rew, term, valid if valid is not None else self._ones, gt, weights, td_error, augment,
-                           discount, augment_color, augment_zoom)
+            if augment_affine is None:
+                a = self._args(before, after, src_kind, act, rew, term, valid if valid is not None else self._ones, gt, weights, td_error, augment,
+                               discount, augment_color, augment_zoom)
+            else:
+                a = self._args(before, after, src_kind, act, rew, term, valid if valid is not None else self._ones, gt, weights, td_error,
+                               discount=discount)
             st = _stream()
-            ahead, self._ahead = self._ahead, None
+            ahead, self._ahead = self._ahead, None  # (with affine rows a pending pack-ahead, packed without them, is discarded here)
             slot = None
-            if ahead is not None and ahead[0] == self._frames_key(before, after, src_kind):
+            if augment_affine is not None:
+                a.packed_frames = self._pack_affine(before, after, augment, augment_color, augment_affine)
+            elif ahead is not None and ahead[0] == self._frames_key(before, after, src_kind):
                 slot = ahead[1]  # these frames were packed during the previous update (ordered in front of `st` by its last stage)
                 a.packed_frames = self._packed_buffer(slot).data_ptr()
             if self.algo is not None:
@@ -939,9 +963,23 @@ class TDStepper:
             raise _lib.VdqnError(f"TDStepper.step: {name} must be a contiguous {'f32' if dtype == torch.float32 else 'int32'} "
                                  f"{''.join(f'[{d}]' for d in shape)} device tensor")
 
+    def _check_affine(self, augment, augment_zoom, augment_affine, src_kind, next_frames):
+        """What `augment_affine` needs beside it; raised before anything is queued."""
+        if augment is None:
+            raise _lib.VdqnError("TDStepper.step: augment_affine needs augment as well (int32 zeros [B][4] = no shift, no mirror)")
+        if augment_zoom is not None:
+            raise _lib.VdqnError("TDStepper.step: augment_affine and augment_zoom are both given, but the affine rows already contain the zoom "
+                                 "(aug_draw_rotate composes them): pass augment_affine alone")
+        self._check_input("augment_affine", augment_affine, torch.int32, (self.B, 8))
+        self._check_input("augment", augment, torch.int32, (self.B, 4))
+        if src_kind != 0:
+            raise _lib.VdqnError(f"TDStepper.step: augment_affine takes uint8 NHWC frames (src_kind 0), not src_kind {src_kind}")
+        if next_frames is not None:
+            raise _lib.VdqnError("TDStepper.step: next_frames are packed ahead without the augmentation; pass one or the other")
+
     def step(self, before, after, src_kind, act, rew, term, valid=None, gt=None, finish_allreduce=None, next_frames=None,
              weights=None, td_error=None, augment=None, discount=None, augment_color=None, mc_return=None,
-             augment_zoom=None) -> torch.Tensor:
+             augment_zoom=None, augment_affine=None) -> torch.Tensor:
         """One iteration of the reference loop body (train_q_network.py:213-227).  Returns the device loss scalar
         (no host sync).
 
@@ -977,6 +1015,13 @@ class TDStepper:
         `augment`, which must be given as well (zeros = no shift), and with `augment_color` when that is given; the same for `before`
         and `after` (vdqn_step_args.aug_zoom, this update only).
 
+        augment_affine (video_dqn_amd/augment.py): int32 [B][8] {axx, axy, bx, 0, ayx, ayy, by, 0} on the device, each sample's rotation
+        composed with its zoom (Augmenter.affine) — needs `augment` as well (zeros = no shift), goes with `augment_color` and refuses
+        `augment_zoom` beside it (the rows contain the zoom).  vdqn_step_args has no field for them: the stepper packs `before` and
+        `after` itself with vdqn_pack_input_aug_affine, on this stream in front of the engine entry, into a packed-frame buffer of
+        its own (2 * B * F * 115 * 115 * 16 elements, allocated by the first such call) and hands that over as
+        vdqn_step_args.packed_frames; the aug_* pointers stay NULL.  uint8 NHWC frames (src_kind 0) only; this update only.
+
         mc_return (video_dqn_amd/mcreturn.py): f32 [B][num_classes] on the device, the Monte-Carlo return of every sampled row
         (ReturnTable.G at the sampled rows; with n-step returns still the sampled row's, the whole-episode return against the n-step
         target).  Required exactly when the stepper was built with mc_floor or cql_calibrated; this update only.  A table of -inf
@@ -992,6 +1037,8 @@ class TDStepper:
         if augment_zoom is not None and augment is None:
             raise _lib.VdqnError("TDStepper.step: augment_zoom needs augment as well (int32 zeros [B][4] = no shift, no mirror)")
         self._check_input("augment_zoom", augment_zoom, torch.int32, (self.B, 4))
+        if augment_affine is not None:
+            self._check_affine(augment, augment_zoom, augment_affine, src_kind, next_frames)
         if discount is not None and (self.gtb or self.linear):
             raise _lib.VdqnError("TDStepper.step: discount applies to the TD branch without LINEAR (TRAIN_ON_GROUND_TRUTH bootstraps "
                                  "nothing; y = r + (Qa - 0.1) has no discount)")
@@ -1026,7 +1073,7 @@ class TDStepper:
         early = _EARLY_ADAM and self.net.extra_capacity and self.allreduce is None and finish_allreduce is None and self.grad_clip_norm == 0
         self.forward_backward(before, after, src_kind, act, rew, term, valid, gt, early_adam=early, next_frames=next_frames,
                               weights=weights, td_error=td_error, augment=augment, discount=discount, augment_color=augment_color, augment_zoom=augment_zoom,
-                              mc_return=mc_return)
+                              mc_return=mc_return, augment_affine=augment_affine)
         if finish_allreduce is not None:
             finish_allreduce()
             self._clip_slots = 0  # the gradient has just been reduced: its norm is taken from what `grads` holds now

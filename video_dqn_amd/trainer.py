@@ -19,7 +19,7 @@ import torch
 from torch.utils import data
 
 from . import algos
-from .augment import COLOR_KEYS, Augmenter, jz
+from .augment import COLOR_KEYS, Augmenter, jr, jz
 from .dataset import QLearningRealDataset, SyntheticTupleDataset
 from .dist import BucketAllReduce, agree_all, broadcast_replica_state
 from .engine import TDStepper
@@ -201,11 +201,11 @@ def check_prioritized_replay(config, world_size: int = 1) -> None:
                          "and DEVICE_RESIDENT_DATA is 'off'")
 
 
-def check_augment(pad, flip, flip_actions, brightness=0.0, contrast=0.0, saturation=0.0, zoom=0.0, zoom_aspect=False) -> None:
-    """AUG_SHIFT_PAD / AUG_FLIP / AUG_FLIP_ACTIONS / AUG_BRIGHTNESS / AUG_CONTRAST / AUG_SATURATION / AUG_ZOOM / AUG_ZOOM_ASPECT: raise
-    ValueError naming the key (before any device work)."""
+def check_augment(pad, flip, flip_actions, brightness=0.0, contrast=0.0, saturation=0.0, zoom=0.0, zoom_aspect=False, rotate=0.0) -> None:
+    """AUG_SHIFT_PAD / AUG_FLIP / AUG_FLIP_ACTIONS / AUG_BRIGHTNESS / AUG_CONTRAST / AUG_SATURATION / AUG_ZOOM / AUG_ZOOM_ASPECT / AUG_ROTATE:
+    raise ValueError naming the key (before any device work)."""
     from .augment import check_config
-    check_config(pad, flip, flip_actions, brightness, contrast, saturation, zoom, zoom_aspect)
+    check_config(pad, flip, flip_actions, brightness, contrast, saturation, zoom, zoom_aspect, rotate)
 
 
 def check_optim(config) -> None:
@@ -445,7 +445,8 @@ class LateScalar:
 def check_run(config, world_size: int = 1) -> None:
     """Every check of the config, before any device work.  The order decides which error a config with several meets first."""
     check_augment(getattr(config, "AUG_SHIFT_PAD", 0), getattr(config, "AUG_FLIP", False), getattr(config, "AUG_FLIP_ACTIONS", [1, 2]),
-                  *(getattr(config, k, 0.0) for k in COLOR_KEYS), getattr(config, "AUG_ZOOM", 0.0), getattr(config, "AUG_ZOOM_ASPECT", False))
+                  *(getattr(config, k, 0.0) for k in COLOR_KEYS), getattr(config, "AUG_ZOOM", 0.0), getattr(config, "AUG_ZOOM_ASPECT", False),
+                  getattr(config, "AUG_ROTATE", 0.0))
     check_optim(config)
     check_cql(config)
     check_target(config)
@@ -567,6 +568,7 @@ def build_helpers(config, dataset, store, model, comm, rank, world_size, log):
     aug_pad, aug_flip = getattr(config, "AUG_SHIFT_PAD", 0), getattr(config, "AUG_FLIP", False)
     aug_actions, aug_color = getattr(config, "AUG_FLIP_ACTIONS", [1, 2]), tuple(getattr(config, k, 0.0) for k in COLOR_KEYS)
     aug_zoom, aug_zoom_aspect = float(getattr(config, "AUG_ZOOM", 0.0)), bool(getattr(config, "AUG_ZOOM_ASPECT", False))
+    aug_rotate = float(getattr(config, "AUG_ROTATE", 0.0))
     lr_fn = None  # (when on, host arithmetic on the update number alone: a resumed run uses the uninterrupted run's rates)
     if schedule_active(getattr(config, "LR_WARMUP_STEPS", 0), getattr(config, "LR_SCHEDULE", "constant")):
         lr_fn = partial(lr_at, base=float(config.LEARNING_RATE), warmup=int(config.LR_WARMUP_STEPS), schedule=config.LR_SCHEDULE,
@@ -628,10 +630,10 @@ def build_helpers(config, dataset, store, model, comm, rank, world_size, log):
             (f" learning rate {config.LR_SCHEDULE} to {float(config.LR_FINAL_FRACTION):g} x LEARNING_RATE at {int(config.NUM_STEPS)}, "
              f"{int(config.LR_WARMUP_STEPS)} warm-up updates" if lr_fn is not None else ""))
     augmenter = None
-    if aug_pad > 0 or aug_flip or any(j > 0 for j in aug_color) or jz(aug_zoom) > 0:
+    if aug_pad > 0 or aug_flip or any(j > 0 for j in aug_color) or jz(aug_zoom) > 0 or jr(aug_rotate) > 0:
         augmenter = Augmenter(B, device, pad=aug_pad, flip=aug_flip, flip_actions=aug_actions, seed=int(config.SEED),
                               rank=rank, world_size=world_size, brightness=aug_color[0], contrast=aug_color[1], saturation=aug_color[2],
-                              zoom=aug_zoom, zoom_aspect=aug_zoom_aspect)
+                              zoom=aug_zoom, zoom_aspect=aug_zoom_aspect, rotate=aug_rotate)
         on = [f"random shift of up to {aug_pad} pixels"] if aug_pad > 0 or aug_flip else []
         if aug_flip:  # (one action column: nothing to exchange)
             on.append("random left-right mirror" + (f" with actions {aug_actions[0]} <-> {aug_actions[1]} exchanged" if model.engine.action_dim == 3 else ""))
@@ -640,6 +642,8 @@ def build_helpers(config, dataset, store, model, comm, rank, world_size, log):
         if augmenter.zoom is not None:
             on.append(f"random zoom to a window of [{1 - aug_zoom:g}, 1] of the frame" +
                       (", its two sides drawn independently" if aug_zoom_aspect else ""))
+        if augmenter.affine is not None:
+            on.append(f"random rotation by up to ±{aug_rotate:g}°")
         log("augmentation: " + ", ".join(on) + ", one draw per sample and update, shared by s and s'")
     return stepper, replay, walker, returns, augmenter
 
@@ -769,9 +773,11 @@ def run_train(config, resume_from=-1, max_steps=None, rank=0, world_size=1, log=
             model.set_train()  # :221 (flags only; the engine's BatchNorm is always in eval mode in extra_capacity)
             batch = next(iterator)
             act = batch.act
-            aug_params = aug_factors = aug_zoom = None
+            aug_params = aug_factors = aug_zoom = aug_affine = None
             if augmenter is not None:  # this update's draw(s) and the mirrored samples' action labels: small launches, nothing read back
-                aug_params, aug_factors, aug_zoom = augmenter.draw(sample_number), augmenter.color, augmenter.zoom
+                aug_params, aug_factors, aug_zoom, aug_affine = augmenter.draw(sample_number), augmenter.color, augmenter.zoom, augmenter.affine
+                if aug_affine is not None:  # the affine rows contain the zoom: the update takes them instead
+                    aug_zoom = None
                 if swap:
                     act = augmenter.actions(act.contiguous())
             # the stepper performs the :215-216 target refresh itself (sample_number % TARGET_UPDATE_INTERVAL == 0)
@@ -780,7 +786,7 @@ def run_train(config, resume_from=-1, max_steps=None, rank=0, world_size=1, log=
                                 batch.gt if config.TRAIN_ON_GROUND_TRUTH else None,
                                 finish_allreduce=(comm.finish if comm else None), weights=batch.weight,
                                 td_error=(replay.err if replay is not None else None), augment=aug_params, augment_color=aug_factors,
-                                augment_zoom=aug_zoom, discount=batch.discount, mc_return=batch.mc_return)
+                                augment_zoom=aug_zoom, augment_affine=aug_affine, discount=batch.discount, mc_return=batch.mc_return)
             if replay is not None:
                 replay.update()  # behind the loss launch (and, with N ranks, the error exchange that finish_allreduce joined)
             # every rank's `loss` is its share of the global mean (the TD kernel divides by the global batch): their SUM is the
