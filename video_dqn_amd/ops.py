@@ -188,9 +188,12 @@ def conv2d_wgrad(gy: torch.Tensor, x: torch.Tensor, *, co: int, r: int, s: int, 
     return (dw, db) if want_dbias else dw
 
 
-def pack_input(src: torch.Tensor, src_kind: int, n_img: int, dtype: torch.dtype) -> torch.Tensor:
+def pack_input(src: torch.Tensor, src_kind: int, n_img: int, dtype: torch.dtype, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out: a caller-allocated [n_img, 115, 115, 16] tensor of `dtype`, written in place of a fresh one (every element is written)."""
     lib = _lib.load()
-    dst = torch.empty((n_img, 115, 115, 16), dtype=dtype, device=src.device)
+    if out is not None:
+        _check_given("pack_input", "out", out, (n_img, 115, 115, 16), dtype, src.device)
+    dst = out if out is not None else torch.empty((n_img, 115, 115, 16), dtype=dtype, device=src.device)
     _lib.check(lib.vdqn_pack_input(_ptr(src), src_kind, _ptr(dst), n_img, dtype_code(dst), _stream()), "vdqn_pack_input")
     return dst
 
@@ -753,22 +756,33 @@ def avgpool_bwd(g: torch.Tensor, x: torch.Tensor) -> torch.Tensor:
 
 
 def stem_conv_pool(t_in: torch.Tensor, wt: torch.Tensor, bias: torch.Tensor, want_idx: bool = True, n_idx: int = None,
-                   precision: Optional[str] = None):
+                   precision: Optional[str] = None, pool: Optional[torch.Tensor] = None, idx: Optional[torch.Tensor] = None):
     """t_in [n,115,115,16] (pack_input), wt [64,4,1,64], bias f32 [64] -> (pool [n,56,56,64], idx uint8).
     precision="bf16x3" (f32 tensors): split bf16 x 3 MFMAs (gemm_dtype_code).
 
     want_idx=False: frames that never see a backward pass — idx is None and the arg-max bytes are not computed.
-    n_idx: arg-max bytes for the first n_idx images only (vdqn_stem_conv_pool_n); the other rows of idx stay as allocated."""
+    n_idx: arg-max bytes for the first n_idx images only (vdqn_stem_conv_pool_n); the other rows of idx stay as allocated.
+    pool / idx: caller-allocated outputs ([n,56,56,64] of t_in's dtype / of uint8) written in place of fresh tensors; what the call
+    does not write (the rows of idx from n_idx on) keeps the caller's bytes."""
     lib = _lib.load()
     n = t_in.shape[0]
     dt = gemm_dtype_code(t_in, precision)
-    pool = torch.empty((n, 56, 56, 64), dtype=t_in.dtype, device=t_in.device)
+    if pool is not None:
+        _check_given("stem_conv_pool", "pool", pool, (n, 56, 56, 64), t_in.dtype, t_in.device)
+    else:
+        pool = torch.empty((n, 56, 56, 64), dtype=t_in.dtype, device=t_in.device)
+    if idx is not None:
+        if not want_idx:
+            raise ValueError("stem_conv_pool: idx given with want_idx=False")
+        _check_given("stem_conv_pool", "idx", idx, (n, 56, 56, 64), torch.uint8, t_in.device)
     if n_idx is not None:
-        idx = torch.zeros((n, 56, 56, 64), dtype=torch.uint8, device=t_in.device)
+        if idx is None:
+            idx = torch.zeros((n, 56, 56, 64), dtype=torch.uint8, device=t_in.device)
         _lib.check(lib.vdqn_stem_conv_pool_n(_ptr(t_in), _ptr(wt), _ptr(bias), _ptr(pool), _ptr(idx), n, int(n_idx), dt, _stream()),
                    "vdqn_stem_conv_pool_n")
         return pool, idx
-    idx = torch.empty((n, 56, 56, 64), dtype=torch.uint8, device=t_in.device) if want_idx else None
+    if idx is None and want_idx:
+        idx = torch.empty((n, 56, 56, 64), dtype=torch.uint8, device=t_in.device)
     _lib.check(lib.vdqn_stem_conv_pool(_ptr(t_in), _ptr(wt), _ptr(bias), _ptr(pool), _ptr(idx) if want_idx else None, n, dt, _stream()),
                "vdqn_stem_conv_pool")
     return pool, idx
